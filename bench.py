@@ -16,10 +16,12 @@ up to 32 of them per pass over the volume with the voxels held in registers (bit
 updates per second, bound by instruction issue instead of HBM); it is reported beside the headline.
 
 Timing: the depth frame(s) are resident in HBM before the timed region.  After the warm-up (at least --warmup steps
-and two full launches) the K-step sequence is repeated until at least 0.3 s of device time has been timed, between
-a barrier + torch.cuda.synchronize() on both sides; ms_per_step = wall / (K x repeats), max over ranks; HIP events
-on the handle's stream give the kernel time.  For N > 1 every rank owns one z-slab (no data-path collective; by
-default WEAK scaling: each rank's slab holds as many voxels as the whole N = 1 grid); after the timed region the
+and two full launches, then the K-step sequence once untimed) exactly K = --steps steps are timed, between a barrier +
+torch.cuda.synchronize() on both sides; ms_per_step = wall / K, max over ranks; HIP events on the handle's stream give
+the kernel time.  With the same arguments every run integrates the same frames in the same order, so --dump-outputs DIR
+(what the volume holds after the last timed step, as DIR/<name>.npy) can be compared output for output between builds.
+For N > 1 every rank owns one z-slab (no data-path collective; by default WEAK scaling: each rank's slab holds as many
+voxels as the whole N = 1 grid); after the timed region the
 ranks run the one-voxel halo exchange (RCCL) and the halo-fed extraction once and report its time; if that step does
 not come back within 120 s, or raises, the line is still printed (with `extraction_hung` / `extraction.error`) and every
 rank exits non-zero (3 = hung, 4 = failed), so a dead wire shows in the record.  Launch with torch.distributed.run as
@@ -43,7 +45,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md, HBM)
-MIN_TIMED_MS = 300.0       # the K-step sequence is repeated until this much device time has been timed
+DUMP_BYTES = 64 * 2 ** 20   # --dump-outputs: at most this many bytes of .npy files in all
+DUMP_SEED = 20240917       # --dump-outputs: the fixed seed of the voxel sample when a slab's outputs exceed DUMP_BYTES
 
 
 def parse():
@@ -94,6 +97,10 @@ def parse():
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--depth-cache", default="", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget for the CPU baseline sample")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the volume holds after the last of them -- TSDF and weight (and the label "
+                         "state with --labels) -- as DIR/<name>.npy, float32, at most 64 MB in all: when the slab is larger, the same "
+                         "seeded stratified sample of its voxels in every run (N > 1: one set of files per rank, <name>_rank<r>.npy, 64 MB / N each)")
     a = ap.parse_args()
     a.grid_given = bool(a.grid)
     if not a.grid:
@@ -212,6 +219,21 @@ def grid_for(args, world):
             dims[2] *= part_world
             vs = vs / part_world
     return tuple(dims), vs, part_world, scaling
+
+
+def dump_outputs(out_dir, arrays, suffix="", budget=DUMP_BYTES):
+    """Write {name: 1-D per-voxel array} as out_dir/<name><suffix>.npy in float32, `budget` bytes in all: whole when they fit,
+    else every array at the same m voxels -- one per stratum of n / m consecutive voxels, its offset drawn with DUMP_SEED."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    m = min(n, (budget - 4096 * len(arrays)) // (4 * len(arrays)))      # 4096: room for the .npy headers
+    idx = None
+    if m < n:
+        stride = n // m
+        idx = np.arange(m, dtype=np.int64) * stride + np.random.default_rng(DUMP_SEED).integers(0, stride, m)
+    for name, a in arrays.items():
+        assert len(a) == n
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.ascontiguousarray(a if idx is None else a[idx], dtype=np.float32))
 
 
 def grid_label(dims):
@@ -553,43 +575,37 @@ def main():
 
     on_dev = "cpu" if backend == "gloo" else "cuda"
 
-    def timed_region(v, K, Wl=None, ddev=None, min_ms=MIN_TIMED_MS):
-        """The contract's timed region on handle v: warm-up (at least --warmup steps, two full launches, 8 steps), a calibration
-        block, then the K-step sequence `repeats` times between barrier + synchronize fences.  Returns (wall seconds and kernel
-        milliseconds, both max over ranks; steps timed; repeats; frames integrated into v so far; warm-up steps)."""
+    def timed_region(v, K, Wl=None, ddev=None):
+        """The contract's timed region on handle v: warm-up (at least --warmup steps, two full launches, 8 steps, then the K-step
+        sequence once), then exactly K steps between barrier + synchronize fences.  Returns (wall seconds and kernel
+        milliseconds, both max over ranks; steps timed; frames integrated into v so far; warm-up steps)."""
         Wl, ddev = Wl or W, ddev or d_dev
         fpl_ = v.frames_per_launch
         n_warm = max(args.warmup, 2 * fpl_, 8)
         own = (None, None) if (Wl is W and ddev is d_dev) else (Wl, ddev)
         run_block(v, 0, n_warm, *own)
-        cal_ms = run_block(v, n_warm, K, *own)         # calibration block (also warm): how long K steps take
+        run_block(v, n_warm, K, *own)                  # the timed sequence once, untimed: clocks up, per-launch decisions settled
         done = n_warm + K
-        repeats = max(1, int(math.ceil(1.2 * min_ms / max(cal_ms, 1e-3))))   # 20 % margin: the calibration block may run slow
-        if dist is not None:   # every rank times the same number of blocks
-            rt = torch.tensor([repeats], dtype=torch.int64, device=on_dev)
-            dist.all_reduce(rt, op=dist.ReduceOp.MAX)
-            repeats = int(rt[0])
-        # one call: the repeats' launches are queued back to back on the handle's stream (a call per repeat left the device
-        # idle for ~0.4 ms between repeats while the host drained, returned and came back: 5 % at --steps 20); with a depth frame
-        # per pose the call's arguments (K x repeats device pointers and poses) are marshalled ahead of the timed region
+        # one call: the K steps' launches are queued back to back on the handle's stream; with a depth frame per pose the
+        # call's arguments (K device pointers and poses) are marshalled ahead of the timed region
         timed_call = None
         if len(ddev) > 1 and not (args.labels > 0 and v is vol):
-            poses_t, idx_t = Wl.block(done, K * repeats)
+            poses_t, idx_t = Wl.block(done, K)
             timed_call = v.frames_timed_call([ddev[i].data_ptr() for i in idx_t], poses_t)
         fence()
         t0 = time.perf_counter()
-        k_ms = timed_call() if timed_call is not None else run_block(v, done, K * repeats, None if Wl is W else Wl, None if ddev is d_dev else ddev)
+        k_ms = timed_call() if timed_call is not None else run_block(v, done, K, None if Wl is W else Wl, None if ddev is d_dev else ddev)
         fence()
         wall_ = time.perf_counter() - t0
         tt = torch.tensor([wall_, k_ms], dtype=torch.float64, device=on_dev)
         if dist is not None:
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        return float(tt[0]), float(tt[1]), K * repeats, repeats, done + K * repeats, n_warm
+        return float(tt[0]), float(tt[1]), K, done + K, n_warm
 
-    def check_full_coverage(v, Wl, done, what):
+    def check_full_coverage(v, Wl, done, what, downloaded=None):
         """The promise of the S-band / S-full workloads, asserted on the device's result: every voxel of the slab updated by
         every frame (and, S-band, every TSDF value inside the truncation band).  Returns (updates per frame, slab voxels)."""
-        t_h, w_h = v.download()
+        t_h, w_h = downloaded if downloaded is not None else v.download()
         upd = float(w_h.astype(np.float64).sum())       # each update adds exactly 1 to one weight
         if Wl.full_coverage:
             assert w_h.min() == w_h.max() == float(done), f"{what}: full coverage means every voxel every frame"
@@ -600,10 +616,21 @@ def main():
         return upd / done, v.n_voxels
 
     K = args.steps
-    wall, kernel_ms_total, timed_steps, repeats, frames_done, n_warm = timed_region(vol, K)
+    wall, kernel_ms_total, timed_steps, frames_done, n_warm = timed_region(vol, K)
+
+    # ---- what the timed path computed: the volume after its last step (--dump-outputs) --------------------------
+    t_out = vol.download()
+    if args.dump_outputs:
+        outs = {"tsdf": t_out[0], "weight": t_out[1]}
+        if args.labels > 0:
+            lab, fp, bp = vol.download_labels()
+            outs.update(label=lab, label_fp=fp, label_bp=bp)
+        dump_outputs(args.dump_outputs, outs, f"_rank{rank}" if world > 1 else "", DUMP_BYTES // world)
+        del outs
 
     # ---- what was integrated: count updates on this rank's slab ------------------------------------------------
-    n_upd_per_frame, n_slab = check_full_coverage(vol, W, frames_done, "headline")
+    n_upd_per_frame, n_slab = check_full_coverage(vol, W, frames_done, "headline", t_out)
+    del t_out
     # several frames per pass over a scene with free / unseen space: what a launch touches (its voxels updated by at least one
     # of its frames) is counted, not bounded -- every launch of one pass over the step sequence on a fresh volume, weights > 0
     # counted on the device; per fpl frames, like the measured traffic it is compared with
@@ -639,7 +666,7 @@ def main():
         szb, sze = rank * sd[2] // world, (rank + 1) * sd[2] // world
         with capi.Volume(capi.make_config(sd, svs, Ws.origin, trunc=Ws.trunc, z_begin=szb, z_end=sze, device=local_rank)) as sv_:
             sv_.set_kernel_variant(3)
-            s_wall, s_kms, s_steps, s_rep, s_done, _ = timed_region(sv_, K, Ws, s_dev, min_ms=150.0)
+            s_wall, s_kms, s_steps, s_done, _ = timed_region(sv_, K, Ws, s_dev)
             check_full_coverage(sv_, Ws, s_done, "strong_512")
             slab_bytes = 8 * sv_.n_voxels
         n_s = sd[0] * sd[1] * sd[2]
@@ -749,7 +776,7 @@ def main():
         # up to fpl frames per pass with the voxels held in registers: a launch has to read and write each voxel it
         # touches once, whatever the number of its frames that update it, and to read each of its depth frames once
         full, rem = divmod(K, fpl)
-        launches = (full + (1 if rem else 0)) * repeats
+        launches = full + (1 if rem else 0)
         frames_per = K / (full + (1 if rem else 0))
         units_per_launch = touched_per_launch if touched_per_launch is not None else min(float(n_slab), frames_per * n_upd_per_frame)
         alg_bytes = 16.0 * units_per_launch + frames_per * frame_bytes
@@ -824,9 +851,9 @@ def main():
                                 + (f"; single-GPU rehearsal of rank {args.emulate_rank} of {part_world} (value = this slab's rate)"
                                    if args.emulate_world > 1 and world == 1 else ""),
                    "mode": args.mode, "kernel_variant": variant, "frames_per_launch": fpl},
-        "timing": {"timed_steps": timed_steps, "repeats": repeats, "timed_region_s": round(wall, 4),
+        "timing": {"timed_steps": timed_steps, "timed_region_s": round(wall, 4),
                    "kernel_s": round(kernel_ms_total * 1e-3, 4), "warmup_steps_run": n_warm + K,
-                   "note": f"the {K}-step sequence is repeated until >= {MIN_TIMED_MS / 1e3:g} s of device time; ms_per_step = "
+                   "note": f"exactly the {K} steps of --steps are timed, after the warm-up; ms_per_step = "
                            "wall / timed_steps between barrier + synchronize fences, max over ranks"},
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None if traffic is None else int(traffic),

@@ -6,6 +6,7 @@
   * one rank over RCCL (`--dist-world1`): the same code path -- process group on RCCL, barriers, all-reduces on device
     tensors, the halo step (no neighbour), extraction, `multi_gpu` -- on the real library.
   * a halo step that raises / never returns: the line is still printed, the process exits 4 / 3.
+  * --steps times exactly that many steps, and --dump-outputs writes the same arrays in every run with the same arguments.
 Short runs (--steps 5, no companion legs, no PMC passes, no CPU baseline)."""
 import json
 import os
@@ -13,6 +14,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -48,6 +50,29 @@ def test_one_gpu_line_keeps_the_contract(cuda):
     assert r["algorithmic_bytes_per_unit"] == 16 and r["units_per_launch"] == 512 ** 3
     # value = voxels x steps / time
     assert abs(d["value"] - 512 ** 3 / d["ms_per_step"] / 1e3) / d["value"] < 2e-3
+
+
+def test_steps_are_timed_exactly_and_outputs_are_reproducible(cuda, tmp_path):
+    """Two runs with the same arguments: --steps 5 timed steps each, and the volume after the last of them written as float32
+    .npy (a seeded sample of the 256^3 S-band grid, 64 MB in all) -- the same bits both times, every sampled voxel updated by
+    every frame the run integrated (warm-up of 8, the 5-step sequence once untimed, then the 5 timed steps)."""
+    runs = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        rc, lines, err = run([sys.executable, "bench.py", "--grid", "256", "--dump-outputs", str(out)] + QUICK)
+        assert rc == 0, err
+        d = json.loads(lines[0])
+        assert d["steps"] == 5 and d["timing"]["timed_steps"] == 5
+        assert abs(5 * d["ms_per_step"] - d["timing"]["timed_region_s"] * 1e3) <= 0.051      # timed_region_s is rounded to 0.1 ms
+        assert sorted(os.listdir(out)) == ["tsdf.npy", "weight.npy"]
+        assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64 * 2 ** 20
+        runs.append({f: np.load(out / f) for f in ("tsdf.npy", "weight.npy")})
+    for f, a in runs[0].items():
+        assert a.dtype == np.float32 and 2 ** 22 < a.size < 256 ** 3, (f, a.dtype, a.size)
+        assert np.array_equal(a.view(np.uint32), runs[1][f].view(np.uint32)), f
+    assert np.all(runs[0]["weight.npy"] == 18.0)
+    t = runs[0]["tsdf.npy"]
+    assert 0.0 < t.min() and t.max() < 1.0
 
 
 def test_two_ranks_as_the_driver_launches_them(cuda):

@@ -91,9 +91,15 @@ def test_product_pose_math_equals_oracle_bitwise(oracle):
 
 
 # ---- against the reference's own two functions, compiled as they stand (oracle/_ref/libtsdf_ref_host.so) ------------------
+# What they returned on these inputs is stored (tests/golden/ref_pose_math.npz); where oracle/_ref was built they are also
+# run live and checked against what is stored.
 from oracle.oracle import RefHost  # noqa: E402
+from ref_vectors import Stored  # noqa: E402
 
-needs_ref_host = pytest.mark.skipif(not RefHost.available(), reason="oracle/_ref/libtsdf_ref_host.so not built (make -C oracle ref_host)")
+
+@pytest.fixture(scope="module")
+def stored():
+    return Stored("pose_math")
 
 
 def _matrices(rng, n):
@@ -125,25 +131,74 @@ def _same_bits(a, b):
     return np.array_equal(np.asarray(a, f32).view(np.uint32), np.asarray(b, f32).view(np.uint32))
 
 
-@needs_ref_host
-def test_multiply_equals_the_references_function_bit_for_bit(oracle):
-    ref = RefHost()
-    rng = np.random.default_rng(253)
-    ms = _matrices(rng, 4000)
-    for a, b in zip(ms[::2], ms[1::2]):
-        want = ref.multiply(a, b)
+def multiply_inputs():
+    ms = _matrices(np.random.default_rng(253), 4000)
+    return list(zip(ms[::2], ms[1::2]))
+
+
+def invert_inputs():
+    return _matrices(np.random.default_rng(276), 4000)
+
+
+def composition_inputs():
+    rng = np.random.default_rng(142)
+    out = []
+    for _ in range(500):
+        base, cam = synth.random_pose(rng, 0.8, 3.0), synth.random_pose(rng, 0.8, 3.0)
+        out.append((base, cam))
+    return out
+
+
+def reference_multiply(ref, pairs):
+    return np.stack([ref.multiply(a, b) for a, b in pairs])
+
+
+def reference_invert(ref, ms):
+    res = [ref.invert(m) for m in ms]
+    return np.array([ok for ok, _ in res]), np.stack([inv for _, inv in res])
+
+
+def reference_composition(ref, pairs):
+    """TSDF::TSDF inverts the base pose once (ref: src/tsdf.cu:74), TSDF::Integrate multiplies base2world_inv x cam2world
+    (ref: src/tsdf.cu:142): the same two calls on the reference's own functions."""
+    ok, want = [], []
+    for base, cam in pairs:
+        o, inv = ref.invert(base)
+        ok.append(o)
+        want.append(ref.multiply(inv, cam))
+    return np.array(ok), np.stack(want)
+
+
+def _stored_or_live(stored, key, inputs, live):
+    """The reference's results: stored, and -- where oracle/_ref was built -- recomputed live and required to match them."""
+    stored.check_inputs(key, *inputs)
+    keys = [k for k in (key + "/ok", key + "/want") if k in stored.d]
+    want = tuple(stored[k] for k in keys)
+    if RefHost.available():
+        got = live(RefHost())
+        got = got if isinstance(got, tuple) else (got,)
+        assert len(got) == len(want) and all(np.array_equal(np.asarray(g).view(np.uint8), np.asarray(w).view(np.uint8))
+                                             for g, w in zip(got, want)), f"{key}: the live reference differs from its stored results"
+    return want
+
+
+def test_multiply_equals_the_references_function_bit_for_bit(oracle, stored):
+    pairs = multiply_inputs()
+    (wants,) = _stored_or_live(stored, "multiply", [np.stack([a for a, _ in pairs]), np.stack([b for _, b in pairs])],
+                               lambda ref: reference_multiply(ref, pairs))
+    assert len(wants) == len(pairs)
+    for (a, b), want in zip(pairs, wants):
         assert _same_bits(oracle.multiply(a, b), want) or (np.isnan(want).any() and np.array_equal(np.isnan(oracle.multiply(a, b)), np.isnan(want)))
         got = capi.multiply_matrix(a, b)
         assert _same_bits(got, want) or (np.isnan(want).any() and np.array_equal(np.isnan(got), np.isnan(want)))
 
 
-@needs_ref_host
-def test_invert_equals_the_references_function_bit_for_bit(oracle):
-    ref = RefHost()
-    rng = np.random.default_rng(276)
+def test_invert_equals_the_references_function_bit_for_bit(oracle, stored):
+    ms = invert_inputs()
+    oks, invs = _stored_or_live(stored, "invert", [np.stack(ms)], lambda ref: reference_invert(ref, ms))
+    assert len(oks) == len(ms)
     n_singular = 0
-    for m in _matrices(rng, 4000):
-        ok_r, inv_r = ref.invert(m)
+    for m, ok_r, inv_r in zip(ms, oks, invs):
         ok_o, inv_o = oracle.invert(m)
         ok_p, inv_p = capi.invert_matrix(m)
         assert ok_o == ok_r and ok_p == ok_r
@@ -156,14 +211,13 @@ def test_invert_equals_the_references_function_bit_for_bit(oracle):
     assert n_singular > 100, "the singular branch (det == 0 -> false, ref: src/tsdf.cu:392-393) should be exercised"
 
 
-@needs_ref_host
-def test_pose_composition_equals_the_references_two_calls(oracle):
+def test_pose_composition_equals_the_references_two_calls(oracle, stored):
     """TSDF::TSDF inverts the base pose once (ref: src/tsdf.cu:74), TSDF::Integrate multiplies base2world_inv x cam2world
     (ref: src/tsdf.cu:142): the same two calls on the reference's own functions."""
-    ref = RefHost()
-    rng = np.random.default_rng(142)
-    for _ in range(500):
-        base, cam = synth.random_pose(rng, 0.8, 3.0), synth.random_pose(rng, 0.8, 3.0)
-        ok, inv = ref.invert(base)
+    pairs = composition_inputs()
+    oks, wants = _stored_or_live(stored, "composition", [np.stack([b for b, _ in pairs]), np.stack([c for _, c in pairs])],
+                                 lambda ref: reference_composition(ref, pairs))
+    assert len(wants) == len(pairs)
+    for (base, cam), ok, want in zip(pairs, oks, wants):
         assert ok
-        assert _same_bits(oracle.cam2base(base, cam), ref.multiply(inv, cam))
+        assert _same_bits(oracle.cam2base(base, cam), want)

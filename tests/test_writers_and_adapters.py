@@ -4,9 +4,9 @@ src/Engine.cpp:192-193 masking) of the CPU oracle."""
 import struct
 
 import numpy as np
-import pytest
 
 from oracle.oracle import RefHost
+from ref_vectors import Stored, digest
 from semantic_slam_amd import synth
 
 
@@ -58,13 +58,8 @@ def test_ply_format_and_surface_rule(oracle, tmp_path):
     assert raw.startswith(head) and raw[len(head):] == pts.tobytes()
 
 
-@pytest.mark.skipif(not RefHost.available(), reason="oracle/_ref/libtsdf_ref_host.so not built (make -C oracle ref_host)")
-def test_ply_equals_the_references_own_writer_byte_for_byte(oracle, tmp_path):
-    """The oracle's writer against TSDF::SaveVoxelGrid2SurfacePointCloud itself (ref: src/tsdf.cu:170-218, compiled as it
-    stands: oracle/ref_host_driver.cpp), called as ~TSDF calls it (ref: src/tsdf.cu:110-112): the surface rule, the point
-    order, the coordinates' arithmetic and the header, byte for byte -- on an integrated volume and on arrays that hold the
-    rule's edge cases (TSDF +0 / -0 / NaN / denormal, weights around the 0.9 threshold, NaN weights)."""
-    ref = RefHost()
+def ply_cases(oracle):
+    """Inputs of test_ply_equals_the_references_own_writer_byte_for_byte: (dims, voxel size, origin, tsdf, weight) each."""
     rng = np.random.default_rng(170)
     cases = [small_volume(oracle)]
     for dims in ((1, 1, 1), (7, 5, 3), (32, 9, 4), (3, 40, 2)):
@@ -74,12 +69,32 @@ def test_ply_equals_the_references_own_writer_byte_for_byte(oracle, tmp_path):
                                  np.nan, -1.0], np.float32), n).astype(np.float32)
         cases.append((dims, 0.013, np.array([-0.31, 0.2, 1.7], np.float32), t, w))
     cases.append(((4, 4, 4), 0.02, np.zeros(3, np.float32), np.ones(64, np.float32), np.zeros(64, np.float32)))   # no point at all
-    for k, (dims, vs, origin, t, w) in enumerate(cases):
-        a, b = tmp_path / f"oracle{k}.ply", tmp_path / f"ref{k}.ply"
+    return cases
+
+
+def ply_case_inputs(dims, vs, origin, t, w):
+    return [np.array(dims), np.array([vs]), np.asarray(origin), t, w]
+
+
+def test_ply_equals_the_references_own_writer_byte_for_byte(oracle, tmp_path):
+    """The oracle's writer against TSDF::SaveVoxelGrid2SurfacePointCloud itself (ref: src/tsdf.cu:170-218, compiled as it
+    stands: oracle/ref_host_driver.cpp), called as ~TSDF calls it (ref: src/tsdf.cu:110-112): the surface rule, the point
+    order, the coordinates' arithmetic and the header, byte for byte -- on an integrated volume and on arrays that hold the
+    rule's edge cases (TSDF +0 / -0 / NaN / denormal, weights around the 0.9 threshold, NaN weights).  The reference's files
+    are stored (tests/golden/ref_writers.npz: digest and length of each); where oracle/_ref was built the writer also runs live."""
+    stored = Stored("writers")
+    for k, (dims, vs, origin, t, w) in enumerate(ply_cases(oracle)):
+        stored.check_inputs(f"ply{k}", *ply_case_inputs(dims, vs, origin, t, w))
+        a = tmp_path / f"oracle{k}.ply"
         oracle.save_ply(str(a), t, w, dims, vs, origin)
-        ref.save_ply(str(b), t, w, dims, vs, origin)
-        assert a.read_bytes() == b.read_bytes(), f"case {k}: dims {dims}"
-        assert len(oracle.surface_points(t, w, dims, vs, origin)) * 12 + len(b.read_bytes().split(b"end_header\n")[0]) + 11 == len(b.read_bytes())
+        if RefHost.available():
+            b = tmp_path / f"ref{k}.ply"
+            RefHost().save_ply(str(b), t, w, dims, vs, origin)
+            assert digest(b.read_bytes()) == stored.str(f"ply{k}"), f"case {k}: the live reference differs from its stored file"
+            assert a.read_bytes() == b.read_bytes(), f"case {k}: dims {dims}"
+        want_len = int(stored[f"ply{k}/len"])
+        assert len(a.read_bytes()) == want_len and digest(a.read_bytes()) == stored.str(f"ply{k}"), f"case {k}: dims {dims}"
+        assert len(oracle.surface_points(t, w, dims, vs, origin)) * 12 + len(a.read_bytes().split(b"end_header\n")[0]) + 11 == want_len
 
 
 def test_object_origin_rule(oracle):
