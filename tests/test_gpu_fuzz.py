@@ -5,34 +5,10 @@ against the oracle."""
 import numpy as np
 import pytest
 
+from fuzz_cases import random_case  # noqa: F401  (tools/fuzz_stress.py reaches it through this module)
 from semantic_slam_amd import capi, synth
 
 pytestmark = pytest.mark.gpu
-
-
-def random_case(seed):
-    rng = np.random.default_rng(1000 + seed)
-    shape_class = seed % 5
-    if shape_class == 0:
-        dims = (256 * int(rng.integers(1, 3)), int(rng.integers(3, 20)), int(rng.integers(2, 12)))   # row-mapped kernels
-    elif shape_class == 1:
-        dims = (4 * int(rng.integers(1, 90)), int(rng.integers(1, 40)), int(rng.integers(1, 20)))    # flat mapping
-    elif shape_class == 2:
-        dims = (int(rng.integers(1, 70)) | 1, int(rng.integers(1, 30)), int(rng.integers(1, 20)))    # odd rows: scalar kernel
-    elif shape_class == 3:
-        dims = (4, int(rng.integers(1, 5)), int(rng.integers(1, 5)))                                 # less than one chunk
-    else:
-        dims = (int(rng.integers(8, 40)) * 4, int(rng.integers(8, 40)), int(rng.integers(8, 30)))
-    h, w = int(rng.integers(24, 200)), int(rng.integers(32, 260))
-    K = np.array([rng.uniform(30, 400), 0, w / 2 + rng.uniform(-10, 10), 0, rng.uniform(30, 400),
-                  h / 2 + rng.uniform(-10, 10), 0, 0, 1], np.float32)
-    vs = float(rng.choice([0.003, 0.01, 0.02, 0.05]))
-    ext = np.array(dims) * vs
-    # volume placed so that cameras can end up inside, behind or beside it
-    origin = (rng.uniform(-1.0, 0.2, 3) * ext + np.array([0, 0, rng.uniform(-0.5, 1.5)])).astype(np.float32)
-    trunc = float(np.float32(vs) * np.float32(rng.choice([2, 5, 9])))
-    max_depth = float(rng.choice([6.0, 2.5, 10.0]))
-    return rng, dims, h, w, K, vs, origin, trunc, max_depth
 
 
 # 0: classification decided per launch, 7: never, 8: always (bricks per wavefront), 11: always (rows per workgroup)
