@@ -120,6 +120,7 @@ struct tsdf_volume {
     float pend_c2b[16 * tsdfk::kMaxFramesPerLaunch];
     const uint8_t *pend_mask[tsdfk::kMaxFramesPerLaunch];   // instance masks of collected masked frames (in the store's mask slots)
     int variant;
+    int sweep_parity;        // direction of the next integrate_tile sweep (flips every launch; a performance hint only)
     // per-launch frame blocks of integrate_multi: pinned host ring -> device ring (allocated on first use)
     tsdfk::FramePose *h_frames[kStageSlots];
     tsdfk::FramePose *d_frames[kStageSlots];
@@ -582,6 +583,32 @@ int launch_single_experiment(tsdf_volume *v, tsdfk::IntegrateParams &common, tsd
                              const float *c2b, bool *handled);
 #endif
 
+// Infinity Cache window of the one-frame kernel (integrate_tile, IntegrateParams::cache_lo/hi): successive launches sweep z
+// in alternate directions and the last slices of each sweep, up to kWindowBytes of TSDF + weight state, are loaded and
+// stored with the default cache policy (the rest streams non-temporal), so the next launch starts on lines still in the
+// 256 MiB Infinity Cache.  Chosen by measurement (tools/window_sweep.py, profiles/r05_window_sweep.txt), S-band 512^3,
+// ms per frame with a window of 0 / 128 / 256 / 384 / 512 / 768 / 1024 MiB: 0.3317 / 0.3242 / 0.3205 / 0.3177 / 0.3161 /
+// 0.3182 / 0.3230 (forward sweeps, no window: 0.3319); loading the slices before the window with the default policy too
+// was slower (0.3232 at 64-192 MiB).  A slab whose state fits the window is swept cacheable throughout.
+constexpr int64_t kWindowBytes = 512ll << 20;
+
+void set_sweep(tsdf_volume *v, tsdfk::IntegrateParams &p)
+{
+    int64_t window = kWindowBytes;
+    bool forward_only = false;
+#ifdef TSDF_EXPERIMENTS
+    if (const char *e = std::getenv("TSDF_MALL_WINDOW_MB")) window = (int64_t)std::atoi(e) << 20;    // A/B knobs of the measurement build
+    forward_only = std::getenv("TSDF_SWEEP_FORWARD") && std::atoi(std::getenv("TSDF_SWEEP_FORWARD")) != 0;
+    p.head_plain_loads = std::getenv("TSDF_HEAD_PLAIN_LOADS") && std::atoi(std::getenv("TSDF_HEAD_PLAIN_LOADS")) != 0;
+#endif
+    const int64_t slice_bytes = 8 * (int64_t)p.dim_x * p.dim_y;
+    const int w = (int)std::min<int64_t>(p.nz, window / slice_bytes);
+    p.sweep_reverse = forward_only ? 0 : v->sweep_parity;
+    v->sweep_parity ^= 1;
+    p.cache_lo = p.sweep_reverse ? 0 : p.nz - w;
+    p.cache_hi = p.sweep_reverse ? w : p.nz;
+}
+
 // Queue one Integrate launch.  Shapes are validated at tsdf_create, so the grid covers exactly
 // the slab and every access stays inside the two allocations.
 int launch_integrate(tsdf_volume *v, const float *depth_dev, const uint8_t *mask_dev,
@@ -622,9 +649,11 @@ int launch_integrate(tsdf_volume *v, const float *depth_dev, const uint8_t *mask
 #ifdef TSDF_EXPERIMENTS
             if (v->variant == 11 && classify_one_frame(v, v->n_vox) && tiles_fit(p)) return launch_integrate_experiment(v, depth_dev, mask_dev, c2b);
 #endif
+            set_sweep(v, p);
             hipLaunchKernelGGL((tsdfk::integrate_tile<2, true>), grid, block, 0, v->stream, p);
         }
     } else {
+        set_sweep(v, p);
         hipLaunchKernelGGL((tsdfk::integrate_tile<2, false>), grid, block, 0, v->stream, p);
     }
     HIP_TRY(hipGetLastError());

@@ -17,6 +17,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace tsdfk {
 
@@ -90,6 +91,15 @@ struct IntegrateParams {
     // 1 = every voxel updated with dist = 1, 2 = no voxel updated.  Index = linear workgroup id of the launch.
     // Null = not classified.
     const uint8_t *wg_class;
+    // Sweep order of integrate_tile (a performance hint only: every voxel's update reads its own state, the frame and the
+    // pose, so no order changes a bit of the result).  sweep_reverse: the launch's z index runs nz-1 .. 0.  Slices
+    // [cache_lo, cache_hi) -- the last of the sweep -- load and store the volume with the default cache policy, so the
+    // next launch, which sweeps the other way, finds them in the Infinity Cache; every other slice streams (non-temporal).
+    int sweep_reverse = 0;
+    int cache_lo = 0, cache_hi = 0;
+#ifdef TSDF_EXPERIMENTS
+    int head_plain_loads = 0;   // measurement build: the slices before the window load with the default policy too
+#endif
 };
 
 // Terms of the camera-frame point that do not depend on x (shared by a lane's voxels).
@@ -183,7 +193,9 @@ __global__ __launch_bounds__(256) void integrate_scalar(IntegrateParams p)
 //      - a row whose TSDF values all come out bit-identical to what was loaded is not stored
 //        (the weight always changes and is always stored).
 //    Every skipped value is the value the full computation would produce, bit for bit.
-//  * volume loads/stores carry the non-temporal hint (each byte is touched once per frame).
+//  * volume loads/stores carry the non-temporal hint (each byte is touched once per frame), except in the last slices
+//    of the sweep (IntegrateParams::cache_lo/hi): successive launches sweep z in alternate directions, and those
+//    slices, loaded and stored with the default policy, are the first the next launch reads.
 //  * free-space summary.  A wavefront's row is one 256-voxel segment with one flag word;
 //    while the flag says "all TSDF == 1" the TSDF quad is not loaded -- the constant 1 stands
 //    in for it and the same arithmetic runs on it -- so free space moves 8 B per voxel, not 12.
@@ -289,6 +301,19 @@ __device__ __forceinline__ void vol_store(float *p, float4 v)
     }
 }
 
+// The policy as a compile-time constant (std::true_type / std::false_type) or as a wave-uniform run-time flag (a scalar
+// branch around the one instruction).
+template <bool NT>
+__device__ __forceinline__ float4 vol_load_p(std::integral_constant<bool, NT>, const float *p) { return vol_load<NT>(p); }
+__device__ __forceinline__ float4 vol_load_p(bool nt, const float *p) { return nt ? vol_load<true>(p) : vol_load<false>(p); }
+template <bool NT>
+__device__ __forceinline__ void vol_store_p(std::integral_constant<bool, NT>, float *p, float4 v) { vol_store<NT>(p, v); }
+__device__ __forceinline__ void vol_store_p(bool nt, float *p, float4 v)
+{
+    if (nt) vol_store<true>(p, v);
+    else vol_store<false>(p, v);
+}
+
 // depth[px] through a 32-bit byte offset from the wave-uniform base: the load takes the base from SGPRs
 // and the offset from one VGPR (global_load_dword v, v_off, s[base]) instead of a 64-bit address built
 // per voxel.  px < 2^30 pixels (tsdf_create refuses larger images), so px * 4 does not wrap.
@@ -305,8 +330,10 @@ __device__ __forceinline__ int pixel_index24(int iv, int W, int iu)
 }
 
 // MASKED: 0 = plain depth, 1 = depth * (mask/255) (p.mask must be set).
+// lnt / snt (wave-uniform): volume loads / stores carry the non-temporal hint.
 template <int R, int MASKED>
-__device__ __forceinline__ void integrate_tile_body(const IntegrateParams &p, const int bx, const int by, const int lz)
+__device__ __forceinline__ void integrate_tile_body(const IntegrateParams &p, const int bx, const int by, const int lz,
+                                                    const bool lnt, const bool snt)
 {
     const int gz = p.z_begin + lz;
     const int xg = bx * 64 + threadIdx.x;
@@ -451,8 +478,9 @@ __device__ __forceinline__ void integrate_tile_body(const IntegrateParams &p, co
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         if (rowany[r]) {
-            w4[r] = vol_load<true>(p.weight + row0 + (size_t)r * p.dim_x);
-            if (!(fl[r] & 1u)) t4[r] = vol_load<true>(p.tsdf + row0 + (size_t)r * p.dim_x);
+            const float *wp = p.weight + row0 + (size_t)r * p.dim_x, *tp = p.tsdf + row0 + (size_t)r * p.dim_x;
+            w4[r] = vol_load_p(lnt, wp);
+            if (!(fl[r] & 1u)) t4[r] = vol_load_p(lnt, tp);
         }
     }
     float dist[R][4];
@@ -469,63 +497,82 @@ __device__ __forceinline__ void integrate_tile_body(const IntegrateParams &p, co
     }
 
     // ---- phase 4: running weighted mean (ref: src/tsdf.cu:54-57), stores ----------------------
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        if (fl[r] == 3u && __ballot(bandr[r]) == 0ull) {
-            // Free space, wave-uniform: every TSDF value of the segment is 1, every weight is finite
-            // and >= 0, and every updated lane has dist == 1.  Then num = fl(1*w + 1) = fl(w + 1) = wn,
-            // the quotient is exactly 1, the TSDF row is unchanged: only the weights move.
-            if (rowany[r]) {
-                const float4 w = w4[r];
-                vol_store<true>(p.weight + row0 + (size_t)r * p.dim_x,
-                                make_float4(upd[r][0] ? w.x + 1.0f : w.x, upd[r][1] ? w.y + 1.0f : w.y,
-                                            upd[r][2] ? w.z + 1.0f : w.z, upd[r][3] ? w.w + 1.0f : w.w));
+    auto store_rows = [&](auto snt_c) {
+    #pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (fl[r] == 3u && __ballot(bandr[r]) == 0ull) {
+                // Free space, wave-uniform: every TSDF value of the segment is 1, every weight is finite
+                // and >= 0, and every updated lane has dist == 1.  Then num = fl(1*w + 1) = fl(w + 1) = wn,
+                // the quotient is exactly 1, the TSDF row is unchanged: only the weights move.
+                if (rowany[r]) {
+                    const float4 w = w4[r];
+                    vol_store_p(snt_c, p.weight + row0 + (size_t)r * p.dim_x,
+                                    make_float4(upd[r][0] ? w.x + 1.0f : w.x, upd[r][1] ? w.y + 1.0f : w.y,
+                                                upd[r][2] ? w.z + 1.0f : w.z, upd[r][3] ? w.w + 1.0f : w.w));
+                }
+                continue;
             }
-            continue;
+            float tv[4] = {t4[r].x, t4[r].y, t4[r].z, t4[r].w};
+            float wv[4] = {w4[r].x, w4[r].y, w4[r].z, w4[r].w};
+            float num[4], wn[4];
+            bool need = false;
+    #pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                wn[j] = wv[j] + 1.0f;
+                num[j] = tv[j] * wv[j] + dist[r][j];
+                // x / x == 1 exactly for finite non-zero x (wn >= 1 whenever the weights are counts)
+                need |= upd[r][j] && !(num[j] == wn[j] && wn[j] < 3.0e38f && wn[j] > 0.0f);
+            }
+            float nt[4];
+            if (__ballot(rowany[r] && need) != 0ull) {
+    #pragma unroll
+                for (int j = 0; j < 4; ++j) nt[j] = num[j] / wn[j];
+            } else {
+    #pragma unroll
+                for (int j = 0; j < 4; ++j) nt[j] = 1.0f;
+            }
+            bool changed = false, notone = false;
+    #pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float newt = upd[r][j] ? nt[j] : tv[j];
+                changed |= __float_as_uint(newt) != __float_as_uint(tv[j]);
+                notone |= upd[r][j] && __float_as_uint(newt) != 0x3f800000u;
+                tv[j] = newt;
+                wv[j] = upd[r][j] ? wn[j] : wv[j];
+            }
+            if ((fl[r] & 1u) && __ballot(notone) != 0ull) {
+                if (notone) p.flags[flag0 + (size_t)r * p.nseg] = fl[r] & 2u;  // segment no longer all ones
+            }
+            const bool store_t = __ballot(rowany[r] && changed) != 0ull;
+            if (rowany[r]) {
+                if (store_t) vol_store_p(snt_c, p.tsdf + row0 + (size_t)r * p.dim_x, make_float4(tv[0], tv[1], tv[2], tv[3]));
+                vol_store_p(snt_c, p.weight + row0 + (size_t)r * p.dim_x, make_float4(wv[0], wv[1], wv[2], wv[3]));
+            }
         }
-        float tv[4] = {t4[r].x, t4[r].y, t4[r].z, t4[r].w};
-        float wv[4] = {w4[r].x, w4[r].y, w4[r].z, w4[r].w};
-        float num[4], wn[4];
-        bool need = false;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            wn[j] = wv[j] + 1.0f;
-            num[j] = tv[j] * wv[j] + dist[r][j];
-            // x / x == 1 exactly for finite non-zero x (wn >= 1 whenever the weights are counts)
-            need |= upd[r][j] && !(num[j] == wn[j] && wn[j] < 3.0e38f && wn[j] > 0.0f);
-        }
-        float nt[4];
-        if (__ballot(rowany[r] && need) != 0ull) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) nt[j] = num[j] / wn[j];
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) nt[j] = 1.0f;
-        }
-        bool changed = false, notone = false;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float newt = upd[r][j] ? nt[j] : tv[j];
-            changed |= __float_as_uint(newt) != __float_as_uint(tv[j]);
-            notone |= upd[r][j] && __float_as_uint(newt) != 0x3f800000u;
-            tv[j] = newt;
-            wv[j] = upd[r][j] ? wn[j] : wv[j];
-        }
-        if ((fl[r] & 1u) && __ballot(notone) != 0ull) {
-            if (notone) p.flags[flag0 + (size_t)r * p.nseg] = fl[r] & 2u;  // segment no longer all ones
-        }
-        const bool store_t = __ballot(rowany[r] && changed) != 0ull;
-        if (rowany[r]) {
-            if (store_t) vol_store<true>(p.tsdf + row0 + (size_t)r * p.dim_x, make_float4(tv[0], tv[1], tv[2], tv[3]));
-            vol_store<true>(p.weight + row0 + (size_t)r * p.dim_x, make_float4(wv[0], wv[1], wv[2], wv[3]));
-        }
+    };
+    // Register allocation, measured: a branch per store costs the masked kernel 7 VGPRs (53), one branch around all
+    // of this phase costs the plain kernel 7 (53); each kernel takes the form that keeps it at 46.
+    if constexpr (MASKED == 1) {
+        if (snt) store_rows(std::true_type{});
+        else store_rows(std::false_type{});
+    } else {
+        store_rows(snt);
     }
 }
 
 template <int R, bool MASKED>
 __global__ __launch_bounds__(256) void integrate_tile(IntegrateParams p)
 {
-    integrate_tile_body<R, MASKED ? 1 : 0>(p, blockIdx.x, blockIdx.y, blockIdx.z);
+    // z of the launch index -> slice: reversed every other launch (blocks are dispatched in launch-index order, so the
+    // sweep starts at the slices the previous launch ended with).  The policy is uniform over the workgroup.
+    const int lz = p.sweep_reverse ? p.nz - 1 - (int)blockIdx.z : (int)blockIdx.z;
+    const bool cached = lz >= p.cache_lo && lz < p.cache_hi;
+#ifdef TSDF_EXPERIMENTS
+    const bool lnt = !cached && !p.head_plain_loads;
+#else
+    const bool lnt = !cached;
+#endif
+    integrate_tile_body<R, MASKED ? 1 : 0>(p, blockIdx.x, blockIdx.y, lz, lnt, !cached);
 }
 
 // Device self-test of fast_div2 against the compiler's IEEE division: pseudo-random operands from a
