@@ -425,6 +425,37 @@ int tsdf_integrate_rgbd(tsdf_volume *vol, const float *depth_host, const uint8_t
 int tsdf_download_colour(tsdf_volume *vol, uint32_t *colour_host);
 
 /*
+ * Raycasting: what the fused model looks like from a camera -- per pixel the depth of the first zero crossing of the TSDF
+ * along the pixel's ray, the surface normal there (camera frame, toward the camera), and the fused label and colour of the
+ * voxel nearest to it.  Not a reference function (its front end asks this of sparse ObjectPoints, ref: src/Engine.cpp:356-496);
+ * the rule is stated exactly in csrc/tsdf_raycast.hip.h and restated in tests/raycast_spec.py.  A miss gives depth 0,
+ * normal (0, 0, 0), label 0, colour 0.  Every call applies the handle's (or batch's) collected frames first and reads the
+ * volume only: the TSDF, the weights, the summary words, labels and colours are not written.  Whole-grid handles only (a
+ * z-slab or a tsdf_group is refused); every dim must be >= 2.
+ *   near_m, far_m      0 <= near < far, both finite: the camera-depth range the ray is marched over
+ *   weight_thresh      a voxel counts as observed when its weight is > this
+ * tsdf_raycast_params_default: the config's K and image size, near 0, far = max_depth, weight_thresh 0.9 (the extraction
+ * default).  Host arithmetic only: needs no device.
+ */
+typedef struct tsdf_raycast_params {
+    float cam_K[9];            /* row-major 3x3 */
+    int32_t im_height, im_width;
+    float near_m, far_m;
+    float weight_thresh;
+} tsdf_raycast_params;
+
+int tsdf_raycast_params_default(const tsdf_config *cfg, tsdf_raycast_params *out);
+/*
+ * Device outputs, each may be NULL but not all: depth H*W floats (camera z, metres), normal H*W*3 floats, label H*W uint16
+ * (needs tsdf_labels_enable), colour H*W uint32 (needs tsdf_colour_enable).  Queued on the handle's stream (tsdf_set_stream).
+ */
+int tsdf_raycast_device(tsdf_volume *vol, const tsdf_raycast_params *p, const float cam2world[16], float *depth_dev,
+                        float *normal_dev, uint16_t *label_dev, uint32_t *colour_dev);
+/* The same into host memory; returns when the images are there. */
+int tsdf_raycast(tsdf_volume *vol, const tsdf_raycast_params *p, const float cam2world[16], float *depth_host,
+                 float *normal_host, uint16_t *label_host, uint32_t *colour_host);
+
+/*
  * Grid origin of a new object volume from its first (masked) depth frame, on the device: the per-axis
  * minimum over pixels with depth > 0 of the back-projected point, starting from 1000 -- what
  * Object::Object computes on the host before it constructs its TSDF (ref: src/Object.cpp:37-49, with the
@@ -462,6 +493,14 @@ int tsdf_batch_volume(tsdf_batch *batch, int32_t i, tsdf_volume **vol);
 int tsdf_batch_integrate_device(tsdf_batch *batch, const float *depth_dev, const uint8_t *const *masks_dev,
                                 const float cam2world[16]);
 int tsdf_batch_sync(tsdf_batch *batch);
+/*
+ * Every member of the batch rendered into one image (tsdf_raycast rule per member, with that member's own cam2base, voxel
+ * size and truncation): per pixel the nearest hit wins, ties go to the lower member index; member_dev = that index or -1.
+ * depth / normal are the winning member's own bits.  Device outputs, each may be NULL but not all; queued on the batch's
+ * stream after its collected frames.
+ */
+int tsdf_batch_raycast_device(tsdf_batch *batch, const tsdf_raycast_params *p, const float cam2world[16], float *depth_dev,
+                              float *normal_dev, int32_t *member_dev);
 
 /*
  * One grid over several devices in ONE process.  The reference's host is a C++ program that owns its TSDFs directly

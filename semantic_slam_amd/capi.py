@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "tsdf_labels_enable", "tsdf_compose_labels", "tsdf_integrate_labels_device", "tsdf_integrate_frames_labels_device",
     "tsdf_download_labels",
     "tsdf_colour_enable", "tsdf_integrate_colour_device", "tsdf_integrate_rgbd", "tsdf_download_colour",
+    "tsdf_raycast_params_default", "tsdf_raycast_device", "tsdf_raycast", "tsdf_batch_raycast_device",
     "tsdf_object_origin", "tsdf_batch_create", "tsdf_batch_destroy", "tsdf_batch_size", "tsdf_batch_volume",
     "tsdf_batch_integrate_device", "tsdf_batch_sync",
     "tsdf_group_create", "tsdf_group_destroy", "tsdf_group_size", "tsdf_group_voxels", "tsdf_group_volume",
@@ -66,6 +67,14 @@ class TsdfConfig(C.Structure):
         ("voxel_size", C.c_float), ("trunc_margin", C.c_float), ("max_depth", C.c_float),
         ("origin", C.c_float * 3), ("cam_K", C.c_float * 9), ("base2world", C.c_float * 16),
         ("device", C.c_int32), ("id", C.c_int32),
+    ]
+
+
+class RaycastParams(C.Structure):
+    """Mirror of `struct tsdf_raycast_params` (include/tsdf_hip.h)."""
+    _fields_ = [
+        ("cam_K", C.c_float * 9), ("im_height", C.c_int32), ("im_width", C.c_int32),
+        ("near_m", C.c_float), ("far_m", C.c_float), ("weight_thresh", C.c_float),
     ]
 
 
@@ -156,6 +165,10 @@ def load():
     L.tsdf_integrate_colour_device.argtypes = [vp, vp, vp, vp]
     L.tsdf_integrate_rgbd.argtypes = [vp, vp, vp, vp]
     L.tsdf_download_colour.argtypes = [vp, vp]
+    L.tsdf_raycast_params_default.argtypes = [C.POINTER(TsdfConfig), C.POINTER(RaycastParams)]
+    L.tsdf_raycast_device.argtypes = [vp, C.POINTER(RaycastParams), vp, vp, vp, vp, vp]
+    L.tsdf_raycast.argtypes = [vp, C.POINTER(RaycastParams), vp, vp, vp, vp, vp]
+    L.tsdf_batch_raycast_device.argtypes = [vp, C.POINTER(RaycastParams), vp, vp, vp, vp]
     L.tsdf_object_origin.argtypes = [C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp]
     L.tsdf_batch_create.argtypes = [C.POINTER(TsdfConfig), C.c_int32, C.POINTER(vp)]
     L.tsdf_batch_destroy.argtypes = [vp]
@@ -260,6 +273,13 @@ def object_origin(depth_ptr, mask_ptr, h, w, K, device=0):
     out = np.empty(3, np.float32)
     check(load().tsdf_object_origin(device, depth_ptr, mask_ptr, h, w, k.ctypes.data, out.ctypes.data), "tsdf_object_origin")
     return out
+
+
+def raycast_params_default(cfg):
+    """Raycast parameters from a config: its K and image size, near 0, far = max_depth, weight_thresh 0.9 (no device)."""
+    p = RaycastParams()
+    check(load().tsdf_raycast_params_default(C.byref(cfg), C.byref(p)), "tsdf_raycast_params_default")
+    return p
 
 
 def selftest_round(device=0):
@@ -559,6 +579,33 @@ class Volume:
         check(self.lib.tsdf_download_colour(self._h, out.ctypes.data), "tsdf_download_colour")
         return out
 
+    # -- raycasting -------------------------------------------------------------------------
+    def raycast(self, cam2world, params=None, normals=True, labels=False, colour=False):
+        """Render the volume from cam2world (csrc/tsdf_raycast.hip.h): dict of host arrays "depth" [H, W] float32 and, as
+        asked, "normal" [H, W, 3] float32 (camera frame), "label" [H, W] uint16, "colour" [H, W] uint32.  params: a
+        RaycastParams, default raycast_params_default(cfg)."""
+        p = raycast_params_default(self.cfg) if params is None else params
+        h, w = p.im_height, p.im_width
+        out = {"depth": np.empty((h, w), np.float32)}
+        if normals:
+            out["normal"] = np.empty((h, w, 3), np.float32)
+        if labels:
+            out["label"] = np.empty((h, w), np.uint16)
+        if colour:
+            out["colour"] = np.empty((h, w), np.uint32)
+        ptr = lambda k: out[k].ctypes.data if k in out else None
+        c2w = _f32(cam2world, 16)
+        check(self.lib.tsdf_raycast(self._h, C.byref(p), c2w.ctypes.data, ptr("depth"), ptr("normal"), ptr("label"),
+                                    ptr("colour")), "tsdf_raycast")
+        return out
+
+    def raycast_device(self, cam2world, depth_ptr, normal_ptr=None, label_ptr=None, colour_ptr=None, params=None):
+        """The same into device buffers (pointers, each may be None), queued on the handle's stream."""
+        p = raycast_params_default(self.cfg) if params is None else params
+        c2w = _f32(cam2world, 16)
+        check(self.lib.tsdf_raycast_device(self._h, C.byref(p), c2w.ctypes.data, depth_ptr, normal_ptr, label_ptr, colour_ptr),
+              "tsdf_raycast_device")
+
     # -- outputs ----------------------------------------------------------------------------
     def count_surface(self, weight_thresh=0.9):
         n = C.c_int64()
@@ -662,6 +709,14 @@ class Batch:
 
     def sync(self):
         check(self.lib.tsdf_batch_sync(self._h), "tsdf_batch_sync")
+
+    def raycast_device(self, cam2world, depth_ptr, normal_ptr=None, member_ptr=None, params=None):
+        """Every member into one image (nearest hit wins, ties to the lower index; member -1 = miss), device pointers (each
+        may be None), queued on the batch's stream.  params default: raycast_params_default of the first member's config."""
+        p = raycast_params_default(self.cfgs[0]) if params is None else params
+        c2w = _f32(cam2world, 16)
+        check(self.lib.tsdf_batch_raycast_device(self._h, C.byref(p), c2w.ctypes.data, depth_ptr, normal_ptr, member_ptr),
+              "tsdf_batch_raycast_device")
 
     def close(self):
         if self._h:

@@ -32,6 +32,7 @@
 #include "tsdf_labels.hip.h"
 #include "tsdf_colour.hip.h"
 #include "tsdf_extract.hip.h"
+#include "tsdf_raycast.hip.h"
 #ifdef TSDF_EXPERIMENTS
 #include "tsdf_experiments.hip.h"
 #endif
@@ -230,6 +231,11 @@ struct tsdf_batch {
     hipStream_t side[kBatchSideStreams];
     hipEvent_t side_done[kBatchSideStreams];
     hipEvent_t collected;
+    // the members as tsdf_batch_raycast_device's kernel reads them: pinned host block -> HBM (allocated on first use); the host
+    // block is refilled only after the copy out of it (ray_copied) has run
+    tsdfk::RayVolume *h_ray = nullptr, *d_ray = nullptr;
+    hipEvent_t ray_copied = nullptr;
+    bool ray_used = false;
 };
 
 namespace {
@@ -2445,6 +2451,9 @@ int tsdf_batch_destroy(tsdf_batch *b)
         if (b->side_done[i]) (void)hipEventDestroy(b->side_done[i]);
     }
     if (b->collected) (void)hipEventDestroy(b->collected);
+    if (b->h_ray) (void)hipHostFree(b->h_ray);
+    if (b->d_ray) (void)hipFree(b->d_ray);
+    if (b->ray_copied) (void)hipEventDestroy(b->ray_copied);
     if (b->d_depth_pool) (void)hipFree(b->d_depth_pool);
     if (b->d_mask_pool) (void)hipFree(b->d_mask_pool);
     if (b->stream) (void)hipStreamDestroy(b->stream);
@@ -3002,6 +3011,180 @@ int tsdf_load_state(tsdf_volume *v, const char *path)
     std::fclose(fp);
     if (!ok) return fail(TSDF_ERR_IO, "tsdf_load_state: %s does not hold the state of this slab", path);
     return tsdf_upload(v, t.data(), w.data());
+}
+
+// ---------------------------------------------------------------------------------------------
+// raycasting (csrc/tsdf_raycast.hip.h states the rule)
+// ---------------------------------------------------------------------------------------------
+static int ray_params_ok(const char *who, const tsdf_raycast_params *p)
+{
+    if (!p) return fail(TSDF_ERR_INVALID, "%s: NULL parameters", who);
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(p->cam_K[i])) return fail(TSDF_ERR_INVALID, "%s: cam_K[%d] is not finite", who, i);
+    if (p->cam_K[0] == 0.0f || p->cam_K[4] == 0.0f) return fail(TSDF_ERR_INVALID, "%s: fx and fy must be non-zero", who);
+    if (p->im_height <= 0 || p->im_width <= 0 || (p->im_height + 15) / 16 > 65535 ||
+        (int64_t)p->im_height * p->im_width > (int64_t)1 << 30)
+        return fail(TSDF_ERR_INVALID, "%s: bad image size %dx%d", who, p->im_height, p->im_width);
+    if (!std::isfinite(p->near_m) || !std::isfinite(p->far_m) || !(p->near_m >= 0.0f) || !(p->near_m < p->far_m))
+        return fail(TSDF_ERR_INVALID, "%s: need 0 <= near < far, both finite (near %g, far %g)", who, (double)p->near_m,
+                    (double)p->far_m);
+    return TSDF_OK;
+}
+
+static int ray_volume_ok(const char *who, const tsdf_volume *v)
+{
+    const tsdf_config &c = v->cfg;
+    if (c.z_begin != 0 || c.z_end != c.dim_z)
+        return fail(TSDF_ERR_INVALID, "%s: the handle is the z-slab [%d,%d) of %d slices; raycasting needs a whole-grid handle",
+                    who, c.z_begin, c.z_end, c.dim_z);
+    if (c.dim_x < 2 || c.dim_y < 2 || c.dim_z < 2)
+        return fail(TSDF_ERR_INVALID, "%s: every dim must be >= 2 (%d,%d,%d)", who, c.dim_x, c.dim_y, c.dim_z);
+    return TSDF_OK;
+}
+
+// The volume as the march sees it, under the relative pose c2b (host float32 arithmetic: go and s_free are part of the rule).
+static tsdfk::RayVolume ray_volume(const tsdf_volume *v, const float c2b[16])
+{
+    const tsdf_config &c = v->cfg;
+    tsdfk::RayVolume V;
+    V.tsdf = v->d_tsdf;
+    V.weight = v->d_weight;
+    const int dims[3] = {c.dim_x, c.dim_y, c.dim_z};
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) V.r[3 * i + j] = c2b[4 * i + j];
+        V.go[i] = (c2b[4 * i + 3] - c.origin[i]) / c.voxel_size;
+        V.hi[i] = (float)(dims[i] - 1);
+        V.dim[i] = dims[i];
+    }
+    V.vs = c.voxel_size;
+    V.s_free = 0.8f * c.trunc_margin;
+    V.max_steps = (int)std::min<int64_t>(2 * ((int64_t)c.dim_x + c.dim_y + c.dim_z) + 8, INT32_MAX);
+    return V;
+}
+
+extern "C++" template <typename P>
+static void ray_camera(P &k, const tsdf_raycast_params *p)
+{
+    k.fx = p->cam_K[0]; k.fy = p->cam_K[4]; k.cx = p->cam_K[2]; k.cy = p->cam_K[5];
+    k.near_m = p->near_m; k.far_m = p->far_m; k.wthr = p->weight_thresh;
+    k.H = p->im_height; k.W = p->im_width;
+}
+
+static dim3 ray_grid(const tsdf_raycast_params *p) { return dim3((p->im_width + 15) / 16, (p->im_height + 15) / 16); }
+
+static int raycast_checks(const char *who, tsdf_volume *v, const tsdf_raycast_params *p, const float *cam2world, bool any_out,
+                          bool want_label, bool want_colour)
+{
+    if (!v || !cam2world) return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
+    if (!any_out) return fail(TSDF_ERR_INVALID, "%s: every output is NULL", who);
+    int rc = ray_params_ok(who, p);
+    if (rc == TSDF_OK) rc = ray_volume_ok(who, v);
+    if (rc) return rc;
+    if (want_label && !v->d_label) return fail(TSDF_ERR_INVALID, "%s: a label image needs tsdf_labels_enable", who);
+    if (want_colour && !v->d_colour) return fail(TSDF_ERR_INVALID, "%s: a colour image needs tsdf_colour_enable", who);
+    return bind_device(v);   // the collected frames first
+}
+
+static int launch_raycast(tsdf_volume *v, const tsdf_raycast_params *p, const float cam2world[16], float *depth, float *normal,
+                          uint16_t *label, uint32_t *colour)
+{
+    float c2b[16];
+    compose_cam2base(v, cam2world, c2b);
+    tsdfk::RaycastParams k;
+    k.vol = ray_volume(v, c2b);
+    k.label = v->d_label; k.colour = v->d_colour;
+    k.depth = depth; k.normal = normal; k.label_out = label; k.colour_out = colour;
+    ray_camera(k, p);
+    hipLaunchKernelGGL(tsdfk::raycast_volume, ray_grid(p), dim3(256), 0, v->stream, k);
+    HIP_TRY(hipGetLastError());
+    return TSDF_OK;
+}
+
+int tsdf_raycast_params_default(const tsdf_config *cfg, tsdf_raycast_params *out)
+{
+    if (!cfg || !out) return fail(TSDF_ERR_INVALID, "tsdf_raycast_params_default: NULL argument");
+    std::memcpy(out->cam_K, cfg->cam_K, sizeof out->cam_K);
+    out->im_height = cfg->im_height;
+    out->im_width = cfg->im_width;
+    out->near_m = 0.0f;
+    out->far_m = cfg->max_depth;
+    out->weight_thresh = 0.9f;
+    return TSDF_OK;
+}
+
+int tsdf_raycast_device(tsdf_volume *v, const tsdf_raycast_params *p, const float cam2world[16], float *depth_dev,
+                        float *normal_dev, uint16_t *label_dev, uint32_t *colour_dev)
+{
+    int rc = raycast_checks("tsdf_raycast_device", v, p, cam2world, depth_dev || normal_dev || label_dev || colour_dev,
+                            label_dev != nullptr, colour_dev != nullptr);
+    if (rc) return rc;
+    return launch_raycast(v, p, cam2world, depth_dev, normal_dev, label_dev, colour_dev);
+}
+
+int tsdf_raycast(tsdf_volume *v, const tsdf_raycast_params *p, const float cam2world[16], float *depth_host,
+                 float *normal_host, uint16_t *label_host, uint32_t *colour_host)
+{
+    int rc = raycast_checks("tsdf_raycast", v, p, cam2world, depth_host || normal_host || label_host || colour_host,
+                            label_host != nullptr, colour_host != nullptr);
+    if (rc) return rc;
+    // the images go through the handle's output list buffer (kept between calls), one copy each, then one wait
+    const size_t px = (size_t)p->im_height * p->im_width;
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t o_n = up(px * 4), o_l = o_n + up(px * 12), o_c = o_l + up(px * 2), bytes = o_c + px * 4;
+    rc = ensure_list(v, bytes);
+    if (rc) return rc;
+    char *base = static_cast<char *>(v->d_list);
+    float *d = depth_host ? reinterpret_cast<float *>(base) : nullptr;
+    float *n = normal_host ? reinterpret_cast<float *>(base + o_n) : nullptr;
+    uint16_t *l = label_host ? reinterpret_cast<uint16_t *>(base + o_l) : nullptr;
+    uint32_t *c = colour_host ? reinterpret_cast<uint32_t *>(base + o_c) : nullptr;
+    rc = launch_raycast(v, p, cam2world, d, n, l, c);
+    if (rc) return rc;
+    if (d) HIP_TRY(hipMemcpyAsync(depth_host, d, px * 4, hipMemcpyDeviceToHost, v->stream));
+    if (n) HIP_TRY(hipMemcpyAsync(normal_host, n, px * 12, hipMemcpyDeviceToHost, v->stream));
+    if (l) HIP_TRY(hipMemcpyAsync(label_host, l, px * 2, hipMemcpyDeviceToHost, v->stream));
+    if (c) HIP_TRY(hipMemcpyAsync(colour_host, c, px * 4, hipMemcpyDeviceToHost, v->stream));
+    HIP_TRY(hipStreamSynchronize(v->stream));
+    return TSDF_OK;
+}
+
+int tsdf_batch_raycast_device(tsdf_batch *b, const tsdf_raycast_params *p, const float cam2world[16], float *depth_dev,
+                              float *normal_dev, int32_t *member_dev)
+{
+    const char *who = "tsdf_batch_raycast_device";
+    if (!b || !cam2world) return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
+    if (!depth_dev && !normal_dev && !member_dev) return fail(TSDF_ERR_INVALID, "%s: every output is NULL", who);
+    int rc = ray_params_ok(who, p);
+    for (size_t i = 0; i < b->vols.size() && rc == TSDF_OK; ++i) rc = ray_volume_ok(who, b->vols[i]);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(b->device));
+    for (tsdf_volume *v : b->vols) {   // the batch's collected frames, then any a member collected through its own handle
+        rc = bind_device(v);
+        if (rc) return rc;
+    }
+    const int n = (int)b->vols.size();
+    if (!b->d_ray) {
+        HIP_TRY(hipHostMalloc((void **)&b->h_ray, n * sizeof(tsdfk::RayVolume), hipHostMallocDefault));
+        HIP_TRY(hipMalloc((void **)&b->d_ray, n * sizeof(tsdfk::RayVolume)));
+        HIP_TRY(hipEventCreateWithFlags(&b->ray_copied, hipEventDisableTiming));
+    }
+    if (b->ray_used) HIP_TRY(hipEventSynchronize(b->ray_copied));
+    for (int i = 0; i < n; ++i) {
+        float c2b[16];
+        compose_cam2base(b->vols[i], cam2world, c2b);   // each object has its own base frame (ref: src/Object.cpp:23-29)
+        b->h_ray[i] = ray_volume(b->vols[i], c2b);
+    }
+    HIP_TRY(hipMemcpyAsync(b->d_ray, b->h_ray, n * sizeof(tsdfk::RayVolume), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipEventRecord(b->ray_copied, b->stream));
+    b->ray_used = true;
+    tsdfk::BatchRaycastParams k;
+    k.members = b->d_ray;
+    k.n = n;
+    k.depth = depth_dev; k.normal = normal_dev; k.member = member_dev;
+    ray_camera(k, p);
+    hipLaunchKernelGGL(tsdfk::raycast_batch, ray_grid(p), dim3(256), 0, b->stream, k);
+    HIP_TRY(hipGetLastError());
+    return TSDF_OK;
 }
 
 }  // extern "C"
