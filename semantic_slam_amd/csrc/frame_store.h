@@ -19,7 +19,10 @@
 
 #include <mutex>
 #include <thread>
+#include <utility>
 #include <vector>
+
+#include "hip_owned.h"
 
 namespace tsdf_store {
 
@@ -28,36 +31,36 @@ constexpr int kSoftCapFrames = 160;    // frame slots (197 MB at 640 x 480) befo
 constexpr int kSoftCapTables = 16;     // table slots (9.2 MB each at 640 x 480): launches of that many handles may be in flight before one waits for another's
 
 struct Slot {
-    void *dev;
-    hipEvent_t *release;     // state 2: free again once this event (owned by the handle that used the slot) has happened
-    const void *owner;       // the handle holding it (state 1) or whose event it waits for (state 2)
-    int state;               // 0 free, 1 held, 2 in flight
-    unsigned long long seq;  // state 2: when it was released (the class's counter): the oldest is reused first
+    hip_owned::DevPtr<void> dev;
+    const hip_owned::Event *release = nullptr;   // state 2: free again once this event (owned by the handle that used the slot) has happened
+    const void *owner = nullptr;   // the handle holding it (state 1) or whose event it waits for (state 2)
+    int state = 0;                 // 0 free, 1 held, 2 in flight
+    unsigned long long seq = 0;    // state 2: when it was released (the class's counter): the oldest is reused first
 };
 
 struct RingSlot {
-    float *host;             // pinned, one float frame (also holds a 16-bit frame)
-    hipEvent_t copied;       // the last copy out of it
-    bool used, busy;
+    hip_owned::HostPtr<float> host;   // pinned, one float frame (also holds a 16-bit frame)
+    hip_owned::Event copied;          // the last copy out of it
+    bool used = false, busy = false;
 };
 
 struct SlotClass {
     std::vector<Slot> slots;
-    size_t bytes;
-    int soft_cap;
-    int quota;               // slots one handle may take before it reuses its own (stream-ordered) instead of growing the class
-    unsigned long long seq;
+    size_t bytes = 0;
+    int soft_cap = 0;
+    int quota = 0;           // slots one handle may take before it reuses its own (stream-ordered) instead of growing the class
+    unsigned long long seq = 0;
 };
 
 struct FrameStore {
-    int device;
-    size_t px;               // pixels per frame
-    int refs;
+    int device = 0;
+    size_t px = 0;           // pixels per frame
+    int refs = 0;
     std::mutex mu;
     RingSlot ring[kRingSlots];
-    int ring_next;
+    int ring_next = 0;
     SlotClass frames, masks, tables;
-    hipStream_t copy_stream;   // host -> device copies of every handle of the store (one PCIe pipe; a stream per handle cost ~2 MiB each)
+    hip_owned::Stream copy_stream;   // host -> device copies of every handle of the store (one PCIe pipe; a stream per handle cost ~2 MiB each)
 };
 
 inline std::mutex &registry_mutex() { static std::mutex m; return m; }
@@ -70,15 +73,12 @@ inline hipError_t store_ref(int device, size_t px, size_t table_bytes, FrameStor
     for (FrameStore *s : registry())
         if (s->device == device && s->px == px && s->tables.bytes == table_bytes) { ++s->refs; *out = s; return hipSuccess; }
     FrameStore *s = new FrameStore();
-    s->device = device; s->px = px; s->refs = 1; s->ring_next = 0;
-    s->frames.seq = s->masks.seq = s->tables.seq = 0;
+    s->device = device; s->px = px; s->refs = 1;
     s->frames.bytes = px * sizeof(float); s->frames.soft_cap = kSoftCapFrames; s->frames.quota = 64;
     s->masks.bytes = px; s->masks.soft_cap = kSoftCapFrames; s->masks.quota = 64;
     s->tables.bytes = table_bytes; s->tables.soft_cap = kSoftCapTables; s->tables.quota = 2;
-    s->copy_stream = nullptr;
-    for (int i = 0; i < kRingSlots; ++i) { s->ring[i].host = nullptr; s->ring[i].copied = nullptr; s->ring[i].used = s->ring[i].busy = false; }
     (void)hipSetDevice(device);
-    const hipError_t e = hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking);
+    const hipError_t e = hip_owned::stream_create(s->copy_stream);
     if (e != hipSuccess) { delete s; return e; }
     registry().push_back(s);
     *out = s;
@@ -91,16 +91,12 @@ inline void store_unref(FrameStore *s)
     std::lock_guard<std::mutex> lk(registry_mutex());
     if (--s->refs > 0) return;
     (void)hipSetDevice(s->device);
-    if (s->copy_stream) { (void)hipStreamSynchronize(s->copy_stream); (void)hipStreamDestroy(s->copy_stream); }
-    for (int i = 0; i < kRingSlots; ++i) {
-        if (s->ring[i].copied) { (void)hipEventSynchronize(s->ring[i].copied); (void)hipEventDestroy(s->ring[i].copied); }
-        if (s->ring[i].host) (void)hipHostFree(s->ring[i].host);
-    }
-    for (SlotClass *c : {&s->frames, &s->masks, &s->tables})
-        for (Slot &x : c->slots) if (x.dev) (void)hipFree(x.dev);
+    if (s->copy_stream) (void)hipStreamSynchronize(s->copy_stream);
+    for (RingSlot &slot : s->ring)
+        if (slot.copied) (void)hipEventSynchronize(slot.copied);
     auto &r = registry();
     for (size_t i = 0; i < r.size(); ++i) if (r[i] == s) { r.erase(r.begin() + (long)i); break; }
-    delete s;
+    delete s;   // (the copy stream, the pinned ring and the slots go with it)
 }
 
 // A pinned frame of the ring, ready to be written by the host (its previous copy has run).  Release with ring_release.
@@ -120,9 +116,12 @@ inline hipError_t ring_acquire(FrameStore *s, int *index)
     }
     RingSlot &r = s->ring[i];
     hipError_t e = hipSuccess;
-    if (!r.host) {
-        e = hipHostMalloc((void **)&r.host, s->px * sizeof(float), hipHostMallocPortable);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&r.copied, hipEventDisableTiming);
+    if (!r.host) {      // both or neither
+        hip_owned::HostPtr<float> host;
+        hip_owned::Event copied;
+        e = hip_owned::host_alloc(host, s->px * sizeof(float), hipHostMallocPortable);
+        if (e == hipSuccess) e = hip_owned::event_create(copied);
+        if (e == hipSuccess) { r.host = std::move(host); r.copied = std::move(copied); }
     }
     if (e == hipSuccess && r.used) e = hipEventSynchronize(r.copied);
     if (e != hipSuccess) { std::lock_guard<std::mutex> lk(s->mu); r.busy = false; return e; }
@@ -172,10 +171,9 @@ inline hipError_t slot_acquire(FrameStore *s, SlotClass *c, const void *owner, h
     if (pick < 0) {
         if (at_cap && !force) return hipSuccess;
         Slot x;
-        x.dev = nullptr; x.release = nullptr; x.owner = nullptr; x.state = 0; x.seq = 0;
-        const hipError_t e = hipMalloc(&x.dev, c->bytes ? c->bytes : 1);
+        const hipError_t e = hip_owned::dev_alloc(x.dev, c->bytes ? c->bytes : 1);
         if (e != hipSuccess) return e;
-        c->slots.push_back(x);
+        c->slots.push_back(std::move(x));
         pick = (int)c->slots.size() - 1;
     }
     Slot &x = c->slots[(size_t)pick];
@@ -187,7 +185,7 @@ inline hipError_t slot_acquire(FrameStore *s, SlotClass *c, const void *owner, h
 
 // The slots' last reader has been queued: they are free again once *release (an event of `owner`, recorded after that reader)
 // has happened.
-inline void slots_release_after(FrameStore *s, SlotClass *c, const int *idx, int n, hipEvent_t *release, const void *owner)
+inline void slots_release_after(FrameStore *s, SlotClass *c, const int *idx, int n, const hip_owned::Event *release, const void *owner)
 {
     std::lock_guard<std::mutex> lk(s->mu);
     for (int k = 0; k < n; ++k) {

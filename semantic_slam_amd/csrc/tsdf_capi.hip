@@ -26,6 +26,7 @@
 #include "pose_math.h"
 #include "host_derive.h"
 #include "host_copy.h"
+#include "hip_owned.h"
 #include "frame_store.h"
 #include "tsdf_kernels.hip.h"
 #include "tsdf_multiframe.hip.h"
@@ -36,6 +37,8 @@
 #ifdef TSDF_EXPERIMENTS
 #include "tsdf_experiments.hip.h"
 #endif
+
+using namespace hip_owned;   // DevPtr, HostPtr, Event, Stream and their allocation helpers
 
 namespace {
 
@@ -52,13 +55,15 @@ int fail(int code, const char *fmt, ...)
     return code;
 }
 
-#define HIP_TRY(expr)                                                                          \
+// HIP_TRY_OR(undo, expr): on failure, return undo(code) -- undo puts right what the function has queued so far
+#define HIP_TRY_OR(undo, expr)                                                                 \
     do {                                                                                       \
         hipError_t _e = (expr);                                                                \
         if (_e != hipSuccess)                                                                  \
-            return fail(TSDF_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e),   \
-                        __FILE__, __LINE__);                                                   \
+            return undo(fail(TSDF_ERR_HIP, "%s failed: %s (%s:%d)", #expr,                     \
+                             hipGetErrorString(_e), __FILE__, __LINE__));                      \
     } while (0)
+#define HIP_TRY(expr) HIP_TRY_OR(, expr)
 
 constexpr int kStageSlots = 3;
 
@@ -90,83 +95,88 @@ constexpr int kWedgeMode = TSDF_WEDGE_MODE;
 }  // namespace
 
 struct tsdf_volume {
-    tsdf_config cfg;
-    float base2world_inv[16];
-    float last_cam2base[16];
-    int64_t n_vox;           // voxels in the slab
-    float *d_tsdf;
-    float *d_weight;
-    hipStream_t own_stream;
-    hipStream_t stream;      // the stream work is queued on (own_stream unless overridden)
+    tsdf_config cfg = {};
+    float base2world_inv[16] = {};
+    float last_cam2base[16] = {};
+    int64_t n_vox = 0;       // voxels in the slab
+    DevPtr<float> d_tsdf;
+    DevPtr<float> d_weight;
+    Stream own_stream;
+    hipStream_t stream = nullptr;   // the stream work is queued on (own_stream unless overridden)
     // Staging and deferral memory is not the handle's: pinned frames, frame / mask slots in HBM and depth tile tables come from
     // the store all handles of this device and image size share (frame_store.h) and go back to it by stream order.
-    tsdf_store::FrameStore *store;
+    tsdf_store::FrameStore *store = nullptr;
     // the H2D copy of a frame runs on its own stream and overlaps the previous frame's kernel; the kernel waits for it
-    hipStream_t copy_stream;
-    hipEvent_t flush_done[2];         // recorded on `stream` after every launch that read store slots: what they are released after;
-    int flush_parity;                 // two, used in turn, so that a slot of pass k is not held until pass k + 1 has run as well
-    int table_slot;                   // the store's table slot of the launch being queued, or -1
+    hipStream_t copy_stream = nullptr;   // the store's
+    Event flush_done[2];              // recorded on `stream` after every launch that read store slots: what they are released after;
+    int flush_parity = 0;             // two, used in turn, so that a slot of pass k is not held until pass k + 1 has run as well
+    int table_slot = -1;              // the store's table slot of the launch being queued, or -1
     // Deferred integration of host frames (tsdf_integrate): the reference reads results back only in its destructor
     // (ref: src/tsdf.cu:101-104) and this library only at download / extraction / save, so the frames of successive
     // calls are collected -- copied into a pool in HBM, poses composed at call time -- and applied defer_n at a time as
     // ONE fused, classified sequence launch; every entry point that observes or changes the volume flushes first.
-    int defer_n;                      // frames per deferred launch (<= 1: every call launches; default kMaxFramesPerLaunch)
-    hipEvent_t pend_copied;
-    int pend_count;
-    int pend_slot[tsdfk::kMaxFramesPerLaunch], pend_mask_slot[tsdfk::kMaxFramesPerLaunch];   // store slots of the collected frames (-1: none)
-    const float *pend_depth[tsdfk::kMaxFramesPerLaunch];
-    struct tsdf_batch *owner;   // the batch this handle is a member of (its collected frames come first), or null
-    struct tsdf_group *group_owner;   // the group this handle is a slab of (likewise), or null
-    bool in_flush;
-    float pend_c2b[16 * tsdfk::kMaxFramesPerLaunch];
-    const uint8_t *pend_mask[tsdfk::kMaxFramesPerLaunch];   // instance masks of collected masked frames (in the store's mask slots)
-    int variant;
-    int sweep_parity;        // direction of the next integrate_tile sweep (flips every launch; a performance hint only)
+    int defer_n = tsdfk::kMaxFramesPerLaunch;   // frames per deferred launch (<= 1: every call launches)
+    Event pend_copied;
+    int pend_count = 0;
+    int pend_slot[tsdfk::kMaxFramesPerLaunch] = {}, pend_mask_slot[tsdfk::kMaxFramesPerLaunch] = {};   // store slots of the collected frames (-1: none)
+    const float *pend_depth[tsdfk::kMaxFramesPerLaunch] = {};
+    struct tsdf_batch *owner = nullptr;         // the batch this handle is a member of (its collected frames come first), or null
+    struct tsdf_group *group_owner = nullptr;   // the group this handle is a slab of (likewise), or null
+    bool in_flush = false;
+    float pend_c2b[16 * tsdfk::kMaxFramesPerLaunch] = {};
+    const uint8_t *pend_mask[tsdfk::kMaxFramesPerLaunch] = {};   // instance masks of collected masked frames (in the store's mask slots)
+    int variant = 0;
+    int sweep_parity = 0;    // direction of the next integrate_tile sweep (flips every launch; a performance hint only)
+#ifdef TSDF_EXPERIMENTS
     // per-launch frame blocks of integrate_multi: pinned host ring -> device ring (allocated on first use)
-    tsdfk::FramePose *h_frames[kStageSlots];
-    tsdfk::FramePose *d_frames[kStageSlots];
-    hipEvent_t frames_done[kStageSlots];
-    bool frames_used[kStageSlots];
-    int frames_next;
+    HostPtr<tsdfk::FramePose> h_frames[kStageSlots];
+    DevPtr<tsdfk::FramePose> d_frames[kStageSlots];
+    Event frames_done[kStageSlots];
+    bool frames_used[kStageSlots] = {};
+    int frames_next = 0;
+#endif
     // per-voxel label fusion (allocated by tsdf_labels_enable)
-    uint16_t *d_label;
-    float *d_fp, *d_bp;
-    float prob_thd;
+    DevPtr<uint16_t> d_label;
+    DevPtr<float> d_fp, d_bp;
+    float prob_thd = 0.0f;
     // per-voxel colour (allocated by tsdf_colour_enable): packed 0x00BBGGRR; staging of the RGB frames of tsdf_integrate_rgbd
-    uint32_t *d_colour;
-    uint8_t *d_rgb[kStageSlots];
-    uint8_t *h_rgb[kStageSlots];
-    hipEvent_t rgb_done[kStageSlots];
-    bool rgb_used[kStageSlots];
-    int rgb_next;
+    DevPtr<uint32_t> d_colour;
+    DevPtr<uint8_t> d_rgb[kStageSlots];
+    HostPtr<uint8_t> h_rgb[kStageSlots];
+    Event rgb_done[kStageSlots];
+    bool rgb_used[kStageSlots] = {};
+    int rgb_next = 0;
     // free-space summary (one word per 256-voxel row segment), see tsdf_kernels.hip.h
-    uint32_t *d_flags;
-    size_t n_flags;
-    int nseg;              // chunks per row when dim_x % 256 == 0 (row-mapped kernels), else 0
-    int chunks_per_slice;  // ceil(dim_x*dim_y / 256)
-    bool flat;             // dim_x % 256 != 0: summary-maintaining launches use the flat mapping
-    int brick_q, brick_r, brick_s;   // wavefront brick of the classified launches (choose_brick / tsdf_set_brick_shape); q = 0: none
-    int tile;                        // pixels per edge of the depth tiles of this handle's classified launches (tile_edge_for)
+    DevPtr<uint32_t> d_flags;
+    size_t n_flags = 0;
+    int nseg = 0;              // chunks per row when dim_x % 256 == 0 (row-mapped kernels), else 0
+    int chunks_per_slice = 0;  // ceil(dim_x*dim_y / 256)
+    bool flat = false;         // dim_x % 256 != 0: summary-maintaining launches use the flat mapping
+    int brick_q = 0, brick_r = 0, brick_s = 0;   // wavefront brick of the classified launches (choose_brick / tsdf_set_brick_shape); q = 0: none
+    int tile = 0;                    // pixels per edge of the depth tiles of this handle's classified launches (tile_edge_for)
     bool fine_tables = false;        // ... and, beside them, 4-pixel tiles for brick-sized boxes (fine_tables_for)
-    bool flags_known_zero;
-    unsigned int *d_super;       // per super-brick frame words of the current fused brick launch (classify_superbricks)
-    size_t super_words;
-    uint4 *d_work;               // work list of the current fused brick launch: {brick, slice group, free frames, skipped frames}
-    size_t work_entries;         // per live brick (classify_brick_list); capacity = every brick of the slab
-    int64_t work_nsuper, work_bucket_supers;   // super-bricks of the shape the list was sized for; most of them in one sub-list
+    bool flags_known_zero = false;
+#ifdef TSDF_EXPERIMENTS
+    DevPtr<unsigned int> d_super;    // per super-brick frame words of the current fused brick launch (classify_superbricks)
+    size_t super_words = 0;
+#endif
+    DevPtr<uint4> d_work;        // work list of the current fused brick launch: {brick, slice group, free frames, skipped frames}
+    size_t work_entries = 0;     // per live brick (classify_brick_list); capacity = every brick of the slab
+    int64_t work_nsuper = 0, work_bucket_supers = 0;   // super-bricks of the shape the list was sized for; most of them in one sub-list
     int work_wedge_mode = -1;                  // ... and the list_bucket mode they were counted under
     // optional diagnostic counters (tsdf_shortcut_stats)
-    unsigned int *d_shortcut_stats;
+    DevPtr<unsigned int> d_shortcut_stats;
     // adaptive use of the classification: claims of the last classifying launch, read back without blocking
-    unsigned long long *d_claims, *h_claims;   // d_claims: TWO counter blocks (+ frame table each), one per list parity
-    hipEvent_t claims_done;
+    DevPtr<unsigned long long> d_claims;   // TWO counter blocks (+ frame table each), one per list parity
+    HostPtr<unsigned long long> h_claims;
+    Event claims_done;
     // A sequence call's launches are pipelined: the pre-pass of launch k + 1 (tile tables, classify_brick_list: small grids, 11 % of
     // a 512^3 S-surf launch, reading only the frames and the poses) runs on pre_stream beside launch k's Integrate kernel.  Two work
     // lists, two counter blocks, two table slots (list_parity); pre_done[p]: pre-pass of parity p queued on pre_stream; list_free[p]:
     // the Integrate kernel that read parity p's list has been queued on the handle's stream; seq_ready: a sequence's inputs.
-    hipStream_t pre_stream = nullptr, rb_stream = nullptr;   // rb_stream: the counters' read-back of a pipelined launch
-    int rb_parity = -1;                                      // parity of the block the read-back in flight on rb_stream reads, or -1
-    hipEvent_t pre_done[2] = {nullptr, nullptr}, list_free[2] = {nullptr, nullptr}, seq_ready = nullptr;
+    Stream pre_stream, rb_stream;   // rb_stream: the counters' read-back of a pipelined launch
+    int rb_parity = -1;             // parity of the block the read-back in flight on rb_stream reads, or -1
+    Event pre_done[2], list_free[2], seq_ready;
     int list_parity = 0;
     bool list_used[2] = {false, false};
     // Pipelining pays where a launch is short enough for its small pre-pass kernels to matter and the chip is not full: measured,
@@ -175,66 +185,67 @@ struct tsdf_volume {
     // 84 us alone: its latency-bound wavefronts hold slots the Integrate kernel's would use), fr3 trajectory 1024^3 0.1460 -> 0.1458.
     // So: slabs below 64 M voxels; larger ones keep one list (the second would be 134 MB at 1024^3) and one stream.
     bool pipeline_ok = false;
-    bool claims_pending, claims_known;
-    double claims_total;        // workgroup-frames of the launch the pending read-back belongs to
-    double claim_fraction;      // claimed / total of the last launch that was read back
-    int launches_unclassified;  // since the last classifying launch
+    bool claims_pending = false, claims_known = false;
+    double claims_total = 0.0;      // workgroup-frames of the launch the pending read-back belongs to
+    double claim_fraction = 0.0;    // claimed / total of the last launch that was read back
+    int launches_unclassified = 0;  // since the last classifying launch
     // scratch for surface extraction (allocated on first use)
-    void *d_scratch;
-    size_t scratch_bytes;
+    DevPtr<char> d_scratch;
+    size_t scratch_bytes = 0;
     // class of every workgroup of a one-frame masked launch (classify_workgroups), grown on demand
-    uint8_t *d_wg_class;
-    size_t wg_class_bytes;
+    DevPtr<uint8_t> d_wg_class;
+    size_t wg_class_bytes = 0;
     // output list of the extraction passes (points / vertices / triangles), grown on demand and kept
-    void *d_list;
-    size_t list_bytes;
+    DevPtr<char> d_list;
+    size_t list_bytes = 0;
 };
 
 constexpr int kBatchSideStreams = 4;
 
 // Many volumes integrated by one launch per frame (include/tsdf_hip.h, tsdf_batch_*).
 struct tsdf_batch {
-    int device;
+    int device = 0;
     std::vector<tsdf_volume *> vols;
-    hipStream_t stream;
+    Stream stream;
     // per-frame parameter blocks: pinned host ring -> device ring
-    tsdfk::IntegrateParams *h_params[kStageSlots];
-    tsdfk::IntegrateParams *d_params[kStageSlots];
-    tsdfk::FramePose *h_poses[kStageSlots];
-    tsdfk::FramePose *d_poses[kStageSlots];
-    hipEvent_t slot_done[kStageSlots];
-    bool slot_used[kStageSlots];
-    int slot_next;
-    int2 *d_slice_map;
-    int total_slices, max_blocks;
-    int2 *d_group_map;           // {object, slice group}: the brick launches' z index (a brick spans brick_s slices)
-    int total_groups;
+    HostPtr<tsdfk::IntegrateParams> h_params[kStageSlots];
+    DevPtr<tsdfk::IntegrateParams> d_params[kStageSlots];
+    HostPtr<tsdfk::FramePose> h_poses[kStageSlots];
+    DevPtr<tsdfk::FramePose> d_poses[kStageSlots];
+    Event slot_done[kStageSlots];
+    bool slot_used[kStageSlots] = {};
+    int slot_next = 0;
+    DevPtr<int2> d_slice_map;
+    int total_slices = 0, max_blocks = 0;
+    DevPtr<int2> d_group_map;    // {object, slice group}: the brick launches' z index (a brick spans brick_s slices)
+    int total_groups = 0;
     std::vector<int> group_s;    // the brick_s of every member the group map was built with
     // per-object depth tile tables of the current frame and the class of every workgroup of the launch
-    float2 *d_tiles;
-    size_t tiles_per_object;
-    uint8_t *d_wg_class;
-    uint8_t *d_brick_class;      // class per wavefront brick of the launch (classify_bricks_batched), on first use
-    size_t brick_class_bytes;
+    DevPtr<float2> d_tiles;
+    size_t tiles_per_object = 0;
+    DevPtr<uint8_t> d_wg_class;
+    DevPtr<uint8_t> d_brick_class;   // class per wavefront brick of the launch (classify_bricks_batched), on first use
+    size_t brick_class_bytes = 0;
     // Deferred integration of a batch of large members (tsdf_batch_integrate_device): frames are collected in HBM -- the
     // depth image once, every member's mask beside it -- and applied by ONE fused launch per member per 32 frames
     // (the volume then moves once per 32 frames instead of once per frame); flushed by anything that observes a member.
-    float *d_depth_pool;                     // kMaxFramesPerLaunch frames
-    uint8_t *d_mask_pool;                    // kMaxFramesPerLaunch x members masks
+    DevPtr<float> d_depth_pool;              // kMaxFramesPerLaunch frames
+    DevPtr<uint8_t> d_mask_pool;             // kMaxFramesPerLaunch x members masks
     std::vector<float> pend_c2b;             // [member][frame][16], composed at collection time
     std::vector<const uint8_t *> pend_mask;  // [member][frame], null = the member's frame has no mask
-    int pend_count;
-    bool in_flush;
+    int pend_count = 0;
+    bool in_flush = false;
     // the members' fused launches of a flush are independent of each other: they go out on a few side streams (forked
     // from and joined back into the batch's stream by events), so one member's tail and table kernels overlap the next
     // member's launch
-    hipStream_t side[kBatchSideStreams];
-    hipEvent_t side_done[kBatchSideStreams];
-    hipEvent_t collected;
+    Stream side[kBatchSideStreams];
+    Event side_done[kBatchSideStreams];
+    Event collected;
     // the members as tsdf_batch_raycast_device's kernel reads them: pinned host block -> HBM (allocated on first use); the host
     // block is refilled only after the copy out of it (ray_copied) has run
-    tsdfk::RayVolume *h_ray = nullptr, *d_ray = nullptr;
-    hipEvent_t ray_copied = nullptr;
+    HostPtr<tsdfk::RayVolume> h_ray;
+    DevPtr<tsdfk::RayVolume> d_ray;
+    Event ray_copied;
     bool ray_used = false;
 };
 
@@ -284,7 +295,7 @@ int store_slot(tsdf_volume *v, tsdf_store::SlotClass *c, hipStream_t first_user,
 // Everything queued on the handle's stream so far has read its store slots: they go back after flush_done.
 int store_release(tsdf_volume *v, tsdf_store::SlotClass *c, const int *idx, int n)
 {
-    hipEvent_t *evt = &v->flush_done[v->flush_parity];
+    const Event *evt = &v->flush_done[v->flush_parity];
     HIP_TRY(hipEventRecord(*evt, v->stream));
     tsdf_store::slots_release_after(v->store, c, idx, n, evt, v);
     return TSDF_OK;
@@ -508,10 +519,8 @@ int launch_masked_bricks(tsdf_volume *v, tsdfk::IntegrateParams &p)
     if (rc0) return rc0;
     const size_t n_bricks = (size_t)blocks * nz * 4;
     if (v->wg_class_bytes < n_bricks) {
-        if (v->d_wg_class) HIP_TRY(hipFree(v->d_wg_class));
-        v->d_wg_class = nullptr;
         v->wg_class_bytes = 0;
-        HIP_TRY(hipMalloc((void **)&v->d_wg_class, n_bricks));
+        HIP_TRY(dev_alloc(v->d_wg_class, n_bricks));
         v->wg_class_bytes = n_bricks;
     }
     const float *d = p.depth;
@@ -585,6 +594,7 @@ void experiment_adjust(const tsdf_volume *v, bool labels, bool *classify, int *z
 int launch_integrate_experiment(tsdf_volume *v, const float *depth_dev, const uint8_t *mask_dev, const float *c2b);
 int launch_multi_experiment(tsdf_volume *v, tsdfk::MultiParamsInline &mi, const float *const *depth_dev, const uint8_t *const *masks_dev,
                             const float *c2b, int n, bool labels, bool any_mask, bool classify, bool *handled, double *claims_total);
+bool experiment_takes_multi(const tsdf_volume *v, bool labels, bool classify);
 int launch_single_experiment(tsdf_volume *v, tsdfk::IntegrateParams &common, tsdfk::FramePose &pose, const float *depth_dev,
                              const float *c2b, bool *handled);
 #endif
@@ -762,23 +772,17 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
     if (classify && !v->d_claims) {
         // the launch's counter block (tsdf_multiframe.hip.h, kListBuckets): per bucket the lengths of its brick sub-list and
         // its share of the claims, cleared by the table kernel below; behind it the frames' table for classify_patch
-        // all three or none: a launch that finds d_claims set relies on the host mirror and the event being there too
-        unsigned long long *dc = nullptr;
-        unsigned char *hc = nullptr;
-        hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        hipError_t e = hipMalloc((void **)&dc, 2 * kClaimBlockBytes);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&hc, tsdfk::kCounterBytes, hipHostMallocDefault);
-        for (int i = 0; i < 6 && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming);
-        if (e != hipSuccess) {
-            for (int i = 0; i < 6; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]);
-            if (hc) (void)hipHostFree(hc);
-            if (dc) (void)hipFree(dc);
-            return fail(TSDF_ERR_HIP, "claim counters: %s", hipGetErrorString(e));
-        }
-        v->d_claims = reinterpret_cast<decltype(v->d_claims)>(dc);
-        v->h_claims = reinterpret_cast<decltype(v->h_claims)>(hc);
-        v->claims_done = ev[0];
-        v->pre_done[0] = ev[1]; v->pre_done[1] = ev[2]; v->list_free[0] = ev[3]; v->list_free[1] = ev[4]; v->seq_ready = ev[5];
+        // all or none: a launch that finds d_claims set relies on the host mirror and the events being there too
+        DevPtr<unsigned long long> dc;
+        HostPtr<unsigned long long> hc;
+        Event ev[6];
+        hipError_t e = dev_alloc(dc, 2 * kClaimBlockBytes);
+        if (e == hipSuccess) e = host_alloc(hc, tsdfk::kCounterBytes, hipHostMallocDefault);
+        for (int i = 0; i < 6 && e == hipSuccess; ++i) e = event_create(ev[i]);
+        if (e != hipSuccess) return fail(TSDF_ERR_HIP, "claim counters: %s", hipGetErrorString(e));
+        v->d_claims = std::move(dc); v->h_claims = std::move(hc); v->claims_done = std::move(ev[0]);
+        v->pre_done[0] = std::move(ev[1]); v->pre_done[1] = std::move(ev[2]); v->list_free[0] = std::move(ev[3]);
+        v->list_free[1] = std::move(ev[4]); v->seq_ready = std::move(ev[5]);
     }
     // this launch's parity: its counter block, its half of the work list, its table slot
     // (slabs too large to be pipelined -- see pipeline_ok -- keep one list and one parity)
@@ -791,61 +795,30 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
     if (pipelined && !v->pre_stream) {
         // the two side streams of a pipelined handle, at its first pipelined launch (a stream costs about 2 MiB of device memory:
         // the per-object handles of a scene, which are fed frame by frame and never pipeline, do not pay for them)
-        hipStream_t a = nullptr, b = nullptr;
+        Stream a, b;
         int prio = 0;
 #ifdef TSDF_EXPERIMENTS
         if (std::getenv("TSDF_PRE_PRIORITY")) { int lo = 0, hi = 0; (void)hipDeviceGetStreamPriorityRange(&lo, &hi); prio = hi; }   // (numerically lower = higher)
 #endif
         // (default priority: with the highest one the pre-pass finished 180 us into the launch beside it, which then ran 65 us longer)
-        hipError_t e = hipStreamCreateWithPriority(&a, hipStreamNonBlocking, prio);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&b, hipStreamNonBlocking);
-        if (e != hipSuccess) {
-            if (a) (void)hipStreamDestroy(a);
-            return fail(TSDF_ERR_HIP, "side streams: %s", hipGetErrorString(e));
-        }
-        v->pre_stream = a;
-        v->rb_stream = b;
-    }
-    const hipStream_t ps = pipelined ? v->pre_stream : v->stream;
-    if (pipelined) {
-        HIP_TRY(hipStreamWaitEvent(ps, inputs_ready, 0));
-        if (v->list_used[P]) HIP_TRY(hipStreamWaitEvent(ps, v->list_free[P], 0));   // the Integrate kernel two launches back has read this parity's buffers
-        if (v->rb_parity == P) HIP_TRY(hipStreamWaitEvent(ps, v->claims_done, 0)); // ... and its counters have left for the host
-    } else if (classify && v->rb_parity == P) {
-        HIP_TRY(hipStreamWaitEvent(v->stream, v->claims_done, 0));
-    }
-    if (count_claims) mi.common.claim_counter = claims_p + 1;   // bucket 0's claims word (the pre-pass adds the bucket's offset)
-    if (classify) {
-        // depth tile tables of the n frames (two small launches), then the kernels that consult them
-        const size_t per_frame = tile_table_elems_host(mi.common.tiles_w, mi.common.tiles_h);
-        float2 *tiles = nullptr;
-        int rc = tables_begin(v, &tiles, ps);
-        if (rc) return rc;
-        // (fine_tables) the fine tables of the launch's frames sit behind its kMaxFramesPerLaunch coarse ones in the same slot
-        float2 *fine = v->fine_tables ? tiles + (size_t)tsdfk::kMaxFramesPerLaunch * per_frame : nullptr;
-        rc = build_tile_tables(ps, c, mi.common, depth_dev, masks_dev, n, tiles, claims_p, fine, pipelined);
-        if (rc) return rc;
-        mi.common.fine = fine;
-        for (int f = 0; f < n; ++f) mi.frames[f].tiles = tiles + (size_t)f * per_frame;
-        for (int f = n; f < tsdfk::kMaxFramesPerLaunch; ++f) mi.frames[f] = mi.frames[0];
+        hipError_t e = hipStreamCreateWithPriority(a.put(), hipStreamNonBlocking, prio);
+        if (e == hipSuccess) e = stream_create(b);
+        if (e != hipSuccess) return fail(TSDF_ERR_HIP, "side streams: %s", hipGetErrorString(e));
+        v->pre_stream = std::move(a); v->rb_stream = std::move(b);
     }
     const int nz_groups = (nz + mi.common.brick_s - 1) / mi.common.brick_s;   // a brick spans brick_s slices
-    double claims_total = 0.0;
-    bool launched = false, listed = false;
+    // the brick work list (below), sized and allocated before anything is queued on the side stream
+    bool listed = classify;
 #ifdef TSDF_EXPERIMENTS
-    {
-        int rc = launch_multi_experiment(v, mi, depth_dev, masks_dev, c2b, n, label_ims != nullptr, any_mask, classify, &launched, &claims_total);
-        if (rc) return rc;
-    }
+    listed = listed && !experiment_takes_multi(v, label_ims != nullptr, classify);
 #endif
-    if (!launched && classify) {
+    tsdfk::BrickListParams bl;
+    int64_t n_super = 0, cap = 0;
+    if (listed) {
         // A pre-pass compacts the bricks some frame may touch into a work list and the launch runs one wavefront per entry.
-        const int64_t per_group = (int64_t)mi.common.brick_groups * mi.common.bricks_per_group;
-        tsdfk::BrickListParams bl;
         bl.nsx = (mi.common.bricks_per_group + tsdfk::kSuperBX - 1) / tsdfk::kSuperBX;
         bl.nsy = (mi.common.brick_groups + tsdfk::kSuperBY - 1) / tsdfk::kSuperBY;
         bl.nsz = (nz_groups + tsdfk::kSuperBZ - 1) / tsdfk::kSuperBZ;
-        const int64_t n_super = (int64_t)bl.nsx * bl.nsy * bl.nsz;
         bl.wedge_mode = kWedgeMode;
 #ifdef TSDF_EXPERIMENTS
         if (const char *e = std::getenv("TSDF_WEDGE_MODE")) bl.wedge_mode = std::atoi(e);     // A/B knob of the measurement build
@@ -856,6 +829,7 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
         bl.wedge_oz = (int)std::lround(std::fmax(-30000.0, std::fmin(30000.0, (double)c.origin[2] / c.voxel_size + c.z_begin)));
         bl.fy_px = (int)std::lround(std::fmax(1.0, std::fmin(16000.0, std::fabs((double)c.cam_K[4]))));
         if (!(c.voxel_size > 0) || std::isnan(c.origin[1]) || std::isnan(c.origin[2])) bl.wedge_mode = 0;
+        n_super = (int64_t)bl.nsx * bl.nsy * bl.nsz;
         // a sub-list must hold every brick of every super-brick list_bucket deals to it: counted exactly, once per grid shape
         if (v->work_nsuper != n_super || v->work_wedge_mode != bl.wedge_mode) {
             std::vector<int64_t> per((size_t)tsdfk::kListBuckets, 0);
@@ -867,20 +841,58 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
             v->work_nsuper = n_super;
             v->work_wedge_mode = bl.wedge_mode;
         }
-        const int64_t cap = v->work_bucket_supers * tsdfk::kSuperBricks;
+        cap = v->work_bucket_supers * tsdfk::kSuperBricks;
         const int64_t total = cap * tsdfk::kListBuckets;
         if (total > 0x7fffffffll - 1024) return fail(TSDF_ERR_INVALID, "fused launch: %lld bricks exceed the work list's 32-bit index", (long long)total);
         if (v->work_entries < (size_t)total) {
             if (v->d_work) {      // (a list in flight on either stream is done before its memory goes)
                 if (v->pre_stream) HIP_TRY(hipStreamSynchronize(v->pre_stream));
                 HIP_TRY(hipStreamSynchronize(v->stream));
-                HIP_TRY(hipFree(v->d_work));
             }
-            v->d_work = nullptr;
             v->work_entries = 0;
-            HIP_TRY(hipMalloc((void **)&v->d_work, (v->pipeline_ok ? 2 : 1) * (size_t)total * sizeof(uint4)));     // one list per parity
+            HIP_TRY(dev_alloc(v->d_work, (v->pipeline_ok ? 2 : 1) * (size_t)total * sizeof(uint4)));     // one list per parity
             v->work_entries = (size_t)total;
         }
+    }
+    const hipStream_t ps = pipelined ? v->pre_stream : v->stream;
+    // a failure from here on joins the side stream back into the handle's stream and gives the table slot back
+    auto unwind = [&](int code) {
+        if (pipelined && hipEventRecord(v->pre_done[P], ps) == hipSuccess) (void)hipStreamWaitEvent(v->stream, v->pre_done[P], 0);
+        (void)tables_end(v);
+        return code;
+    };
+    if (pipelined) {
+        HIP_TRY_OR(unwind, hipStreamWaitEvent(ps, inputs_ready, 0));
+        if (v->list_used[P]) HIP_TRY_OR(unwind, hipStreamWaitEvent(ps, v->list_free[P], 0));   // the Integrate kernel two launches back has read this parity's buffers
+        if (v->rb_parity == P) HIP_TRY_OR(unwind, hipStreamWaitEvent(ps, v->claims_done, 0)); // ... and its counters have left for the host
+    } else if (classify && v->rb_parity == P) {
+        HIP_TRY(hipStreamWaitEvent(v->stream, v->claims_done, 0));
+    }
+    if (count_claims) mi.common.claim_counter = claims_p + 1;   // bucket 0's claims word (the pre-pass adds the bucket's offset)
+    if (classify) {
+        // depth tile tables of the n frames (two small launches), then the kernels that consult them
+        const size_t per_frame = tile_table_elems_host(mi.common.tiles_w, mi.common.tiles_h);
+        float2 *tiles = nullptr;
+        int rc = tables_begin(v, &tiles, ps);
+        if (rc) return unwind(rc);
+        // (fine_tables) the fine tables of the launch's frames sit behind its kMaxFramesPerLaunch coarse ones in the same slot
+        float2 *fine = v->fine_tables ? tiles + (size_t)tsdfk::kMaxFramesPerLaunch * per_frame : nullptr;
+        rc = build_tile_tables(ps, c, mi.common, depth_dev, masks_dev, n, tiles, claims_p, fine, pipelined);
+        if (rc) return unwind(rc);
+        mi.common.fine = fine;
+        for (int f = 0; f < n; ++f) mi.frames[f].tiles = tiles + (size_t)f * per_frame;
+        for (int f = n; f < tsdfk::kMaxFramesPerLaunch; ++f) mi.frames[f] = mi.frames[0];
+    }
+    double claims_total = 0.0;
+    bool launched = false;
+#ifdef TSDF_EXPERIMENTS
+    {
+        int rc = launch_multi_experiment(v, mi, depth_dev, masks_dev, c2b, n, label_ims != nullptr, any_mask, classify, &launched, &claims_total);
+        if (rc) return unwind(rc);
+    }
+#endif
+    if (listed) {
+        const int64_t per_group = (int64_t)mi.common.brick_groups * mi.common.bricks_per_group;
         uint4 *const work_p = v->d_work + (size_t)P * v->work_entries;
         bl.list = work_p;
         bl.counters = reinterpret_cast<unsigned char *>(claims_p);
@@ -888,8 +900,8 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
         bl.poses = reinterpret_cast<tsdfk::ClassPoseTable *>(bl.counters + tsdfk::kCounterBytes);
         hipLaunchKernelGGL(tsdfk::classify_brick_list, dim3((unsigned)((n_super + 3) / 4)), block, 0, ps, mi, bl);
         if (pipelined) {       // the Integrate kernel waits for its pre-pass; everything before it on the handle's stream does not
-            HIP_TRY(hipEventRecord(v->pre_done[P], ps));
-            HIP_TRY(hipStreamWaitEvent(v->stream, v->pre_done[P], 0));
+            HIP_TRY_OR(unwind, hipEventRecord(v->pre_done[P], ps));
+            HIP_TRY_OR(unwind, hipStreamWaitEvent(v->stream, v->pre_done[P], 0));
         }
         const dim3 grid_list((unsigned)(((cap + 3) / 4 + 1) * tsdfk::kListBuckets));   // front groups + back groups of every sub-list
         const uint4 *wl = work_p;
@@ -903,7 +915,6 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
             hipLaunchKernelGGL((tsdfk::integrate_brick_list<kBrickNT, false, false>), grid_list, block, 0, v->stream, mi, wl, wc, bl.bucket_cap, wp);
         claims_total = (double)per_group * nz_groups * n;   // wavefront-frames = bricks x frames
         launched = true;
-        listed = true;
     }
     if (!launched) {
         // The per-voxel fused kernel.  Workgroup order: slices fastest -- consecutively dispatched workgroups share their
@@ -932,7 +943,7 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
     }
     if (listed) {
         // after this parity's Integrate kernel: its buffers may be rebuilt (a pre-pass on the side stream waits for it)
-        HIP_TRY(hipEventRecord(v->list_free[P], v->stream));
+        HIP_TRY_OR(unwind, hipEventRecord(v->list_free[P], v->stream));
         v->list_used[P] = true;
         v->list_parity = v->pipeline_ok ? P ^ 1 : 0;
     }
@@ -942,13 +953,13 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
         // next pre-pass on the side stream; the pre-pass that clears this block again waits for it (rb_done)
         v->claims_total = claims_total;
         const hipStream_t rs = (pipelined && listed) ? v->rb_stream : v->stream;
-        if (rs != v->stream) HIP_TRY(hipStreamWaitEvent(rs, v->list_free[P], 0));
-        HIP_TRY(hipMemcpyAsync(v->h_claims, claims_p, tsdfk::kCounterBytes, hipMemcpyDeviceToHost, rs));
-        HIP_TRY(hipEventRecord(v->claims_done, rs));
+        if (rs != v->stream) HIP_TRY_OR(unwind, hipStreamWaitEvent(rs, v->list_free[P], 0));
+        HIP_TRY_OR(unwind, hipMemcpyAsync(v->h_claims, claims_p, tsdfk::kCounterBytes, hipMemcpyDeviceToHost, rs));
+        HIP_TRY_OR(unwind, hipEventRecord(v->claims_done, rs));
         v->claims_pending = true;
         v->rb_parity = (rs != v->stream) ? P : -1;
     }
-    HIP_TRY(hipGetLastError());
+    HIP_TRY_OR(unwind, hipGetLastError());
     const int rc_end = tables_end(v);
     // (pipelined) the next launch's table slot is released after the OTHER of the handle's two events: a slot taken two launches
     // later then waits for this launch's Integrate kernel, not for the one in between
@@ -1130,10 +1141,8 @@ int fill(tsdf_volume *v)
 int ensure_list(tsdf_volume *v, size_t bytes)
 {
     if (v->list_bytes >= bytes) return TSDF_OK;
-    if (v->d_list) HIP_TRY(hipFree(v->d_list));
-    v->d_list = nullptr;
     v->list_bytes = 0;
-    HIP_TRY(hipMalloc(&v->d_list, bytes));
+    HIP_TRY(dev_alloc(v->d_list, bytes));
     v->list_bytes = bytes;
     return TSDF_OK;
 }
@@ -1141,10 +1150,8 @@ int ensure_list(tsdf_volume *v, size_t bytes)
 int ensure_scratch(tsdf_volume *v, size_t bytes)
 {
     if (v->scratch_bytes >= bytes) return TSDF_OK;
-    if (v->d_scratch) HIP_TRY(hipFree(v->d_scratch));
-    v->d_scratch = nullptr;
     v->scratch_bytes = 0;
-    HIP_TRY(hipMalloc(&v->d_scratch, bytes));
+    HIP_TRY(dev_alloc(v->d_scratch, bytes));
     v->scratch_bytes = bytes;
     return TSDF_OK;
 }
@@ -1218,13 +1225,8 @@ int write_bin(const char *path, int dx, int dy, int dz, const float origin[3], f
 // (files are written rarely and the disk serialises writers anyway); the lock is held for the length of one array.
 struct FileStager {
     std::mutex mu;
-    void *pin[2] = {nullptr, nullptr};       // portable: any device may copy into them
+    HostPtr<char> pin[2];                    // portable: any device may copy into them
     static constexpr size_t kPiece = (size_t)32 << 20;
-    ~FileStager()
-    {
-        for (int i = 0; i < 2; ++i)
-            if (pin[i]) (void)hipHostFree(pin[i]);
-    }
 };
 FileStager &file_stager() { static FileStager s; return s; }
 
@@ -1235,11 +1237,11 @@ int stream_device_to_file(tsdf_volume *v, FILE *fp, const void *src, size_t byte
     FileStager &fs = file_stager();
     std::lock_guard<std::mutex> lk(fs.mu);
     for (int i = 0; i < 2; ++i)
-        if (!fs.pin[i]) HIP_TRY(hipHostMalloc(&fs.pin[i], FileStager::kPiece, hipHostMallocPortable));
+        if (!fs.pin[i]) HIP_TRY(host_alloc(fs.pin[i], FileStager::kPiece, hipHostMallocPortable));
     // the events belong to the device of v's stream (the current one: every caller has bound it), so they live for the call
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    hipError_t e = hipEventCreateWithFlags(&ev[0], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ev[1], hipEventDisableTiming);
+    Event ev[2];
+    hipError_t e = event_create(ev[0]);
+    if (e == hipSuccess) e = event_create(ev[1]);
     const size_t pieces = (bytes + FileStager::kPiece - 1) / FileStager::kPiece;
     auto len = [&](size_t k) { return k + 1 < pieces ? FileStager::kPiece : bytes - k * FileStager::kPiece; };
     bool short_write = false;
@@ -1254,8 +1256,6 @@ int stream_device_to_file(tsdf_volume *v, FILE *fp, const void *src, size_t byte
         }
     }
     if (e != hipSuccess) (void)hipStreamSynchronize(v->stream);     // nothing may still be writing into the buffers
-    for (int i = 0; i < 2; ++i)
-        if (ev[i]) (void)hipEventDestroy(ev[i]);
     if (e != hipSuccess) return fail(TSDF_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     if (short_write) return fail(TSDF_ERR_IO, "%s: short write to %s", who, path);
     return TSDF_OK;
@@ -1332,11 +1332,9 @@ int tsdf_create(const tsdf_config *cfg, tsdf_volume **out)
 
     tsdf_volume *v = new (std::nothrow) tsdf_volume();
     if (!v) return fail(TSDF_ERR_INVALID, "tsdf_create: out of host memory");
-    std::memset(v, 0, sizeof *v);
     v->cfg = *cfg;
     v->n_vox = (int64_t)cfg->dim_x * cfg->dim_y * (cfg->z_end - cfg->z_begin);
     // ref: src/tsdf.cu:74 -- the inverse stays zero when base2world is singular, silently
-    std::memset(v->base2world_inv, 0, sizeof v->base2world_inv);
     tsdf_host::invert_matrix(cfg->base2world, v->base2world_inv);
 
     int rc = TSDF_OK;
@@ -1344,20 +1342,19 @@ int tsdf_create(const tsdf_config *cfg, tsdf_volume **out)
     if (hipSetDevice(cfg->device) != hipSuccess)
         return cleanup(fail(TSDF_ERR_HIP, "tsdf_create: hipSetDevice(%d) failed", cfg->device));
     hipError_t e;
-    if ((e = hipStreamCreateWithFlags(&v->own_stream, hipStreamNonBlocking)) != hipSuccess)
+    if ((e = stream_create(v->own_stream)) != hipSuccess)
         return cleanup(fail(TSDF_ERR_HIP, "tsdf_create: hipStreamCreate: %s", hipGetErrorString(e)));
     v->stream = v->own_stream;
-    v->defer_n = tsdfk::kMaxFramesPerLaunch;
     size_t bytes = (size_t)(v->n_vox > 0 ? v->n_vox : 1) * sizeof(float);
-    if ((e = hipMalloc((void **)&v->d_tsdf, bytes)) != hipSuccess ||
-        (e = hipMalloc((void **)&v->d_weight, bytes)) != hipSuccess)
+    if ((e = dev_alloc(v->d_tsdf, bytes)) != hipSuccess ||
+        (e = dev_alloc(v->d_weight, bytes)) != hipSuccess)
         return cleanup(fail(TSDF_ERR_HIP, "tsdf_create: hipMalloc of %zu bytes x2: %s", bytes, hipGetErrorString(e)));
     v->flat = cfg->dim_x % 256 != 0;
     v->nseg = v->flat ? 0 : cfg->dim_x / 256;
     v->chunks_per_slice = (int)(((int64_t)cfg->dim_x * cfg->dim_y + 255) / 256);
     choose_brick(v);
     v->n_flags = cfg->dim_x % 4 == 0 ? (size_t)v->chunks_per_slice * (size_t)(cfg->z_end - cfg->z_begin) : 0;
-    if ((e = hipMalloc((void **)&v->d_flags, (v->n_flags ? v->n_flags : 1) * sizeof(uint32_t))) != hipSuccess)
+    if ((e = dev_alloc(v->d_flags, (v->n_flags ? v->n_flags : 1) * sizeof(uint32_t))) != hipSuccess)
         return cleanup(fail(TSDF_ERR_HIP, "tsdf_create: hipMalloc of the summary: %s", hipGetErrorString(e)));
     // staging, deferral and tile-table memory: the store shared by every handle of this device and image size (nothing is
     // allocated until a frame arrives)
@@ -1374,11 +1371,10 @@ int tsdf_create(const tsdf_config *cfg, tsdf_volume **out)
         const size_t table_bytes = (int64_t)tw * th <= 16384
             ? tsdfk::kMaxFramesPerLaunch * (tile_table_elems_host(tw, th) + (v->fine_tables ? tsdfk::fine_table_elems(fw, fh) : 0)) * sizeof(float2) : 0;
         if ((e = tsdf_store::store_ref(cfg->device, (size_t)cfg->im_height * cfg->im_width, table_bytes, &v->store)) != hipSuccess ||
-            (e = hipEventCreateWithFlags(&v->flush_done[0], hipEventDisableTiming)) != hipSuccess ||
-            (e = hipEventCreateWithFlags(&v->flush_done[1], hipEventDisableTiming)) != hipSuccess ||
-            (e = hipEventCreateWithFlags(&v->pend_copied, hipEventDisableTiming)) != hipSuccess)
+            (e = event_create(v->flush_done[0])) != hipSuccess ||
+            (e = event_create(v->flush_done[1])) != hipSuccess ||
+            (e = event_create(v->pend_copied)) != hipSuccess)
             return cleanup(fail(TSDF_ERR_HIP, "tsdf_create: frame store: %s", hipGetErrorString(e)));
-        v->table_slot = -1;
         v->copy_stream = v->store->copy_stream;   // the store's: shared by its handles (thread-safe; copies share one PCIe pipe anyway)
     }
     if ((rc = fill(v)) != TSDF_OK) return cleanup(rc);
@@ -1397,47 +1393,11 @@ int tsdf_destroy(tsdf_volume *v)
     if (v->rb_stream) (void)hipStreamSynchronize(v->rb_stream);
     v->pend_count = 0;   // frames collected but never observed: nothing can tell whether they were applied
     if (v->store) {      // (the streams are idle: whatever this handle held, or others were waiting on its events for, is free)
-        tsdf_store::slots_drop_owner(v->store, v);
+        tsdf_store::slots_drop_owner(v->store, v);   // before the events the store's slots point at (flush_done) go
         tsdf_store::store_unref(v->store);
         v->store = nullptr;
     }
-    if (v->pend_copied) (void)hipEventDestroy(v->pend_copied);
-    for (int i = 0; i < 2; ++i) if (v->flush_done[i]) (void)hipEventDestroy(v->flush_done[i]);
-    for (int i = 0; i < kStageSlots; ++i) {
-        if (v->h_frames[i]) (void)hipHostFree(v->h_frames[i]);
-        if (v->d_frames[i]) (void)hipFree(v->d_frames[i]);
-        if (v->frames_done[i]) (void)hipEventDestroy(v->frames_done[i]);
-    }
-    if (v->d_colour) (void)hipFree(v->d_colour);
-    for (int i = 0; i < kStageSlots; ++i) {
-        if (v->d_rgb[i]) (void)hipFree(v->d_rgb[i]);
-        if (v->h_rgb[i]) (void)hipHostFree(v->h_rgb[i]);
-        if (v->rgb_done[i]) (void)hipEventDestroy(v->rgb_done[i]);
-    }
-    if (v->d_label) (void)hipFree(v->d_label);
-    if (v->d_fp) (void)hipFree(v->d_fp);
-    if (v->d_bp) (void)hipFree(v->d_bp);
-    if (v->d_scratch) (void)hipFree(v->d_scratch);
-    if (v->d_list) (void)hipFree(v->d_list);
-    if (v->d_wg_class) (void)hipFree(v->d_wg_class);
-    if (v->d_flags) (void)hipFree(v->d_flags);
-    if (v->d_super) (void)hipFree(v->d_super);
-    if (v->d_work) (void)hipFree(v->d_work);
-    if (v->d_claims) (void)hipFree(v->d_claims);
-    if (v->h_claims) (void)hipHostFree(v->h_claims);
-    if (v->claims_done) (void)hipEventDestroy(v->claims_done);
-    for (int i = 0; i < 2; ++i) {
-        if (v->pre_done[i]) (void)hipEventDestroy(v->pre_done[i]);
-        if (v->list_free[i]) (void)hipEventDestroy(v->list_free[i]);
-    }
-    if (v->seq_ready) (void)hipEventDestroy(v->seq_ready);
-    if (v->pre_stream) (void)hipStreamDestroy(v->pre_stream);
-    if (v->rb_stream) (void)hipStreamDestroy(v->rb_stream);
-    if (v->d_shortcut_stats) (void)hipFree(v->d_shortcut_stats);
-    if (v->d_tsdf) (void)hipFree(v->d_tsdf);
-    if (v->d_weight) (void)hipFree(v->d_weight);
-    if (v->own_stream) (void)hipStreamDestroy(v->own_stream);
-    delete v;
+    delete v;            // the owners release the handle's memory, events and streams (its device is current)
     return TSDF_OK;
 }
 
@@ -1561,8 +1521,9 @@ int tsdf_integrate_u16(tsdf_volume *v, const uint16_t *raw_host, float depth_fac
     float c2b[16];
     compose_cam2base(v, cam2world, c2b);
     rc = launch_integrate(v, static_cast<const float *>(dev), nullptr, c2b);
-    if (rc) return give_back(rc);
-    return stage_end(v, &slot, 1);
+    // (after a failed launch too: kernels it queued on the handle's stream may read the slot, so it goes back behind them)
+    const int rc_end = stage_end(v, &slot, 1);
+    return rc ? rc : rc_end;
 }
 
 int tsdf_integrate_device(tsdf_volume *v, const float *depth_dev, const float cam2world[16])
@@ -1722,10 +1683,10 @@ int tsdf_shortcut_stats(tsdf_volume *v, int32_t enable, uint64_t counts_out[3])
         if (v->d_shortcut_stats) HIP_TRY(hipMemcpy(h, v->d_shortcut_stats, sizeof h, hipMemcpyDeviceToHost));
         for (int i = 0; i < 3; ++i) counts_out[i] = h[i];
     }
-    if (enable && !v->d_shortcut_stats) HIP_TRY(hipMalloc((void **)&v->d_shortcut_stats, 8 * sizeof(unsigned int)));
+    if (enable && !v->d_shortcut_stats) HIP_TRY(dev_alloc(v->d_shortcut_stats, 8 * sizeof(unsigned int)));
     if (v->d_shortcut_stats) {
         if (enable) HIP_TRY(hipMemset(v->d_shortcut_stats, 0, 8 * sizeof(unsigned int)));
-        else { (void)hipFree(v->d_shortcut_stats); v->d_shortcut_stats = nullptr; }
+        else v->d_shortcut_stats.reset();
     }
     return TSDF_OK;
 }
@@ -1844,11 +1805,11 @@ int tsdf_selftest_fastdiv(int32_t device, uint64_t seed, uint64_t n_samples, flo
 {
     if (!mismatches || !first_bad) return fail(TSDF_ERR_INVALID, "tsdf_selftest_fastdiv: NULL argument");
     HIP_TRY(hipSetDevice(device));
-    unsigned long long *d_cnt = nullptr;
-    float *d_bad = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_cnt, sizeof *d_cnt));
-    HIP_TRY(hipMalloc((void **)&d_bad, 4 * sizeof(float)));
-    HIP_TRY(hipMemset(d_cnt, 0, sizeof *d_cnt));
+    DevPtr<unsigned long long> d_cnt;
+    DevPtr<float> d_bad;
+    HIP_TRY(dev_alloc(d_cnt, sizeof(unsigned long long)));
+    HIP_TRY(dev_alloc(d_bad, 4 * sizeof(float)));
+    HIP_TRY(hipMemset(d_cnt, 0, sizeof(unsigned long long)));
     HIP_TRY(hipMemset(d_bad, 0, 4 * sizeof(float)));
     hipLaunchKernelGGL(tsdfk::selftest_fastdiv, dim3(256 * 8), dim3(256), 0, 0, seed, n_samples, fx, cx, d_cnt, d_bad);
     hipError_t e = hipGetLastError();
@@ -1856,8 +1817,6 @@ int tsdf_selftest_fastdiv(int32_t device, uint64_t seed, uint64_t n_samples, flo
     unsigned long long cnt = 0;
     if (e == hipSuccess) e = hipMemcpy(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(first_bad, d_bad, 4 * sizeof(float), hipMemcpyDeviceToHost);
-    (void)hipFree(d_cnt);
-    (void)hipFree(d_bad);
     if (e != hipSuccess) return fail(TSDF_ERR_HIP, "tsdf_selftest_fastdiv: %s", hipGetErrorString(e));
     *mismatches = cnt;
     return TSDF_OK;
@@ -1867,11 +1826,11 @@ int tsdf_selftest_fastdiv_band(int32_t device, uint64_t seed, uint64_t n_samples
 {
     if (!mismatches || !first_bad) return fail(TSDF_ERR_INVALID, "tsdf_selftest_fastdiv_band: NULL argument");
     HIP_TRY(hipSetDevice(device));
-    unsigned long long *d_cnt = nullptr;
-    float *d_bad = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_cnt, sizeof *d_cnt));
-    HIP_TRY(hipMalloc((void **)&d_bad, 4 * sizeof(float)));
-    HIP_TRY(hipMemset(d_cnt, 0, sizeof *d_cnt));
+    DevPtr<unsigned long long> d_cnt;
+    DevPtr<float> d_bad;
+    HIP_TRY(dev_alloc(d_cnt, sizeof(unsigned long long)));
+    HIP_TRY(dev_alloc(d_bad, 4 * sizeof(float)));
+    HIP_TRY(hipMemset(d_cnt, 0, sizeof(unsigned long long)));
     HIP_TRY(hipMemset(d_bad, 0, 4 * sizeof(float)));
     hipLaunchKernelGGL(tsdfk::selftest_fastdiv_band, dim3(256 * 8), dim3(256), 0, 0, seed, n_samples, d_cnt, d_bad);
     hipError_t e = hipGetLastError();
@@ -1879,8 +1838,6 @@ int tsdf_selftest_fastdiv_band(int32_t device, uint64_t seed, uint64_t n_samples
     unsigned long long cnt = 0;
     if (e == hipSuccess) e = hipMemcpy(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(first_bad, d_bad, 4 * sizeof(float), hipMemcpyDeviceToHost);
-    (void)hipFree(d_cnt);
-    (void)hipFree(d_bad);
     if (e != hipSuccess) return fail(TSDF_ERR_HIP, "tsdf_selftest_fastdiv_band: %s", hipGetErrorString(e));
     *mismatches = cnt;
     return TSDF_OK;
@@ -1894,9 +1851,9 @@ int tsdf_object_origin(int32_t device, const float *depth_dev, const uint8_t *ma
     HIP_TRY(hipSetDevice(device));
     // the frame may have been produced on a handle's (non-blocking) stream, which the null stream does not order against
     HIP_TRY(hipDeviceSynchronize());
-    float *d_out = nullptr;
+    DevPtr<float> d_out;
     const float init[3] = {1000.0f, 1000.0f, 1000.0f};   // ref: src/Object.cpp:37
-    HIP_TRY(hipMalloc((void **)&d_out, sizeof init));
+    HIP_TRY(dev_alloc(d_out, sizeof init));
     hipError_t e = hipMemcpy(d_out, init, sizeof init, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         const int n = im_height * im_width;
@@ -1905,7 +1862,6 @@ int tsdf_object_origin(int32_t device, const float *depth_dev, const uint8_t *ma
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(origin_out, d_out, sizeof init, hipMemcpyDeviceToHost);
-    (void)hipFree(d_out);
     if (e != hipSuccess) return fail(TSDF_ERR_HIP, "tsdf_object_origin: %s", hipGetErrorString(e));
     return TSDF_OK;
 }
@@ -1914,11 +1870,11 @@ int tsdf_selftest_round(int32_t device, uint64_t *mismatches, float first_bad[4]
 {
     if (!mismatches || !first_bad) return fail(TSDF_ERR_INVALID, "tsdf_selftest_round: NULL argument");
     HIP_TRY(hipSetDevice(device));
-    unsigned long long *d_cnt = nullptr;
-    float *d_bad = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_cnt, sizeof *d_cnt));
-    HIP_TRY(hipMalloc((void **)&d_bad, 4 * sizeof(float)));
-    HIP_TRY(hipMemset(d_cnt, 0, sizeof *d_cnt));
+    DevPtr<unsigned long long> d_cnt;
+    DevPtr<float> d_bad;
+    HIP_TRY(dev_alloc(d_cnt, sizeof(unsigned long long)));
+    HIP_TRY(dev_alloc(d_bad, 4 * sizeof(float)));
+    HIP_TRY(hipMemset(d_cnt, 0, sizeof(unsigned long long)));
     HIP_TRY(hipMemset(d_bad, 0, 4 * sizeof(float)));
     hipLaunchKernelGGL(tsdfk::selftest_round, dim3(256 * 8), dim3(256), 0, 0, d_cnt, d_bad);
     hipError_t e = hipGetLastError();
@@ -1926,8 +1882,6 @@ int tsdf_selftest_round(int32_t device, uint64_t *mismatches, float first_bad[4]
     unsigned long long cnt = 0;
     if (e == hipSuccess) e = hipMemcpy(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(first_bad, d_bad, 4 * sizeof(float), hipMemcpyDeviceToHost);
-    (void)hipFree(d_cnt);
-    (void)hipFree(d_bad);
     if (e != hipSuccess) return fail(TSDF_ERR_HIP, "tsdf_selftest_round: %s", hipGetErrorString(e));
     *mismatches = cnt;
     return TSDF_OK;
@@ -1944,9 +1898,9 @@ int tsdf_selftest_tile_tables(int32_t device, const float *depth_dev, const uint
         const int tw = (im_width + tile - 1) / tile, th = (im_height + tile - 1) / tile;
         if ((int64_t)tw * th > 16384) continue;
         const size_t per = tile_table_elems_host(tw, th);
-        float2 *d_a = nullptr, *d_b = nullptr;
-        HIP_TRY(hipMalloc((void **)&d_a, per * sizeof(float2)));
-        if (hipMalloc((void **)&d_b, per * sizeof(float2)) != hipSuccess) { (void)hipFree(d_a); return fail(TSDF_ERR_HIP, "tsdf_selftest_tile_tables: hipMalloc"); }
+        DevPtr<float2> d_a, d_b;
+        HIP_TRY(dev_alloc(d_a, per * sizeof(float2)));
+        if (dev_alloc(d_b, per * sizeof(float2)) != hipSuccess) return fail(TSDF_ERR_HIP, "tsdf_selftest_tile_tables: hipMalloc");
         (void)hipMemset(d_a, 0xff, per * sizeof(float2));
         (void)hipMemset(d_b, 0x7f, per * sizeof(float2));
         tsdfk::TileSummaryParams tp;
@@ -1975,17 +1929,15 @@ int tsdf_selftest_tile_tables(int32_t device, const float *depth_dev, const uint
         std::vector<float2> a(per), b(per);
         if (e == hipSuccess) e = hipMemcpy(a.data(), d_a, per * sizeof(float2), hipMemcpyDeviceToHost);
         if (e == hipSuccess) e = hipMemcpy(b.data(), d_b, per * sizeof(float2), hipMemcpyDeviceToHost);
-        (void)hipFree(d_a);
-        (void)hipFree(d_b);
         if (e != hipSuccess) return fail(TSDF_ERR_HIP, "tsdf_selftest_tile_tables: %s", hipGetErrorString(e));
         for (size_t i = 0; i < per; ++i) bad += std::memcmp(&a[i], &b[i], sizeof(float2)) != 0;
     }
     {   // the fine table (4-pixel tiles, nine levels): the two kernels the library launches against the pixel-by-pixel one
         const int fw = (im_width + tsdfk::kFineTile - 1) / tsdfk::kFineTile, fh = (im_height + tsdfk::kFineTile - 1) / tsdfk::kFineTile;
         const size_t per = tsdfk::fine_table_elems(fw, fh);
-        float2 *d_a = nullptr, *d_b = nullptr;
-        HIP_TRY(hipMalloc((void **)&d_a, per * sizeof(float2)));
-        if (hipMalloc((void **)&d_b, per * sizeof(float2)) != hipSuccess) { (void)hipFree(d_a); return fail(TSDF_ERR_HIP, "tsdf_selftest_tile_tables: hipMalloc"); }
+        DevPtr<float2> d_a, d_b;
+        HIP_TRY(dev_alloc(d_a, per * sizeof(float2)));
+        if (dev_alloc(d_b, per * sizeof(float2)) != hipSuccess) return fail(TSDF_ERR_HIP, "tsdf_selftest_tile_tables: hipMalloc");
         (void)hipMemset(d_a, 0xff, per * sizeof(float2));
         (void)hipMemset(d_b, 0x7f, per * sizeof(float2));
         tsdfk::FineTileParams fp;
@@ -2009,8 +1961,8 @@ int tsdf_selftest_tile_tables(int32_t device, const float *depth_dev, const uint
             } else {
                 const int tw = (im_width + 7) / 8, th = (im_height + 7) / 8;
                 if ((int64_t)tw * th > tsdfk::kTileLdsEntries) break;
-                float2 *d_c = nullptr;
-                if (hipMalloc((void **)&d_c, tile_table_elems_host(tw, th) * sizeof(float2)) != hipSuccess) { e = hipErrorOutOfMemory; break; }
+                DevPtr<float2> d_c;
+                if (dev_alloc(d_c, tile_table_elems_host(tw, th) * sizeof(float2)) != hipSuccess) { e = hipErrorOutOfMemory; break; }
                 tsdfk::TileSummaryParams tp;
                 for (int f = 0; f < tsdfk::kMaxFramesPerLaunch; ++f) { tp.depth[f] = depth_dev; tp.mask[f] = mask_dev; }
                 tp.H = im_height; tp.W = im_width; tp.tiles_w = tw; tp.tiles_h = th; tp.max_depth = max_depth;
@@ -2021,15 +1973,12 @@ int tsdf_selftest_tile_tables(int32_t device, const float *depth_dev, const uint
                                    d_c, tw, th, (unsigned long long *)nullptr, d_a, fw, fh);
                 e = hipGetLastError();
                 if (e == hipSuccess) e = hipDeviceSynchronize();
-                (void)hipFree(d_c);
             }
             if (e == hipSuccess) e = hipGetLastError();
             if (e == hipSuccess) e = hipDeviceSynchronize();
             if (e == hipSuccess) e = hipMemcpy(a.data(), d_a, per * sizeof(float2), hipMemcpyDeviceToHost);
             if (e == hipSuccess) for (size_t i = 0; i < per; ++i) bad += std::memcmp(&a[i], &b[i], sizeof(float2)) != 0;
         }
-        (void)hipFree(d_a);
-        (void)hipFree(d_b);
         if (e != hipSuccess) return fail(TSDF_ERR_HIP, "tsdf_selftest_tile_tables (fine): %s", hipGetErrorString(e));
     }
     *mismatches = bad;
@@ -2042,9 +1991,9 @@ int tsdf_probe_stream(tsdf_volume *v, int32_t non_temporal, int32_t n_iters, flo
     int rc = bind_device(v);
     if (rc) return rc;
     if (v->n_vox % 4 != 0 || v->n_vox == 0) return fail(TSDF_ERR_INVALID, "tsdf_probe_stream: slab voxels must be a positive multiple of 4");
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
+    Event e0, e1;
+    HIP_TRY(event_create(e0, hipEventDefault));
+    HIP_TRY(event_create(e1, hipEventDefault));
     const size_t nq = (size_t)v->n_vox / 4;
     const int blocks = (int)std::min<size_t>((nq + 255) / 256, (size_t)256 * 8);
     HIP_TRY(hipEventRecord(e0, v->stream));
@@ -2056,8 +2005,6 @@ int tsdf_probe_stream(tsdf_volume *v, int32_t non_temporal, int32_t n_iters, flo
     hipError_t es = hipEventSynchronize(e1);
     float ms = 0.f;
     hipError_t et = hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     if (er != hipSuccess || es != hipSuccess || et != hipSuccess)
         return fail(TSDF_ERR_HIP, "tsdf_probe_stream: event timing failed");
     *elapsed_ms = ms;
@@ -2069,17 +2016,15 @@ static int frames_timed(tsdf_volume *v, const float *const *depth_dev, const uin
 {
     int rc = bind_device(v);
     if (rc) return rc;
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
+    Event e0, e1;
+    HIP_TRY(event_create(e0, hipEventDefault));
+    HIP_TRY(event_create(e1, hipEventDefault));
     HIP_TRY(hipEventRecord(e0, v->stream));
     rc = integrate_frames(v, depth_dev, masks_dev, cam2world, n_frames);
     hipError_t er = hipEventRecord(e1, v->stream);
     hipError_t es = hipEventSynchronize(e1);
     float ms = 0.f;
     hipError_t et = hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     if (rc) return rc;
     if (er != hipSuccess || es != hipSuccess || et != hipSuccess)
         return fail(TSDF_ERR_HIP, "%s: event timing failed", who);
@@ -2115,9 +2060,9 @@ int tsdf_probe_graph_replay(tsdf_volume *v, const float *depth_dev, const float 
         }
         return TSDF_OK;
     };
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
+    Event e0, e1;
+    HIP_TRY(event_create(e0, hipEventDefault));
+    HIP_TRY(event_create(e1, hipEventDefault));
     rc = queue_all();                                   // warm-up (and the summary's one-off work)
     if (rc) return rc;
     HIP_TRY(hipEventRecord(e0, v->stream));
@@ -2127,14 +2072,14 @@ int tsdf_probe_graph_replay(tsdf_volume *v, const float *depth_dev, const float 
     HIP_TRY(hipEventSynchronize(e1));
     HIP_TRY(hipEventElapsedTime(ms_launches, e0, e1));
     *ms_launches /= (float)iters;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
+    Graph graph;
+    GraphExec exec;
     HIP_TRY(hipStreamBeginCapture(v->stream, hipStreamCaptureModeThreadLocal));
     rc = queue_all();
-    hipError_t ce = hipStreamEndCapture(v->stream, &graph);
+    hipError_t ce = hipStreamEndCapture(v->stream, graph.put());
     if (rc) return rc;
     if (ce != hipSuccess) return fail(TSDF_ERR_HIP, "tsdf_probe_graph_replay: capture failed: %s", hipGetErrorString(ce));
-    HIP_TRY(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+    HIP_TRY(hipGraphInstantiate(exec.put(), graph, nullptr, nullptr, 0));
     HIP_TRY(hipGraphLaunch(exec, v->stream));           // warm-up
     HIP_TRY(hipEventRecord(e0, v->stream));
     for (int i = 0; i < iters; ++i) HIP_TRY(hipGraphLaunch(exec, v->stream));
@@ -2142,10 +2087,6 @@ int tsdf_probe_graph_replay(tsdf_volume *v, const float *depth_dev, const float 
     HIP_TRY(hipEventSynchronize(e1));
     HIP_TRY(hipEventElapsedTime(ms_graph, e0, e1));
     *ms_graph /= (float)iters;
-    (void)hipGraphExecDestroy(exec);
-    (void)hipGraphDestroy(graph);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     return TSDF_OK;
 }
 
@@ -2170,10 +2111,13 @@ int tsdf_labels_enable(tsdf_volume *v, float prob_threshold)
     if (rc) return rc;
     v->prob_thd = prob_threshold;
     const size_t n = (size_t)(v->n_vox > 0 ? v->n_vox : 1);
-    if (!v->d_label) {
-        HIP_TRY(hipMalloc((void **)&v->d_label, n * sizeof(uint16_t)));
-        HIP_TRY(hipMalloc((void **)&v->d_fp, n * sizeof(float)));
-        HIP_TRY(hipMalloc((void **)&v->d_bp, n * sizeof(float)));
+    if (!v->d_label) {      // all three or none: the other entry points test d_label alone
+        DevPtr<uint16_t> label;
+        DevPtr<float> fp, bp;
+        HIP_TRY(dev_alloc(label, n * sizeof(uint16_t)));
+        HIP_TRY(dev_alloc(fp, n * sizeof(float)));
+        HIP_TRY(dev_alloc(bp, n * sizeof(float)));
+        v->d_label = std::move(label); v->d_fp = std::move(fp); v->d_bp = std::move(bp);
     }
     HIP_TRY(hipMemsetAsync(v->d_label, 0, n * sizeof(uint16_t), v->stream));
     HIP_TRY(hipMemsetAsync(v->d_fp, 0, n * sizeof(float), v->stream));
@@ -2245,7 +2189,7 @@ int tsdf_colour_enable(tsdf_volume *v)
     int rc = bind_device(v);
     if (rc) return rc;
     const size_t n = (size_t)(v->n_vox > 0 ? v->n_vox : 1);
-    if (!v->d_colour) HIP_TRY(hipMalloc((void **)&v->d_colour, n * sizeof(uint32_t)));
+    if (!v->d_colour) HIP_TRY(dev_alloc(v->d_colour, n * sizeof(uint32_t)));
     HIP_TRY(hipMemsetAsync(v->d_colour, 0, n * sizeof(uint32_t), v->stream));
     return TSDF_OK;
 }
@@ -2286,10 +2230,14 @@ int tsdf_integrate_rgbd(tsdf_volume *v, const float *depth_host, const uint8_t *
     // kernel that read it), the depth frame goes through the shared store like any other host frame
     const int s = v->rgb_next;
     v->rgb_next = (s + 1) % kStageSlots;
-    if (!v->d_rgb[s]) {
-        HIP_TRY(hipMalloc((void **)&v->d_rgb[s], px * 3));
-        HIP_TRY(hipHostMalloc((void **)&v->h_rgb[s], px * 3, hipHostMallocDefault));
-        HIP_TRY(hipEventCreateWithFlags(&v->rgb_done[s], hipEventDisableTiming));
+    if (!v->d_rgb[s]) {      // all three or none
+        DevPtr<uint8_t> d;
+        HostPtr<uint8_t> h;
+        Event done;
+        HIP_TRY(dev_alloc(d, px * 3));
+        HIP_TRY(host_alloc(h, px * 3, hipHostMallocDefault));
+        HIP_TRY(event_create(done));
+        v->d_rgb[s] = std::move(d); v->h_rgb[s] = std::move(h); v->rgb_done[s] = std::move(done);
     }
     if (v->rgb_used[s]) HIP_TRY(hipEventSynchronize(v->rgb_done[s]));
     std::memcpy(v->h_rgb[s], rgb_host, px * 3);           // the caller may free both images after we return
@@ -2345,11 +2293,17 @@ int batch_flush(tsdf_batch *b)
     const int lanes = members < 8 ? 1 : kBatchSideStreams;
     hipError_t e = hipSuccess;
     if (rc == TSDF_OK && lanes > 1) {
-        if (!b->collected) {
-            e = hipEventCreateWithFlags(&b->collected, hipEventDisableTiming);
+        if (!b->collected) {      // all or none
+            Event collected, side_done[kBatchSideStreams];
+            Stream side[kBatchSideStreams];
+            e = event_create(collected);
             for (int k = 0; k < kBatchSideStreams && e == hipSuccess; ++k) {
-                e = hipStreamCreateWithFlags(&b->side[k], hipStreamNonBlocking);
-                if (e == hipSuccess) e = hipEventCreateWithFlags(&b->side_done[k], hipEventDisableTiming);
+                e = stream_create(side[k]);
+                if (e == hipSuccess) e = event_create(side_done[k]);
+            }
+            if (e == hipSuccess) {
+                b->collected = std::move(collected);
+                for (int k = 0; k < kBatchSideStreams; ++k) { b->side[k] = std::move(side[k]); b->side_done[k] = std::move(side_done[k]); }
             }
         }
         if (e == hipSuccess) e = hipEventRecord(b->collected, b->stream);
@@ -2389,14 +2343,14 @@ int batch_collect(tsdf_batch *b, const float *depth_dev, const uint8_t *const *m
     const int members = (int)b->vols.size(), slot = b->pend_count;
     const size_t px = (size_t)b->vols[0]->cfg.im_height * b->vols[0]->cfg.im_width;
     if (!b->d_depth_pool) {
-        HIP_TRY(hipMalloc((void **)&b->d_depth_pool, (size_t)tsdfk::kMaxFramesPerLaunch * px * sizeof(float)));
+        HIP_TRY(dev_alloc(b->d_depth_pool, (size_t)tsdfk::kMaxFramesPerLaunch * px * sizeof(float)));
         b->pend_c2b.assign((size_t)members * tsdfk::kMaxFramesPerLaunch * 16, 0.0f);
         b->pend_mask.assign((size_t)members * tsdfk::kMaxFramesPerLaunch, nullptr);
     }
     bool any_mask = false;
     for (int i = 0; i < members && masks_dev; ++i) any_mask = any_mask || masks_dev[i] != nullptr;
     if (any_mask && !b->d_mask_pool)
-        HIP_TRY(hipMalloc((void **)&b->d_mask_pool, (size_t)tsdfk::kMaxFramesPerLaunch * members * px));
+        HIP_TRY(dev_alloc(b->d_mask_pool, (size_t)tsdfk::kMaxFramesPerLaunch * members * px));
     HIP_TRY(hipMemcpyAsync(b->d_depth_pool + (size_t)slot * px, depth_dev, px * sizeof(float), hipMemcpyDeviceToDevice, b->stream));
     for (int i0 = 0; i0 < members && any_mask; i0 += tsdfk::kGatherMasks) {
         tsdfk::MaskGatherParams gp;
@@ -2434,30 +2388,9 @@ int tsdf_batch_destroy(tsdf_batch *b)
     for (tsdf_volume *v : b->vols) {
         if (v) { v->stream = v->own_stream; v->owner = nullptr; tsdf_destroy(v); }
     }
-    for (int i = 0; i < kStageSlots; ++i) {
-        if (b->h_params[i]) (void)hipHostFree(b->h_params[i]);
-        if (b->d_params[i]) (void)hipFree(b->d_params[i]);
-        if (b->h_poses[i]) (void)hipHostFree(b->h_poses[i]);
-        if (b->d_poses[i]) (void)hipFree(b->d_poses[i]);
-        if (b->slot_done[i]) (void)hipEventDestroy(b->slot_done[i]);
-    }
-    if (b->d_slice_map) (void)hipFree(b->d_slice_map);
-    if (b->d_group_map) (void)hipFree(b->d_group_map);
-    if (b->d_tiles) (void)hipFree(b->d_tiles);
-    if (b->d_wg_class) (void)hipFree(b->d_wg_class);
-    if (b->d_brick_class) (void)hipFree(b->d_brick_class);
-    for (int i = 0; i < kBatchSideStreams; ++i) {
-        if (b->side[i]) { (void)hipStreamSynchronize(b->side[i]); (void)hipStreamDestroy(b->side[i]); }
-        if (b->side_done[i]) (void)hipEventDestroy(b->side_done[i]);
-    }
-    if (b->collected) (void)hipEventDestroy(b->collected);
-    if (b->h_ray) (void)hipHostFree(b->h_ray);
-    if (b->d_ray) (void)hipFree(b->d_ray);
-    if (b->ray_copied) (void)hipEventDestroy(b->ray_copied);
-    if (b->d_depth_pool) (void)hipFree(b->d_depth_pool);
-    if (b->d_mask_pool) (void)hipFree(b->d_mask_pool);
-    if (b->stream) (void)hipStreamDestroy(b->stream);
-    delete b;
+    for (Stream &side : b->side)
+        if (side) (void)hipStreamSynchronize(side);
+    delete b;            // the owners release the batch's memory, events and streams
     return TSDF_OK;
 }
 
@@ -2475,16 +2408,6 @@ int tsdf_batch_create(const tsdf_config *cfgs, int32_t n, tsdf_batch **out)
     tsdf_batch *b = new (std::nothrow) tsdf_batch();
     if (!b) return fail(TSDF_ERR_INVALID, "tsdf_batch_create: out of host memory");
     b->device = cfgs[0].device;
-    b->stream = nullptr; b->d_slice_map = nullptr; b->d_group_map = nullptr; b->total_groups = 0; b->slot_next = 0;
-    b->d_depth_pool = nullptr; b->d_mask_pool = nullptr; b->pend_count = 0; b->in_flush = false;
-    for (int i = 0; i < kBatchSideStreams; ++i) { b->side[i] = nullptr; b->side_done[i] = nullptr; }
-    b->collected = nullptr;
-    b->d_tiles = nullptr; b->tiles_per_object = 0; b->d_wg_class = nullptr; b->d_brick_class = nullptr; b->brick_class_bytes = 0;
-    b->total_slices = b->max_blocks = 0;
-    for (int i = 0; i < kStageSlots; ++i) {
-        b->h_params[i] = nullptr; b->d_params[i] = nullptr; b->h_poses[i] = nullptr; b->d_poses[i] = nullptr;
-        b->slot_done[i] = nullptr; b->slot_used[i] = false;
-    }
     auto cleanup = [&](int code) { tsdf_batch_destroy(b); return code; };
     std::vector<int2> map;
     for (int i = 0; i < n; ++i) {
@@ -2501,15 +2424,15 @@ int tsdf_batch_create(const tsdf_config *cfgs, int32_t n, tsdf_batch **out)
     b->total_slices = (int)map.size();
     if (b->total_slices > 65535) return cleanup(fail(TSDF_ERR_INVALID, "tsdf_batch_create: %d slices in total exceed the launch limit 65535", b->total_slices));
     hipError_t e = hipSetDevice(b->device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
-    if (e == hipSuccess && !map.empty()) e = hipMalloc((void **)&b->d_slice_map, map.size() * sizeof(int2));
+    if (e == hipSuccess) e = stream_create(b->stream);
+    if (e == hipSuccess && !map.empty()) e = dev_alloc(b->d_slice_map, map.size() * sizeof(int2));
     if (e == hipSuccess && !map.empty()) e = hipMemcpy(b->d_slice_map, map.data(), map.size() * sizeof(int2), hipMemcpyHostToDevice);
     for (int i = 0; i < kStageSlots && e == hipSuccess; ++i) {
-        e = hipHostMalloc((void **)&b->h_params[i], n * sizeof(tsdfk::IntegrateParams), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc((void **)&b->d_params[i], n * sizeof(tsdfk::IntegrateParams));
-        if (e == hipSuccess) e = hipHostMalloc((void **)&b->h_poses[i], n * sizeof(tsdfk::FramePose), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc((void **)&b->d_poses[i], n * sizeof(tsdfk::FramePose));
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&b->slot_done[i], hipEventDisableTiming);
+        e = host_alloc(b->h_params[i], n * sizeof(tsdfk::IntegrateParams), hipHostMallocDefault);
+        if (e == hipSuccess) e = dev_alloc(b->d_params[i], n * sizeof(tsdfk::IntegrateParams));
+        if (e == hipSuccess) e = host_alloc(b->h_poses[i], n * sizeof(tsdfk::FramePose), hipHostMallocDefault);
+        if (e == hipSuccess) e = dev_alloc(b->d_poses[i], n * sizeof(tsdfk::FramePose));
+        if (e == hipSuccess) e = event_create(b->slot_done[i]);
     }
     if (e != hipSuccess) return cleanup(fail(TSDF_ERR_HIP, "tsdf_batch_create: %s", hipGetErrorString(e)));
     for (tsdf_volume *v : b->vols) {   // creation fills ran on each volume's own stream: finish them, then share ours
@@ -2592,9 +2515,12 @@ int tsdf_batch_integrate_device(tsdf_batch *b, const float *depth_dev, const uin
                           tiles_fit(b->h_params[s][0]);
     if (classify) {
         const size_t per = tile_table_elems_host(b->h_params[s][0].tiles_w, b->h_params[s][0].tiles_h);
-        if (!b->d_tiles) {
-            HIP_TRY(hipMalloc((void **)&b->d_tiles, (size_t)n * per * sizeof(float2)));
-            if (kExperiments) HIP_TRY(hipMalloc((void **)&b->d_wg_class, (size_t)b->max_blocks * b->total_slices));
+        if (!b->d_tiles) {      // (and, in the measurement build, the class table beside them: both or neither)
+            DevPtr<float2> tiles;
+            DevPtr<uint8_t> wg_class;
+            HIP_TRY(dev_alloc(tiles, (size_t)n * per * sizeof(float2)));
+            if (kExperiments) HIP_TRY(dev_alloc(wg_class, (size_t)b->max_blocks * b->total_slices));
+            b->d_tiles = std::move(tiles); b->d_wg_class = std::move(wg_class);
             b->tiles_per_object = per;
         }
         std::vector<const float *> depths((size_t)n, depth_dev);
@@ -2626,18 +2552,14 @@ int tsdf_batch_integrate_device(tsdf_batch *b, const float *depth_dev, const uin
                 for (int g = 0; g < (q.nz + q.brick_s - 1) / q.brick_s; ++g) gmap.push_back(make_int2(i, g));
             }
             HIP_TRY(hipStreamSynchronize(b->stream));
-            if (b->d_group_map) HIP_TRY(hipFree(b->d_group_map));
-            b->d_group_map = nullptr;
-            HIP_TRY(hipMalloc((void **)&b->d_group_map, std::max<size_t>(gmap.size(), 1) * sizeof(int2)));
+            HIP_TRY(dev_alloc(b->d_group_map, std::max<size_t>(gmap.size(), 1) * sizeof(int2)));
             HIP_TRY(hipMemcpy(b->d_group_map, gmap.data(), gmap.size() * sizeof(int2), hipMemcpyHostToDevice));
             b->total_groups = (int)gmap.size();
         }
         const size_t n_bricks = (size_t)brick_blocks * b->total_groups * 4;
         if (b->brick_class_bytes < n_bricks) {
-            if (b->d_brick_class) HIP_TRY(hipFree(b->d_brick_class));
-            b->d_brick_class = nullptr;
             b->brick_class_bytes = 0;
-            HIP_TRY(hipMalloc((void **)&b->d_brick_class, n_bricks));
+            HIP_TRY(dev_alloc(b->d_brick_class, n_bricks));
             b->brick_class_bytes = n_bricks;
         }
         hipLaunchKernelGGL(tsdfk::classify_bricks_batched, dim3((unsigned)((n_bricks + 255) / 256)), dim3(256), 0, b->stream,
@@ -2702,7 +2624,7 @@ static int surface_pass(tsdf_volume *v, float weight_thresh, float *xyz_host, in
     int64_t n_out = total < capacity ? total : capacity;
     rc = ensure_list(v, (size_t)total * 3 * sizeof(float));
     if (rc) return rc;
-    float *d_xyz = (float *)v->d_list;
+    float *d_xyz = reinterpret_cast<float *>(v->d_list.get());
     const tsdf_config &c = v->cfg;
     hipLaunchKernelGGL(tsdfx::surface_emit, dim3((unsigned)n_chunks), dim3(256), 0, v->stream,
                        v->d_tsdf, v->d_weight, n, weight_thresh, d_offsets, c.dim_x, c.dim_y,
@@ -2777,7 +2699,7 @@ static int crossing_pass(tsdf_volume *v, const float *halo_tsdf, const float *ha
     const int64_t n_out = total < capacity ? total : capacity;
     rc = ensure_list(v, (size_t)total * item_floats * sizeof(float));
     if (rc) return rc;
-    float *d_xyz = (float *)v->d_list;
+    float *d_xyz = reinterpret_cast<float *>(v->d_list.get());
     if (mesh) hipLaunchKernelGGL(tsdfx::mesh_emit_kernel, dim3((unsigned)n_chunks), dim3(256), 0, v->stream, g, d_offsets, d_xyz);
     else hipLaunchKernelGGL(tsdfx::crossing_emit, dim3((unsigned)n_chunks), dim3(256), 0, v->stream, g, d_offsets, d_xyz);
     hipError_t e = hipGetLastError();
@@ -3163,10 +3085,14 @@ int tsdf_batch_raycast_device(tsdf_batch *b, const tsdf_raycast_params *p, const
         if (rc) return rc;
     }
     const int n = (int)b->vols.size();
-    if (!b->d_ray) {
-        HIP_TRY(hipHostMalloc((void **)&b->h_ray, n * sizeof(tsdfk::RayVolume), hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void **)&b->d_ray, n * sizeof(tsdfk::RayVolume)));
-        HIP_TRY(hipEventCreateWithFlags(&b->ray_copied, hipEventDisableTiming));
+    if (!b->d_ray) {      // all three or none
+        HostPtr<tsdfk::RayVolume> h;
+        DevPtr<tsdfk::RayVolume> d;
+        Event copied;
+        HIP_TRY(host_alloc(h, n * sizeof(tsdfk::RayVolume), hipHostMallocDefault));
+        HIP_TRY(dev_alloc(d, n * sizeof(tsdfk::RayVolume)));
+        HIP_TRY(event_create(copied));
+        b->h_ray = std::move(h); b->d_ray = std::move(d); b->ray_copied = std::move(copied);
     }
     if (b->ray_used) HIP_TRY(hipEventSynchronize(b->ray_copied));
     for (int i = 0; i < n; ++i) {

@@ -53,10 +53,8 @@ int classify_single(tsdf_volume *v, tsdfk::IntegrateParams &p, int nbx, int nby,
     if (rc0) return rc0;
     const size_t n_wg = (size_t)nbx * nby * nz;
     if (v->wg_class_bytes < n_wg) {
-        if (v->d_wg_class) HIP_TRY(hipFree(v->d_wg_class));
-        v->d_wg_class = nullptr;
         v->wg_class_bytes = 0;
-        HIP_TRY(hipMalloc((void **)&v->d_wg_class, n_wg));
+        HIP_TRY(dev_alloc(v->d_wg_class, n_wg));
         v->wg_class_bytes = n_wg;
     }
     const float *d = p.depth;
@@ -165,6 +163,12 @@ int launch_single_experiment(tsdf_volume *v, tsdfk::IntegrateParams &common, tsd
     return tables_end(v);
 }
 
+// The fused launches launch_multi_experiment queues itself (launch_multi sizes the product's work list only for the others).
+bool experiment_takes_multi(const tsdf_volume *v, bool labels, bool classify)
+{
+    return (!labels && (v->variant == 4 || v->variant == 5 || v->variant == 6)) || (classify && v->variant >= 11 && v->variant <= 13);
+}
+
 // Fused launches of the measurement build: staged frame blocks (4, 5, 6), rows classified per workgroup (11), brick
 // workgroups over the whole slab (12, 13).  *handled = a launch was queued; *claims_total = its wavefront- or
 // workgroup-frames when it counts claims.
@@ -172,6 +176,7 @@ int launch_multi_experiment(tsdf_volume *v, tsdfk::MultiParamsInline &mi, const 
                             const float *c2b, int n, bool labels, bool any_mask, bool classify, bool *handled, double *claims_total)
 {
     *handled = false;
+    if (!experiment_takes_multi(v, labels, classify)) return TSDF_OK;
     const tsdf_config &c = v->cfg;
     const int nz = c.z_end - c.z_begin;
     const dim3 block(64, 4, 1);
@@ -182,10 +187,14 @@ int launch_multi_experiment(tsdf_volume *v, tsdfk::MultiParamsInline &mi, const 
         const int s = v->frames_next;
         v->frames_next = (s + 1) % kStageSlots;
         const size_t bytes = tsdfk::kMaxFramesPerLaunch * sizeof(tsdfk::FramePose);
-        if (!v->h_frames[s]) {
-            HIP_TRY(hipHostMalloc((void **)&v->h_frames[s], bytes, hipHostMallocDefault));
-            HIP_TRY(hipMalloc((void **)&v->d_frames[s], bytes));
-            HIP_TRY(hipEventCreateWithFlags(&v->frames_done[s], hipEventDisableTiming));
+        if (!v->h_frames[s]) {      // all three or none
+            HostPtr<tsdfk::FramePose> h;
+            DevPtr<tsdfk::FramePose> d;
+            Event done;
+            HIP_TRY(host_alloc(h, bytes, hipHostMallocDefault));
+            HIP_TRY(dev_alloc(d, bytes));
+            HIP_TRY(event_create(done));
+            v->h_frames[s] = std::move(h); v->d_frames[s] = std::move(d); v->frames_done[s] = std::move(done);
         }
         if (v->frames_used[s]) HIP_TRY(hipEventSynchronize(v->frames_done[s]));
         tsdfk::MultiParams mp;
@@ -215,7 +224,6 @@ int launch_multi_experiment(tsdf_volume *v, tsdfk::MultiParamsInline &mi, const 
         *claims_total = 0.0;
         return TSDF_OK;
     }
-    if (!classify || !(v->variant >= 11 && v->variant <= 13)) return TSDF_OK;
     dim3 grid_flat((v->chunks_per_slice + 3) / 4, 1, nz), grid_rows((mi.common.xgroups + 63) / 64, (c.dim_y + 3) / 4, nz);
     const int nz_groups = (nz + mi.common.brick_s - 1) / mi.common.brick_s;
     if (v->variant == 11) {   // rows / 1024 consecutive voxels, classified per workgroup in the prologue
@@ -239,10 +247,8 @@ int launch_multi_experiment(tsdf_volume *v, tsdfk::MultiParamsInline &mi, const 
             mi.nz_super = (nz_groups + tsdfk::kSuperZ - 1) / tsdfk::kSuperZ;
             const size_t words = (size_t)wgs * mi.nz_super;
             if (v->super_words < words) {
-                if (v->d_super) HIP_TRY(hipFree(v->d_super));
-                v->d_super = nullptr;
                 v->super_words = 0;
-                HIP_TRY(hipMalloc((void **)&v->d_super, words * sizeof(unsigned int)));
+                HIP_TRY(dev_alloc(v->d_super, words * sizeof(unsigned int)));
                 v->super_words = words;
             }
             hipLaunchKernelGGL(tsdfk::classify_superbricks, dim3((unsigned)((words + 3) / 4)), block, 0, v->stream, mi, v->d_super, (int)wgs);

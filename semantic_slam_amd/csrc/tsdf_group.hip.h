@@ -20,23 +20,23 @@
 #include <thread>
 
 struct tsdf_group {
-    tsdf_config cfg;                      // the GLOBAL grid (z_begin = 0, z_end = dim_z)
+    tsdf_config cfg = {};                 // the GLOBAL grid (z_begin = 0, z_end = dim_z)
     std::vector<tsdf_volume *> slabs;     // slab i: z in [i*dim_z/n, (i+1)*dim_z/n), on devices[i]
     std::vector<int> devices;
     // pinned frames every device can read (hipHostMallocPortable): a ring for single frames, a pool for sequences
-    float *h_ring[kStageSlots];
-    int ring_next;
-    std::vector<hipEvent_t> ring_copied;  // [ring slot][slab]: that slab's copy out of the slot
+    HostPtr<float> h_ring[kStageSlots];
+    int ring_next = 0;
+    std::vector<Event> ring_copied;       // [ring slot][slab]: that slab's copy out of the slot
     std::vector<bool> ring_used;
-    float *h_pool;                        // kMaxFramesPerLaunch frames, allocated on first tsdf_group_integrate_frames
-    std::vector<float *> d_pool;          // per slab: the same frames in its device's memory
-    std::vector<hipEvent_t> pool_done;    // per slab: the copy of its last pass out of h_pool has run
+    HostPtr<float> h_pool;                // kMaxFramesPerLaunch frames, allocated on first tsdf_group_integrate_frames
+    std::vector<DevPtr<float>> d_pool;    // per slab: the same frames in its device's memory
+    std::vector<Event> pool_done;         // per slab: the copy of its last pass out of h_pool has run
     std::vector<bool> pool_used;
     // deferred integration (as tsdf_integrate on one handle): tsdf_group_integrate collects frames in h_pool and applies
     // defer_n of them per pass as one fused launch per slab; every other group entry point flushes first
-    int defer_n, pend_count;
-    float pend_poses[16 * tsdfk::kMaxFramesPerLaunch];
-    std::vector<float *> d_halo;          // per slab: slice z_end of the next slab (tsdf, then weight), on first use
+    int defer_n = tsdfk::kMaxFramesPerLaunch, pend_count = 0;
+    float pend_poses[16 * tsdfk::kMaxFramesPerLaunch] = {};
+    std::vector<DevPtr<float>> d_halo;    // per slab: slice z_end of the next slab (tsdf, then weight), on first use
 };
 
 namespace {
@@ -73,7 +73,7 @@ int fetch_halo(tsdf_group *g, int i, const float **ht, const float **hw)
     HIP_TRY(hipSetDevice(hi->cfg.device));
     HIP_TRY(hipStreamSynchronize(hi->stream));          // the neighbour's integrations have finished
     HIP_TRY(hipSetDevice(lo->cfg.device));
-    if (!g->d_halo[(size_t)i]) HIP_TRY(hipMalloc((void **)&g->d_halo[(size_t)i], 2 * bytes));
+    if (!g->d_halo[(size_t)i]) HIP_TRY(dev_alloc(g->d_halo[(size_t)i], 2 * bytes));
     float *buf = g->d_halo[(size_t)i];
     HIP_TRY(hipMemcpyPeerAsync(buf, lo->cfg.device, hi->d_tsdf, hi->cfg.device, bytes, lo->stream));
     HIP_TRY(hipMemcpyPeerAsync(buf + slice, lo->cfg.device, hi->d_weight, hi->cfg.device, bytes, lo->stream));
@@ -127,9 +127,12 @@ int group_pass_from_pool(tsdf_group *g, const float *cam2world, int n)
         tsdf_volume *v = g->slabs[i];
         int rc0 = bind_device(v);
         if (rc0) return rc0;
-        if (!g->d_pool[i]) {
-            HIP_TRY(hipMalloc((void **)&g->d_pool[i], (size_t)tsdfk::kMaxFramesPerLaunch * img));
-            HIP_TRY(hipEventCreateWithFlags(&g->pool_done[i], hipEventDisableTiming));
+        if (!g->d_pool[i]) {      // both or neither
+            DevPtr<float> pool;
+            Event done;
+            HIP_TRY(dev_alloc(pool, (size_t)tsdfk::kMaxFramesPerLaunch * img));
+            HIP_TRY(event_create(done));
+            g->d_pool[i] = std::move(pool); g->pool_done[i] = std::move(done);
         }
         // on the slab's stream: ordered after the launch that read d_pool in the previous pass
         HIP_TRY(hipMemcpyAsync(g->d_pool[i], g->h_pool, (size_t)n * img, hipMemcpyHostToDevice, v->stream));
@@ -177,17 +180,14 @@ int tsdf_group_destroy(tsdf_group *g)
         v->group_owner = nullptr;     // frames collected but never observed go with the group
         (void)hipSetDevice(v->cfg.device);
         (void)hipStreamSynchronize(v->stream);
-        if (i < g->d_pool.size() && g->d_pool[i]) (void)hipFree(g->d_pool[i]);
-        if (i < g->pool_done.size() && g->pool_done[i]) (void)hipEventDestroy(g->pool_done[i]);
-        if (i < g->d_halo.size() && g->d_halo[i]) (void)hipFree(g->d_halo[i]);
+        // the slab's own resources go with its device current
+        if (i < g->d_pool.size()) g->d_pool[i].reset();
+        if (i < g->pool_done.size()) g->pool_done[i].reset();
+        if (i < g->d_halo.size()) g->d_halo[i].reset();
+        for (size_t k = i; k < g->ring_copied.size(); k += g->slabs.size()) g->ring_copied[k].reset();
         tsdf_destroy(v);
     }
-    for (hipEvent_t e : g->ring_copied)
-        if (e) (void)hipEventDestroy(e);
-    for (int s = 0; s < kStageSlots; ++s)
-        if (g->h_ring[s]) (void)hipHostFree(g->h_ring[s]);
-    if (g->h_pool) (void)hipHostFree(g->h_pool);
-    delete g;
+    delete g;            // (the pinned ring and pool are portable)
     return TSDF_OK;
 }
 
@@ -203,11 +203,6 @@ int tsdf_group_create(const tsdf_config *cfg, const int32_t *devices, int32_t n_
     g->cfg.z_begin = 0;
     g->cfg.z_end = cfg->dim_z;
     g->cfg.device = devices[0];
-    g->ring_next = 0;
-    g->h_pool = nullptr;
-    g->defer_n = tsdfk::kMaxFramesPerLaunch;
-    g->pend_count = 0;
-    for (int s = 0; s < kStageSlots; ++s) g->h_ring[s] = nullptr;
     auto cleanup = [&](int code) { const std::string keep = g_last_error; tsdf_group_destroy(g); g_last_error = keep; return code; };
     for (int i = 0; i < n_slabs; ++i) {
         tsdf_config c = *cfg;
@@ -221,15 +216,15 @@ int tsdf_group_create(const tsdf_config *cfg, const int32_t *devices, int32_t n_
         g->slabs.push_back(v);
         g->devices.push_back(devices[i]);
     }
-    g->d_pool.assign((size_t)n_slabs, nullptr);
-    g->pool_done.assign((size_t)n_slabs, nullptr);
+    g->d_pool.resize((size_t)n_slabs);
+    g->pool_done.resize((size_t)n_slabs);
     g->pool_used.assign((size_t)n_slabs, false);
-    g->d_halo.assign((size_t)n_slabs, nullptr);
-    g->ring_copied.assign((size_t)n_slabs * kStageSlots, nullptr);
+    g->d_halo.resize((size_t)n_slabs);
+    g->ring_copied.resize((size_t)n_slabs * kStageSlots);
     g->ring_used.assign((size_t)n_slabs * kStageSlots, false);
     const size_t img = (size_t)cfg->im_height * cfg->im_width * sizeof(float);
     for (int s = 0; s < kStageSlots; ++s) {
-        hipError_t e = hipHostMalloc((void **)&g->h_ring[s], img, hipHostMallocPortable);
+        hipError_t e = host_alloc(g->h_ring[s], img, hipHostMallocPortable);
         if (e != hipSuccess) return cleanup(fail(TSDF_ERR_HIP, "tsdf_group_create: pinned frame: %s", hipGetErrorString(e)));
     }
     // neighbouring slabs on different devices exchange one slice at extraction: let the copy go directly over xGMI
@@ -270,7 +265,7 @@ int tsdf_group_integrate(tsdf_group *g, const float *depth_host, const float cam
     if (g->defer_n > 1) {
         // deferred (see tsdf_integrate): the frame into the pinned pool, launched defer_n at a time as one fused sequence
         const size_t px = (size_t)g->cfg.im_height * g->cfg.im_width, bytes = px * sizeof(float);
-        if (!g->h_pool) HIP_TRY(hipHostMalloc((void **)&g->h_pool, (size_t)tsdfk::kMaxFramesPerLaunch * bytes, hipHostMallocPortable));
+        if (!g->h_pool) HIP_TRY(host_alloc(g->h_pool, (size_t)tsdfk::kMaxFramesPerLaunch * bytes, hipHostMallocPortable));
         if (g->pend_count == 0) { int rc = group_wait_pool(g); if (rc) return rc; }
         tsdf_host::copy_to_pinned(g->h_pool + (size_t)g->pend_count * px, depth_host, bytes);
         std::memcpy(g->pend_poses + 16 * g->pend_count, cam2world, 16 * sizeof(float));
@@ -299,7 +294,7 @@ int tsdf_group_integrate(tsdf_group *g, const float *depth_host, const float cam
         int rc = store_slot(v, &v->store->frames, v->copy_stream, &slot, &dev);
         if (rc) return rc;
         HIP_TRY(hipMemcpyAsync(dev, g->h_ring[s], img, hipMemcpyHostToDevice, v->copy_stream));
-        if (!g->ring_copied[(size_t)s * n + i]) HIP_TRY(hipEventCreateWithFlags(&g->ring_copied[(size_t)s * n + i], hipEventDisableTiming));
+        if (!g->ring_copied[(size_t)s * n + i]) HIP_TRY(event_create(g->ring_copied[(size_t)s * n + i]));
         HIP_TRY(hipEventRecord(g->ring_copied[(size_t)s * n + i], v->copy_stream));
         g->ring_used[(size_t)s * n + i] = true;
         HIP_TRY(hipStreamWaitEvent(v->stream, g->ring_copied[(size_t)s * n + i], 0));
@@ -322,7 +317,7 @@ int tsdf_group_integrate_frames(tsdf_group *g, const float *const *depth_host, c
     if (rc) return rc;
     const size_t px = (size_t)g->cfg.im_height * g->cfg.im_width, img = px * sizeof(float);
     const int fpl = tsdfk::kMaxFramesPerLaunch;
-    if (!g->h_pool) HIP_TRY(hipHostMalloc((void **)&g->h_pool, (size_t)fpl * img, hipHostMallocPortable));
+    if (!g->h_pool) HIP_TRY(host_alloc(g->h_pool, (size_t)fpl * img, hipHostMallocPortable));
     for (int k = 0; k < n_frames; k += fpl) {
         const int n = std::min(fpl, n_frames - k);
         rc = group_wait_pool(g);     // the pool is reused per pass
