@@ -456,6 +456,60 @@ int tsdf_raycast(tsdf_volume *vol, const tsdf_raycast_params *p, const float cam
                  float *normal_host, uint16_t *label_host, uint32_t *colour_host);
 
 /*
+ * Tracking: the camera pose of a live depth frame, by point-to-plane ICP against the model's raycast (frame-to-model, as in
+ * KinectFusion).  Not a reference function (its front end takes poses from ORB-SLAM2, ref: result/rgbd/bundle.txt, and tracks
+ * objects through sparse ObjectPoints, ref: src/Engine.cpp:374,550); the rule is stated exactly in csrc/tsdf_track.hip.h and
+ * restated in tests/track_spec.py.  On a batch member's borrowed handle with that object's instance mask it tracks the camera
+ * against one object's model.
+ *   ray                the model render (tsdf_raycast rule): K and image size (= the live frame's), near_m, far_m,
+ *                      weight_thresh; near_m < d <= far_m is also the live frame's valid depth range
+ *   n_levels           1..3; level l uses every 2^l-th pixel of every 2^l-th row of the live frame
+ *   iters[l]           Gauss-Newton iterations of level l (>= 0; 0 skips it); the coarsest level runs first
+ *   dist_thresh[l]     metres (finite, > 0): a pair further apart than this is rejected
+ *   cos_normal_thresh  in [-1, 1]: a pair whose normals' cosine is below this is rejected
+ *   min_inliers        >= 0: an iteration with fewer pairs loses the track
+ *   eps_rot, eps_trans finite, > 0: an update with |omega| < eps_rot (rad) and |tau| < eps_trans (m) ends its level
+ * tsdf_track_params_default: tsdf_raycast_params_default(cfg); 3 levels; iterations {10, 5, 4}; 0.10 m at every level;
+ * cos(20 deg); min_inliers 300 (the coarsest level of a 640x480 frame has 18,921 samples: an object on 5 % of the image
+ * gives about 950 of them, 300 leaves room for two thirds of those to be lost at its edges or to the thresholds); eps 1e-5 rad
+ * and 1e-5 m.  Host arithmetic only: needs no device.
+ */
+typedef struct tsdf_track_params {
+    tsdf_raycast_params ray;
+    int32_t n_levels;
+    int32_t iters[3];
+    float dist_thresh[3];
+    float cos_normal_thresh;
+    int32_t min_inliers;
+    float eps_rot, eps_trans;
+} tsdf_track_params;
+
+typedef struct tsdf_track_result {
+    float cam2world[16];       /* the estimate; the guess's own bits when lost */
+    int32_t status;            /* 0 converged, 1 iterations exhausted, 2 lost (too few pairs, or a failed Cholesky) */
+    int32_t iters_run[3];      /* per level */
+    int32_t inliers;           /* pairs of the last iteration run */
+    float rmse;                /* sqrt(sum r^2 / inliers) of that iteration, metres */
+} tsdf_track_result;
+
+int tsdf_track_params_default(const tsdf_config *cfg, tsdf_track_params *out);
+/*
+ * depth_dev: the live frame, ray.im_height x ray.im_width floats (metres); mask_dev: as many {0, 255} bytes, or NULL.  Applies
+ * the handle's (or its batch's) collected frames, renders the model once at the guess, runs the iterations and returns when
+ * the result is on the host; everything is queued on the handle's stream (tsdf_set_stream ordering holds).  Reads the volume
+ * only.  Lost is not an error: TSDF_OK with status 2.  Whole-grid handles only (a z-slab or a tsdf_group slab is refused).
+ */
+int tsdf_track(tsdf_volume *vol, const tsdf_track_params *p, const float *depth_dev, const uint8_t *mask_dev,
+               const float guess_cam2world[16], tsdf_track_result *out);
+/*
+ * The linear system of one iteration of level `level` (0 <= level < n_levels): the model rendered at ref_cam2world, the live
+ * frame's pairs at cam2world.  system_out: the 21 upper-triangle entries of J^T J (row-major), the 6 of J^T r, sum r^2, the
+ * pair count.  For callers that combine the dense term with residuals of their own.  Returns when the system is on the host.
+ */
+int tsdf_track_system(tsdf_volume *vol, const tsdf_track_params *p, const float *depth_dev, const uint8_t *mask_dev,
+                      const float ref_cam2world[16], const float cam2world[16], int32_t level, double system_out[29]);
+
+/*
  * Grid origin of a new object volume from its first (masked) depth frame, on the device: the per-axis
  * minimum over pixels with depth > 0 of the back-projected point, starting from 1000 -- what
  * Object::Object computes on the host before it constructs its TSDF (ref: src/Object.cpp:37-49, with the

@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "tsdf_download_labels",
     "tsdf_colour_enable", "tsdf_integrate_colour_device", "tsdf_integrate_rgbd", "tsdf_download_colour",
     "tsdf_raycast_params_default", "tsdf_raycast_device", "tsdf_raycast", "tsdf_batch_raycast_device",
+    "tsdf_track_params_default", "tsdf_track", "tsdf_track_system",
     "tsdf_object_origin", "tsdf_batch_create", "tsdf_batch_destroy", "tsdf_batch_size", "tsdf_batch_volume",
     "tsdf_batch_integrate_device", "tsdf_batch_sync",
     "tsdf_group_create", "tsdf_group_destroy", "tsdf_group_size", "tsdf_group_voxels", "tsdf_group_volume",
@@ -77,6 +78,24 @@ class RaycastParams(C.Structure):
         ("near_m", C.c_float), ("far_m", C.c_float), ("weight_thresh", C.c_float),
     ]
 
+
+class TrackParams(C.Structure):
+    """Mirror of `struct tsdf_track_params` (include/tsdf_hip.h)."""
+    _fields_ = [
+        ("ray", RaycastParams), ("n_levels", C.c_int32), ("iters", C.c_int32 * 3), ("dist_thresh", C.c_float * 3),
+        ("cos_normal_thresh", C.c_float), ("min_inliers", C.c_int32), ("eps_rot", C.c_float), ("eps_trans", C.c_float),
+    ]
+
+
+class TrackResult(C.Structure):
+    """Mirror of `struct tsdf_track_result` (include/tsdf_hip.h)."""
+    _fields_ = [
+        ("cam2world", C.c_float * 16), ("status", C.c_int32), ("iters_run", C.c_int32 * 3), ("inliers", C.c_int32),
+        ("rmse", C.c_float),
+    ]
+
+
+TRACK_STATUS = {0: "converged", 1: "iterations exhausted", 2: "lost"}
 
 _lib = None
 
@@ -169,6 +188,9 @@ def load():
     L.tsdf_raycast_device.argtypes = [vp, C.POINTER(RaycastParams), vp, vp, vp, vp, vp]
     L.tsdf_raycast.argtypes = [vp, C.POINTER(RaycastParams), vp, vp, vp, vp, vp]
     L.tsdf_batch_raycast_device.argtypes = [vp, C.POINTER(RaycastParams), vp, vp, vp, vp]
+    L.tsdf_track_params_default.argtypes = [C.POINTER(TsdfConfig), C.POINTER(TrackParams)]
+    L.tsdf_track.argtypes = [vp, C.POINTER(TrackParams), vp, vp, vp, C.POINTER(TrackResult)]
+    L.tsdf_track_system.argtypes = [vp, C.POINTER(TrackParams), vp, vp, vp, vp, C.c_int32, vp]
     L.tsdf_object_origin.argtypes = [C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp]
     L.tsdf_batch_create.argtypes = [C.POINTER(TsdfConfig), C.c_int32, C.POINTER(vp)]
     L.tsdf_batch_destroy.argtypes = [vp]
@@ -279,6 +301,14 @@ def raycast_params_default(cfg):
     """Raycast parameters from a config: its K and image size, near 0, far = max_depth, weight_thresh 0.9 (no device)."""
     p = RaycastParams()
     check(load().tsdf_raycast_params_default(C.byref(cfg), C.byref(p)), "tsdf_raycast_params_default")
+    return p
+
+
+def track_params_default(cfg):
+    """Tracking parameters from a config (include/tsdf_hip.h): raycast_params_default(cfg), 3 levels, iterations
+    {10, 5, 4}, 0.10 m, cos(20 deg), min_inliers 300, eps 1e-5 rad / 1e-5 m (no device)."""
+    p = TrackParams()
+    check(load().tsdf_track_params_default(C.byref(cfg), C.byref(p)), "tsdf_track_params_default")
     return p
 
 
@@ -605,6 +635,33 @@ class Volume:
         c2w = _f32(cam2world, 16)
         check(self.lib.tsdf_raycast_device(self._h, C.byref(p), c2w.ctypes.data, depth_ptr, normal_ptr, label_ptr, colour_ptr),
               "tsdf_raycast_device")
+
+    def track(self, depth_ptr, guess_cam2world, params=None, mask_ptr=None):
+        """Track a live depth frame (device pointer, params.ray's image size) against the model from guess_cam2world
+        (csrc/tsdf_track.hip.h).  Returns (cam2world [4, 4] float32, stats dict with status, status_name, iters_run,
+        inliers, rmse); a lost track returns the guess itself with status 2.  params: a TrackParams, default
+        track_params_default(cfg)."""
+        p = track_params_default(self.cfg) if params is None else params
+        guess = _f32(guess_cam2world, 16)
+        res = TrackResult()
+        check(self.lib.tsdf_track(self._h, C.byref(p), depth_ptr, mask_ptr, guess.ctypes.data, C.byref(res)), "tsdf_track")
+        pose = np.array(res.cam2world, np.float32).reshape(4, 4)
+        stats = {"status": res.status, "status_name": TRACK_STATUS[res.status], "iters_run": list(res.iters_run),
+                 "inliers": res.inliers, "rmse": res.rmse}
+        return pose, stats
+
+    def track_system(self, depth_ptr, ref_cam2world, cam2world, level=0, params=None, mask_ptr=None):
+        """The linear system of one iteration at `level`, model rendered at ref_cam2world, pairs at cam2world:
+        (A = J^T J [6, 6] float64, b = J^T r [6], sum r^2, pair count)."""
+        p = track_params_default(self.cfg) if params is None else params
+        ref, cur = _f32(ref_cam2world, 16), _f32(cam2world, 16)
+        out = np.zeros(29, np.float64)
+        check(self.lib.tsdf_track_system(self._h, C.byref(p), depth_ptr, mask_ptr, ref.ctypes.data, cur.ctypes.data, level,
+                                         out.ctypes.data), "tsdf_track_system")
+        A = np.zeros((6, 6))
+        A[np.triu_indices(6)] = out[:21]
+        A = A + np.triu(A, 1).T
+        return A, out[21:27].copy(), float(out[27]), int(out[28])
 
     # -- outputs ----------------------------------------------------------------------------
     def count_surface(self, weight_thresh=0.9):

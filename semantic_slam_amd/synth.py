@@ -15,6 +15,8 @@ fixes:
 * S-surf -- a sphere in front of a back wall seen from an orbit, optional uint16
   quantisation at the TUM depth factor 5000 (config/TUM3.yaml:34): a realistic mix of
   updated, truncated and out-of-frustum voxels.
+* S-track -- two spheres and a wall that no rigid motion maps onto themselves: the scene the
+  frame-to-model tracking tests converge on (S-surf is degenerate for ICP).
 """
 import math
 
@@ -218,3 +220,82 @@ def look_at_pose(rng, target, distance, jitter=0.15):
     a = rng.uniform(-jitter, jitter, 3)
     R = R @ rot_z(a[2]) @ rot_y(a[1]) @ rot_x(a[0])
     return make_pose(R, pos)
+
+
+# --------------------------------------------------------------------------------------
+# S-track: a scene no rigid motion maps onto itself (frame-to-model tracking)
+# --------------------------------------------------------------------------------------
+class TrackScene:
+    """Two spheres of different radius at different depths in front of a plane wall, all inside the volume.
+
+    S-surf's one sphere in front of a wall is degenerate for ICP: a rotation about the axis through the sphere centre normal
+    to the wall leaves it unchanged.  Here the line through the two centres is not normal to the wall, so every rigid motion
+    moves some surface: the wall pins the translation along its normal and the two tilts, the two centres the rest.
+    Sphere A: centre origin + ext * (0.32, 0.36, 0.40), radius 0.26 * min(ext); sphere B: centre origin + ext * (0.72, 0.66,
+    0.58), radius 0.18 * min(ext); wall: the plane z = origin_z + 0.84 * ext_z, facing the camera, unbounded."""
+
+    def __init__(self, dims, voxel_size, origin, K=TUM_K, h=IM_H, w=IM_W):
+        self.dims = tuple(int(d) for d in dims)
+        self.vs = float(voxel_size)
+        self.origin = np.asarray(origin, dtype=np.float64)
+        ext = np.array(self.dims, dtype=np.float64) * self.vs
+        self.center = self.origin + ext / 2.0
+        self.spheres = [(self.origin + ext * np.array([0.32, 0.36, 0.40]), 0.26 * float(ext.min())),
+                        (self.origin + ext * np.array([0.72, 0.66, 0.58]), 0.18 * float(ext.min()))]
+        self.wall_z = float(self.origin[2] + 0.84 * ext[2])
+        self.K = np.asarray(K, dtype=np.float64)
+        self.h, self.w = h, w
+        u = np.arange(w, dtype=np.float64)
+        v = np.arange(h, dtype=np.float64)
+        self.dir_cam = np.stack(np.broadcast_arrays((u[None, :] - self.K[2]) / self.K[0],
+                                                    (v[:, None] - self.K[5]) / self.K[4],
+                                                    np.ones((h, w))), axis=-1)
+
+    def pose(self, k, n=64, max_yaw_deg=15.0, max_pitch_deg=8.0):
+        """Orbit about the volume centre: yaw sweeps +-max_yaw and pitch +-max_pitch (at twice the rate) over n frames;
+        the camera looks at the centre from the distance of the base camera."""
+        a = 2.0 * math.pi * k / n
+        R = rot_y(math.radians(max_yaw_deg) * math.sin(a)) @ rot_x(math.radians(max_pitch_deg) * math.sin(2.0 * a))
+        t = self.center - R @ np.array([0.0, 0.0, float(self.center[2])])
+        return make_pose(R, t)
+
+    def _hit(self, cam2base):
+        T = np.asarray(cam2base, dtype=np.float64).reshape(4, 4)
+        R, o = T[:3, :3], T[:3, 3]
+        d = self.dir_cam @ R.T  # ray direction per unit camera z, in the base frame
+        z = np.full(d.shape[:2], np.inf)
+        who = np.full(d.shape[:2], -1)
+        a = np.einsum("hwc,hwc->hw", d, d)
+        for i, (c, r) in enumerate(self.spheres):
+            oc = o - c
+            b = 2.0 * np.einsum("hwc,c->hw", d, oc)
+            disc = b * b - 4.0 * a * (float(oc @ oc) - r * r)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                zs = np.where(disc >= 0.0, (-b - np.sqrt(np.maximum(disc, 0.0))) / (2.0 * a), np.inf)
+            zs = np.where(zs > 0.0, zs, np.inf)
+            who = np.where(zs < z, i, who)
+            z = np.minimum(z, zs)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            zw = (self.wall_z - o[2]) / d[..., 2]
+        zw = np.where(np.isfinite(zw) & (zw > 0.0), zw, np.inf)
+        who = np.where(zw < z, 2, who)
+        z = np.minimum(z, zw)
+        return T, d, z, who
+
+    def depth(self, cam2base, quantize=False):
+        """z-depth image (metres, fp32) from a row-major 4x4 camera-to-base pose; 0 where nothing is hit."""
+        _, _, z, _ = self._hit(cam2base)
+        z = np.where(np.isfinite(z), z, 0.0)
+        if quantize:
+            z = np.round(np.clip(z, 0.0, 13.0) * 5000.0) / 5000.0
+        return z.astype(np.float32)
+
+    def normals(self, cam2base):
+        """Unit surface normals in the camera frame, toward the camera, [h, w, 3] fp32; (0, 0, 0) where nothing is hit."""
+        T, d, z, who = self._hit(cam2base)
+        P = T[:3, 3] + np.where(np.isfinite(z), z, 0.0)[..., None] * d
+        n = np.zeros(P.shape)
+        for i, (c, r) in enumerate(self.spheres):
+            n = np.where((who == i)[..., None], (P - c) / r, n)
+        n = np.where((who == 2)[..., None], np.array([0.0, 0.0, -1.0]), n)
+        return (n @ T[:3, :3]).astype(np.float32)             # R^T n
