@@ -2,7 +2,14 @@
 """bench.py -- Mvoxels/s of the HIP TSDF Integrate path (BASELINE.json metric) with its HBM roofline.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--grid 512] [--workload sband|sfull|ssurf|traj]
-                    [--mode frame|fused]
+                    [--mode frame|fused] [--full]
+
+A plain run does what the headline needs and no more: it sets up, warms up, times the K steps, writes --dump-outputs and
+prints the line (metric, value, ms_per_step, config, timing, the roofline of the timed launches).  Everything else the
+script measures or checks -- the companion legs beside the headline, roofline.traffic and the VALU counters of rocprofv3
+--pmc child runs, the touched-voxel count of a fused line, the CPU baseline and, N > 1, the strong_512 / n1_same_job legs
+and the halo + extraction step -- runs with --full alone, where --no-extras, --no-traffic, --no-cpu-baseline and
+--no-extract leave parts of it out again.
 
 One "step" = one Integrate of one 640x480 depth frame into the whole grid.  At N = 1 the workload is
 BASELINE.json configs[1] -- 512^3 @ 5 mm, synthetic depth + pose stream -- as S-band (semantic_slam_amd/synth.py):
@@ -21,7 +28,7 @@ torch.cuda.synchronize() on both sides; ms_per_step = wall / K, max over ranks; 
 the kernel time.  With the same arguments every run integrates the same frames in the same order, so --dump-outputs DIR
 (what the volume holds after the last timed step, as DIR/<name>.npy) can be compared output for output between builds.
 For N > 1 every rank owns one z-slab (no data-path collective; by default WEAK scaling: each rank's slab holds as many
-voxels as the whole N = 1 grid); after the timed region the
+voxels as the whole N = 1 grid); with --full, after the timed region the
 ranks run the one-voxel halo exchange (RCCL) and the halo-fed extraction once and report its time; if that step does
 not come back within 120 s, or raises, the line is still printed (with `extraction_hung` / `extraction.error`) and every
 rank exits non-zero (3 = hung, 4 = failed), so a dead wire shows in the record.  Launch with torch.distributed.run as
@@ -49,7 +56,7 @@ DUMP_BYTES = 64 * 2 ** 20   # --dump-outputs: at most this many bytes of .npy fi
 DUMP_SEED = 20240917       # --dump-outputs: the fixed seed of the voxel sample when a slab's outputs exceed DUMP_BYTES
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=256)
@@ -66,21 +73,25 @@ def parse():
                          "to cut.  weak = every rank integrates a slab as large as the whole --grid (default 512^3) grid: the global "
                          "grid grows with N inside the same physical box (512x512x1024 @ 5 / 5 / 2.5 mm, 512x1024x1024, 1024^3 @ 2.5 mm)")
     ap.add_argument("--dist-world1", action="store_true",
-                    help="with one rank: still create the process group and run the N > 1 code path (barriers, all-reduces, halo step, "
-                         "multi_gpu object) -- the RCCL rehearsal a one-GPU box allows (tests/test_gpu_bench_cli.py)")
+                    help="with one rank: still create the process group and run the N > 1 code path (barriers, all-reduces, multi_gpu "
+                         "object; with --full the halo step) -- the RCCL rehearsal a one-GPU box allows (tests/test_gpu_bench_cli.py)")
     ap.add_argument("--extract-deadline", type=float, default=120.0, help="seconds the post-run halo + extraction step may take")
     ap.add_argument("--inject-fault", choices=["none", "raise", "hang"], default="none",
-                    help="tests only: make the halo + extraction step fail / never return (the line must still be printed and the "
+                    help="tests only, with --full: make the halo + extraction step fail / never return (the line must still be printed and the "
                          "exit code must say so: 4 / 3)")
     ap.add_argument("--emulate-world", type=int, default=0,
                     help="single-GPU rehearsal of one rank of an N-GPU job: integrate only rank 0's z-slab of N")
     ap.add_argument("--emulate-rank", type=int, default=0, help="with --emulate-world N: which rank's z-slab (default 0)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: companion legs, in-run PMC traffic and VALU counters, counted touched "
+                         "voxels, the CPU baseline and, N > 1, the strong_512 / n1_same_job legs and the halo + extraction step (each "
+                         "can be left out again by the --no-* options below).  Without it only the headline runs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the contract's timed region (for profiler runs: no companion legs, which launch more kernels)")
+                    help="with --full: only the contract's timed region (for profiler runs: no companion legs, which launch more kernels)")
     ap.add_argument("--no-traffic", action="store_true",
-                    help="do not measure roofline.traffic (two short rocprofv3 --pmc child runs of this script)")
-    ap.add_argument("--no-extract", action="store_true", help="N > 1: skip the halo exchange + extraction after the timed region")
+                    help="with --full: do not measure roofline.traffic (two short rocprofv3 --pmc child runs of this script)")
+    ap.add_argument("--no-extract", action="store_true", help="with --full, N > 1: skip the halo exchange + extraction after the timed region")
     ap.add_argument("--noise-mm", type=float, default=0.0, help="ssurf / traj: zero-mean Gaussian depth noise, sigma in mm (SURVEY.md 8d), rng seed 1234")
     ap.add_argument("--holes", type=float, default=0.0, help="ssurf / traj: fraction of the image lost to invalid (zero) 8 x 8 pixel blocks, like a real sensor's dropouts")
     ap.add_argument("--voxel-mm", type=float, default=0.0, help="voxel size in mm (default: 5 at 512, 2 at 1024, else 2560 / grid)")
@@ -93,7 +104,7 @@ def parse():
                          "score in (0.8, 1]), composed on the device.  configs[4] as one rank sees it: --workload ssurf --grid 2048 "
                          "--voxel-mm 2 --emulate-world 8 --emulate-rank 1 --labels 6")
     ap.add_argument("--strong-leg", action="store_true",
-                    help="N > 1 (or --dist-world1): run the strong_512 / n1_same_job legs even with --no-extras (tests)")
+                    help="N > 1 (or --dist-world1): run the strong_512 / n1_same_job legs even without --full or with --no-extras (tests)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--depth-cache", default="", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget for the CPU baseline sample")
@@ -101,7 +112,10 @@ def parse():
                     help="after the timed steps, write what the volume holds after the last of them -- TSDF and weight (and the label "
                          "state with --labels) -- as DIR/<name>.npy, float32, at most 64 MB in all: when the slab is larger, the same "
                          "seeded stratified sample of its voxels in every run (N > 1: one set of files per rank, <name>_rank<r>.npy, 64 MB / N each)")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
+    if not a.full:
+        # a plain run does what its headline needs and no more
+        a.no_cpu_baseline = a.no_extras = a.no_traffic = a.no_extract = True
     a.grid_given = bool(a.grid)
     if not a.grid:
         a.grid = 1024 if a.workload == "traj" else 512
@@ -633,9 +647,10 @@ def main():
     del t_out
     # several frames per pass over a scene with free / unseen space: what a launch touches (its voxels updated by at least one
     # of its frames) is counted, not bounded -- every launch of one pass over the step sequence on a fresh volume, weights > 0
-    # counted on the device; per fpl frames, like the measured traffic it is compared with
+    # counted on the device; per fpl frames, like the measured traffic it is compared with.  These launches of their own run
+    # with --full only
     touched_per_launch, labelled_per_launch = None, 0.0
-    if fpl > 1 and not W.full_coverage and world == 1:
+    if fpl > 1 and not W.full_coverage and world == 1 and args.full:
         nz_s = ze - zb
         t_dev = torch.empty(n_slab, dtype=torch.float32, device="cuda")
         w_dev = torch.empty(n_slab, dtype=torch.float32, device="cuda")
@@ -788,7 +803,7 @@ def main():
         unit_name = ("voxel updated by at least one frame of the launch (4 B TSDF + 4 B weight, read once and written once per "
                      "launch)" + ("" if touched_per_launch is None and W.full_coverage else
                                   "; counted per launch on a fresh volume over one pass of the pose sequence, mean per 32 frames" if touched_per_launch is not None else
-                                  "; bounded by frames x updates per frame (N > 1: not counted)"))
+                                  "; bounded by frames x updates per frame (not counted: N > 1 or a run without --full)"))
         bytes_model = "16 B x voxels touched by the launch + frames per launch x (4*H*W + 100)" + (
             "" if args.labels <= 0 else " + 20 B x voxels that received label evidence in the launch (u16 label + f32 Fp + f32 Bp, read and "
             "written) + frames per launch x 6*H*W (label and score images)")

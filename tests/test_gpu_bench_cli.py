@@ -7,7 +7,8 @@
     tensors, the halo step (no neighbour), extraction, `multi_gpu` -- on the real library.
   * a halo step that raises / never returns: the line is still printed, the process exits 4 / 3.
   * --steps times exactly that many steps, and --dump-outputs writes the same arrays in every run with the same arguments.
-Short runs (--steps 5, no companion legs, no PMC passes, no CPU baseline)."""
+Short runs (--steps 5, no companion legs, no PMC passes, no CPU baseline); what only --full runs (the halo + extraction step)
+is asked for with FULL_QUICK, and a plain run is checked to run the headline alone."""
 import json
 import os
 import socket
@@ -20,6 +21,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 QUICK = ["--steps", "5", "--warmup", "2", "--no-extras", "--no-traffic", "--no-cpu-baseline"]
+FULL_QUICK = ["--full"] + QUICK         # the same legs left out, but the N > 1 halo + extraction step runs
 
 
 def run(cmd, env=None, timeout=300):
@@ -81,7 +83,7 @@ def test_two_ranks_as_the_driver_launches_them(cuda):
     port = so.getsockname()[1]
     so.close()
     rc, lines, err = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", str(port), "bench.py", "--gpus", "2", "--grid", "256", "--strong-leg"] + QUICK,
+                          "--master-port", str(port), "bench.py", "--gpus", "2", "--grid", "256", "--strong-leg"] + FULL_QUICK,
                          env={"TSDF_BENCH_BACKEND": "gloo"})
     assert rc == 0, err
     assert len(lines) == 1, "rank 0 alone prints"
@@ -109,7 +111,7 @@ def test_two_ranks_as_the_driver_launches_them(cuda):
 
 
 def test_one_rank_runs_the_multi_gpu_path_over_rccl(cuda):
-    rc, lines, err = run([sys.executable, "bench.py", "--dist-world1", "--grid", "256"] + QUICK)
+    rc, lines, err = run([sys.executable, "bench.py", "--dist-world1", "--grid", "256"] + FULL_QUICK)
     assert rc == 0, err
     d = json.loads(lines[0])
     m = d["multi_gpu"]
@@ -119,7 +121,7 @@ def test_one_rank_runs_the_multi_gpu_path_over_rccl(cuda):
 
 @pytest.mark.parametrize("fault,code", [("raise", 4), ("hang", 3)])
 def test_a_dead_wire_shows_in_the_exit_code(cuda, fault, code):
-    rc, lines, err = run([sys.executable, "bench.py", "--dist-world1", "--grid", "256", "--inject-fault", fault, "--extract-deadline", "3"] + QUICK)
+    rc, lines, err = run([sys.executable, "bench.py", "--dist-world1", "--grid", "256", "--inject-fault", fault, "--extract-deadline", "3"] + FULL_QUICK)
     assert rc == code, (rc, err)
     assert len(lines) == 1, "the line is printed all the same"
     d = json.loads(lines[0])
@@ -154,3 +156,33 @@ def test_weak_scaling_is_still_there_and_says_so(cuda):
     assert d["scaling"] == "weak" and d["config"]["grid"] == [1024, 1024, 1024] and d["config"]["voxel_size_m"] == 0.0025
     assert "1024x1024x1024 @ 2.5 mm" in d["config"]["workload"] and "weak scaling" in d["config"]["partition"]
     assert d["roofline"]["units_per_launch"] == 512 ** 3
+
+
+def test_a_plain_run_is_the_headline_alone(cuda):
+    """Without --full the line is the headline and the roofline of its timed launches: no companion leg, no PMC child run, no
+    CPU baseline and, on the N > 1 path, neither the strong_512 / n1_same_job legs nor the halo + extraction step."""
+    rc, lines, err = run([sys.executable, "bench.py", "--grid", "256", "--steps", "5", "--warmup", "2"])
+    assert rc == 0, err
+    d = json.loads(lines[0])
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["value"] > 0 and 0.3 < d["roofline"]["frac"] <= 1.0
+    for k in ("per_frame_launches", "fused_sequence", "sfull", "realistic_workload", "realistic_workload_noisy", "configs2_traj1024",
+              "host_depth_path", "cpu_baseline", "cpu_reference", "multi_gpu", "extraction"):
+        assert k not in d, k
+    assert d["roofline"]["traffic"] is None and d["roofline"]["kernel_name_source"].startswith("static")
+    rc, lines, err = run([sys.executable, "bench.py", "--dist-world1", "--grid", "256", "--steps", "5", "--warmup", "2"])
+    assert rc == 0, err
+    d = json.loads(lines[0])
+    assert d["multi_gpu"]["world"] == 1 and d["multi_gpu"]["halo_and_extraction_ran"] is False
+    for k in ("extraction", "extraction_hung", "strong_512", "n1_same_job"):
+        assert k not in d, k
+
+
+def test_full_runs_the_companion_legs(cuda):
+    """--full runs what a plain run leaves out (here without the PMC passes, and with a short CPU sample)."""
+    rc, lines, err = run([sys.executable, "bench.py", "--full", "--grid", "256", "--steps", "5", "--warmup", "2", "--no-traffic",
+                          "--cpu-seconds", "1"])
+    assert rc == 0, err
+    d = json.loads(lines[0])
+    for k in ("fused_sequence", "sfull", "realistic_workload", "realistic_workload_noisy", "host_depth_path", "cpu_baseline"):
+        assert k in d, k
+    assert d["fused_sequence"]["value"] > 0 and d["cpu_baseline"]["value"] > 0 and d["realistic_workload"]["frames"] > 0
