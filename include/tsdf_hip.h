@@ -557,6 +557,84 @@ int tsdf_batch_raycast_device(tsdf_batch *batch, const tsdf_raycast_params *p, c
                               float *normal_dev, int32_t *member_dev);
 
 /*
+ * Association: which object of a batch each instance mask of a live frame shows -- step 1 of the reference's per-instance
+ * object loop (ref: src/Engine.cpp:172-233, TrackObjectPoints at src/Engine.cpp:356-496), on the dense models.  The batch is
+ * rendered at cam2world (tsdf_batch_raycast_device: member[p] in {-1, 0..M-1}, rdepth[p]); a counting kernel compares the
+ * render with the live depth under every mask (csrc/tsdf_associate.hip.h states the per-pixel rule); the host assigns.  Both
+ * are restated in tests/associate_spec.py.
+ *   Per pixel p of the live frame d = depth[p]:
+ *     live valid   isfinite(d) && near_m < d && d <= far_m (ray.near_m / ray.far_m; tsdf_track's test)
+ *     in mask k    masks[k*H*W + p] >= 128 (the masked Integrate's test); masks: K contiguous H*W byte images (MaskRCNN layout)
+ *     rendered     0 <= member[p] < M
+ *     class        of a rendered pixel with valid live depth, r = d - rdepth[p] (float32):  agree if fabsf(r) <= depth_tol_m,
+ *                  front if r < -depth_tol_m (something occludes the model: the reference's occlusion assumption,
+ *                  ref: src/Engine.cpp:399), behind otherwise (the camera sees through where the model has a surface)
+ *   Counts, uint32, one block of 3*K*M + 3*K + 4*M words in this order:
+ *     overlap[k][m][c]  c in {agree, front, behind}: pixels in mask k rendered as member m, of class c
+ *     mask[k][j]        j in {in mask, and live valid, and live valid and not rendered} (the last: what no object explains)
+ *     member[m][c]      c in {agree, front, behind, rendered with live not valid}, over the whole image
+ *   Assignment, host arithmetic, exact and deterministic: a = overlap[k][m][agree], u = mask[k][1] + member[m][0] - a (the
+ *   union of the mask's valid pixels and the member's agreeing ones; 64-bit).  (k, m) is a candidate iff a >= min_pixels and
+ *   (double)a >= (double)min_iou * (double)u; with a label block also iff mask_label[k] == member_label[m] ||
+ *   member_score[m] > 1.1f * mask_score[k] (float32; the reference's c3 || c4, ref: src/Engine.cpp:437-443).
+ *   one_to_one = 1: candidates are accepted greedily by IoU a / u in descending order -- compared exactly, a1 * u2 against
+ *   a2 * u1 as integers -- ties to the lower k, then the lower m; a candidate whose mask or member is taken is skipped.
+ *   one_to_one = 0: each mask takes its best candidate, ties to the lower m.
+ *   Outputs: assign[k] = the member or -1 (no candidate: "create an object"); iou[k] = (float)((double)a / (double)u), 0 when
+ *   unassigned.  A block with some overlap[k][m][agree] above mask[k][1] or member[m][0] cannot come from an image and is
+ *   refused.
+ * Deviations from the reference: it takes the FIRST object in its set's order that passes (not the best), counts sparse
+ * ObjectPoints projected into the keyframe (not pixels of a render) and needs each point mnDist pixels inside the mask's
+ * contour (an erosion, not applied here); its contour-shape test c2 (matchShapes) is disabled there and absent here.
+ *   depth_tol_m   finite, > 0                        min_pixels   >= 1
+ *   min_iou       in [0, 1]                          one_to_one   0 or 1
+ * tsdf_associate_params_default: ray = tsdf_raycast_params_default(cfg); depth_tol_m = cfg->trunc_margin (a fused surface sits
+ * within a fraction of the truncation band of the depth that made it, so an agreeing pixel is off by less; a looser tolerance
+ * would take a nearby occluder for the model); min_pixels 25 (the reference's Engine.mMinArea, ref: config/TUM3.yaml:88);
+ * min_iou 0.25 (a mask half covered by a model that is twice its size still passes -- partial views and fusion holes are
+ * common -- while a mask that merely touches a neighbour does not); one_to_one 1 (one instance is one object in a keyframe).
+ * Host arithmetic only: needs no device.
+ */
+typedef struct tsdf_associate_params {
+    tsdf_raycast_params ray;   /* render; near_m / far_m are also the live depth range */
+    float depth_tol_m;         /* finite, > 0 */
+    int32_t min_pixels;        /* >= 1 */
+    float min_iou;             /* in [0, 1] */
+    int32_t one_to_one;        /* 0 or 1 */
+} tsdf_associate_params;
+typedef struct tsdf_associate_labels {   /* optional; every pointer is a host array */
+    const uint16_t *mask_label; const float *mask_score;       /* K each */
+    const uint16_t *member_label; const float *member_score;   /* M each */
+} tsdf_associate_labels;
+
+int tsdf_associate_params_default(const tsdf_config *cfg, tsdf_associate_params *out);
+/*
+ * The counts over images the caller supplies (ray.im_height x ray.im_width each): member_dev int32, rdepth_dev and depth_dev
+ * floats, masks_dev K images of bytes, all device pointers on `device`; 1 <= k <= 256, 1 <= n_members <= 65536.  Waits for
+ * all work queued on the device (whatever stream produced the images) before it reads, and returns when the block is in
+ * counts_host (3*k*n_members + 3*k + 4*n_members words).
+ */
+int tsdf_associate_count(int32_t device, const tsdf_associate_params *p, const int32_t *member_dev,
+                         const float *rdepth_dev, int32_t n_members, const float *depth_dev,
+                         const uint8_t *masks_dev, int32_t k, uint32_t *counts_host);
+/* The assignment on a count block (labels may be NULL).  Host arithmetic only: needs no device. */
+int tsdf_associate_assign(const tsdf_associate_params *p, const uint32_t *counts_host, int32_t k,
+                          int32_t n_members, const tsdf_associate_labels *labels,
+                          int32_t *assign_out, float *iou_out);
+/*
+ * The product call: applies the batch's collected frames, renders every member at cam2world into scratch the batch owns,
+ * counts under the k masks (masks_dev: k contiguous im_height x im_width byte images; depth_dev: the live frame) and assigns;
+ * returns when assign_out / iou_out (k each) and, unless NULL, counts_host (3*k*M + 3*k + 4*M words, M = tsdf_batch_size)
+ * are on the host.  Everything is queued on the batch's stream; the volumes are only read.  Whole-grid members only.
+ * Refused: a NULL argument (but counts_host and labels), k outside 1..256, ray.im_height / im_width unlike the batch's image
+ * size, and every invalid parameter above.
+ */
+int tsdf_batch_associate(tsdf_batch *batch, const tsdf_associate_params *p, const float cam2world[16],
+                         const float *depth_dev, const uint8_t *masks_dev, int32_t k,
+                         const tsdf_associate_labels *labels, uint32_t *counts_host /* may be NULL */,
+                         int32_t *assign_out, float *iou_out);
+
+/*
  * One grid over several devices in ONE process.  The reference's host is a C++ program that owns its TSDFs directly
  * (ref: include/tsdf.hpp:22-43; src/Engine.cpp:170-172 drives distinct TSDFs from one loop), so a C++ caller must be
  * able to span the node without a process per GPU.  tsdf_group_create cuts the grid of *cfg (its z_begin / z_end /

@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "tsdf_colour_enable", "tsdf_integrate_colour_device", "tsdf_integrate_rgbd", "tsdf_download_colour",
     "tsdf_raycast_params_default", "tsdf_raycast_device", "tsdf_raycast", "tsdf_batch_raycast_device",
     "tsdf_track_params_default", "tsdf_track", "tsdf_track_system",
+    "tsdf_associate_params_default", "tsdf_associate_count", "tsdf_associate_assign", "tsdf_batch_associate",
     "tsdf_object_origin", "tsdf_batch_create", "tsdf_batch_destroy", "tsdf_batch_size", "tsdf_batch_volume",
     "tsdf_batch_integrate_device", "tsdf_batch_sync",
     "tsdf_group_create", "tsdf_group_destroy", "tsdf_group_size", "tsdf_group_voxels", "tsdf_group_volume",
@@ -93,6 +94,20 @@ class TrackResult(C.Structure):
         ("cam2world", C.c_float * 16), ("status", C.c_int32), ("iters_run", C.c_int32 * 3), ("inliers", C.c_int32),
         ("rmse", C.c_float),
     ]
+
+
+class AssociateParams(C.Structure):
+    """Mirror of `struct tsdf_associate_params` (include/tsdf_hip.h)."""
+    _fields_ = [
+        ("ray", RaycastParams), ("depth_tol_m", C.c_float), ("min_pixels", C.c_int32), ("min_iou", C.c_float),
+        ("one_to_one", C.c_int32),
+    ]
+
+
+class AssociateLabels(C.Structure):
+    """Mirror of `struct tsdf_associate_labels` (include/tsdf_hip.h): four host arrays."""
+    _fields_ = [("mask_label", C.c_void_p), ("mask_score", C.c_void_p), ("member_label", C.c_void_p),
+                ("member_score", C.c_void_p)]
 
 
 TRACK_STATUS = {0: "converged", 1: "iterations exhausted", 2: "lost"}
@@ -191,6 +206,12 @@ def load():
     L.tsdf_track_params_default.argtypes = [C.POINTER(TsdfConfig), C.POINTER(TrackParams)]
     L.tsdf_track.argtypes = [vp, C.POINTER(TrackParams), vp, vp, vp, C.POINTER(TrackResult)]
     L.tsdf_track_system.argtypes = [vp, C.POINTER(TrackParams), vp, vp, vp, vp, C.c_int32, vp]
+    L.tsdf_associate_params_default.argtypes = [C.POINTER(TsdfConfig), C.POINTER(AssociateParams)]
+    L.tsdf_associate_count.argtypes = [C.c_int32, C.POINTER(AssociateParams), vp, vp, C.c_int32, vp, vp, C.c_int32, vp]
+    L.tsdf_associate_assign.argtypes = [C.POINTER(AssociateParams), vp, C.c_int32, C.c_int32, C.POINTER(AssociateLabels), vp,
+                                        vp]
+    L.tsdf_batch_associate.argtypes = [vp, C.POINTER(AssociateParams), vp, vp, vp, C.c_int32, C.POINTER(AssociateLabels),
+                                       vp, vp, vp]
     L.tsdf_object_origin.argtypes = [C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp]
     L.tsdf_batch_create.argtypes = [C.POINTER(TsdfConfig), C.c_int32, C.POINTER(vp)]
     L.tsdf_batch_destroy.argtypes = [vp]
@@ -310,6 +331,53 @@ def track_params_default(cfg):
     p = TrackParams()
     check(load().tsdf_track_params_default(C.byref(cfg), C.byref(p)), "tsdf_track_params_default")
     return p
+
+
+def associate_params_default(cfg):
+    """Association parameters from a config (include/tsdf_hip.h): raycast_params_default(cfg), depth_tol_m = trunc_margin,
+    min_pixels 25, min_iou 0.25, one_to_one 1 (no device)."""
+    p = AssociateParams()
+    check(load().tsdf_associate_params_default(C.byref(cfg), C.byref(p)), "tsdf_associate_params_default")
+    return p
+
+
+def associate_split(counts, k, n_members):
+    """The three count arrays of a block, as views: overlap [k, M, 3] (agree, front, behind), mask [k, 3] (in mask, and live
+    valid, and not rendered), member [M, 4] (agree, front, behind, live not valid)."""
+    n_ov = 3 * k * n_members
+    return (counts[:n_ov].reshape(k, n_members, 3), counts[n_ov:n_ov + 3 * k].reshape(k, 3),
+            counts[n_ov + 3 * k:].reshape(n_members, 4))
+
+
+def _associate_labels(labels):
+    """(mask_label, mask_score, member_label, member_score) -> the C block and the arrays it points into (kept alive)."""
+    if labels is None:
+        return None, ()
+    arrs = (np.ascontiguousarray(labels[0], np.uint16), np.ascontiguousarray(labels[1], np.float32),
+            np.ascontiguousarray(labels[2], np.uint16), np.ascontiguousarray(labels[3], np.float32))
+    return C.byref(AssociateLabels(*[a.ctypes.data for a in arrs])), arrs
+
+
+def associate_count(params, member_ptr, rdepth_ptr, n_members, depth_ptr, masks_ptr, k, device=0):
+    """Counts of the association rule over caller images (device pointers); returns (block, overlap, mask, member)."""
+    counts = np.empty(3 * k * n_members + 3 * k + 4 * n_members, np.uint32)
+    check(load().tsdf_associate_count(device, C.byref(params), member_ptr, rdepth_ptr, n_members, depth_ptr, masks_ptr, k,
+                                      counts.ctypes.data), "tsdf_associate_count")
+    return (counts,) + associate_split(counts, k, n_members)
+
+
+def associate_assign(params, counts, k, n_members, labels=None):
+    """The assignment on a count block (host only); labels: None or (mask_label, mask_score, member_label, member_score).
+    Returns (assign int32 [k], iou float32 [k])."""
+    counts = np.ascontiguousarray(counts, np.uint32)
+    if counts.size != 3 * k * n_members + 3 * k + 4 * n_members:
+        raise ValueError(f"a block of {counts.size} words does not fit k = {k}, n_members = {n_members}")
+    lab, keep = _associate_labels(labels)
+    assign, iou = np.empty(k, np.int32), np.empty(k, np.float32)
+    check(load().tsdf_associate_assign(C.byref(params), counts.ctypes.data, k, n_members, lab, assign.ctypes.data,
+                                       iou.ctypes.data), "tsdf_associate_assign")
+    del keep
+    return assign, iou
 
 
 def selftest_round(device=0):
@@ -774,6 +842,24 @@ class Batch:
         c2w = _f32(cam2world, 16)
         check(self.lib.tsdf_batch_raycast_device(self._h, C.byref(p), c2w.ctypes.data, depth_ptr, normal_ptr, member_ptr),
               "tsdf_batch_raycast_device")
+
+    def associate(self, cam2world, depth_ptr, masks_ptr, k, params=None, labels=None):
+        """Which member each of the k instance masks (masks_ptr: k contiguous H x W byte images on the device) shows in the
+        live frame depth_ptr at cam2world (tsdf_batch_associate).  params default: associate_params_default of the first
+        member's config; labels: None or (mask_label, mask_score, member_label, member_score).  Returns a dict: overlap
+        [k, M, 3], mask [k, 3], member [M, 4] (views of the count block `counts`), assign int32 [k] (-1: no member),
+        iou float32 [k]."""
+        p = associate_params_default(self.cfgs[0]) if params is None else params
+        c2w = _f32(cam2world, 16)
+        n = len(self.cfgs)
+        counts = np.empty(3 * k * n + 3 * k + 4 * n, np.uint32)
+        assign, iou = np.empty(k, np.int32), np.empty(k, np.float32)
+        lab, keep = _associate_labels(labels)
+        check(self.lib.tsdf_batch_associate(self._h, C.byref(p), c2w.ctypes.data, depth_ptr, masks_ptr, k, lab,
+                                            counts.ctypes.data, assign.ctypes.data, iou.ctypes.data), "tsdf_batch_associate")
+        del keep
+        overlap, mask, member = associate_split(counts, k, n)
+        return {"counts": counts, "overlap": overlap, "mask": mask, "member": member, "assign": assign, "iou": iou}
 
     def close(self):
         if self._h:

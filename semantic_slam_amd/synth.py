@@ -17,6 +17,8 @@ fixes:
   updated, truncated and out-of-frustum voxels.
 * S-track -- two spheres and a wall that no rigid motion maps onto themselves: the scene the
   frame-to-model tracking tests converge on (S-surf is degenerate for ICP).
+* S-objects -- a few spheres and boxes of different sizes in front of a wall, with a per-pixel instance id: the scene
+  the association tests (one object volume per instance) are built on.
 """
 import math
 
@@ -299,3 +301,84 @@ class TrackScene:
             n = np.where((who == i)[..., None], (P - c) / r, n)
         n = np.where((who == 2)[..., None], np.array([0.0, 0.0, -1.0]), n)
         return (n @ T[:3, :3]).astype(np.float32)             # R^T n
+
+
+# --------------------------------------------------------------------------------------
+# S-objects: several object instances in front of a wall (instance association)
+# --------------------------------------------------------------------------------------
+OBJECTS = (("sphere", (-0.35, -0.15, 1.30), 0.12),
+           ("box", (0.05, -0.30, 1.15), (0.30, -0.05, 1.40)),
+           ("sphere", (0.25, 0.22, 1.50), 0.16),
+           ("box", (-0.40, 0.10, 1.45), (-0.15, 0.32, 1.65)))
+
+
+class ObjectScene:
+    """Objects in the base frame (camera 0 at the origin looking along +z) in front of the plane wall z = wall_z: by default
+    OBJECTS, two spheres and two boxes of different sizes that the poses of `pose` see apart.  An object is
+    ("sphere", centre, radius) or ("box", lo, hi) (axis-aligned).  `depth` gives the z-depth, `ids` the index of the object
+    seen at each pixel (-1: the wall or nothing) for any camera-to-base pose."""
+
+    def __init__(self, objects=OBJECTS, wall_z=2.0, K=TUM_K, h=IM_H, w=IM_W):
+        self.objects = [(o[0], np.asarray(o[1], np.float64), o[2] if o[0] == "sphere" else np.asarray(o[2], np.float64))
+                        for o in objects]
+        self.wall_z = float(wall_z)
+        self.K = np.asarray(K, dtype=np.float64)
+        self.h, self.w = h, w
+        u = np.arange(w, dtype=np.float64)
+        v = np.arange(h, dtype=np.float64)
+        self.dir_cam = np.stack(np.broadcast_arrays((u[None, :] - self.K[2]) / self.K[0],
+                                                    (v[:, None] - self.K[5]) / self.K[4],
+                                                    np.ones((h, w))), axis=-1)
+
+    def bounds(self, i):
+        """Axis-aligned bounds (lo, hi) of object i."""
+        kind, a, b = self.objects[i]
+        return (a - b, a + b) if kind == "sphere" else (a, b)
+
+    @staticmethod
+    def pose(k, n=16, max_yaw_deg=8.0, max_pitch_deg=5.0, center=(0.0, 0.0, 1.4)):
+        """Orbit about `center`: yaw +-max_yaw and pitch +-max_pitch (at twice the rate) over n frames, looking at the
+        centre from its distance to the origin."""
+        c = np.asarray(center, np.float64)
+        a = 2.0 * math.pi * k / n
+        R = rot_y(math.radians(max_yaw_deg) * math.sin(a)) @ rot_x(math.radians(max_pitch_deg) * math.sin(2.0 * a))
+        t = c - R @ np.array([0.0, 0.0, float(np.linalg.norm(c))])
+        return make_pose(R, t)
+
+    def _hit(self, cam2base):
+        T = np.asarray(cam2base, dtype=np.float64).reshape(4, 4)
+        R, o = T[:3, :3], T[:3, 3]
+        d = self.dir_cam @ R.T  # ray direction per unit camera z, in the base frame
+        z = np.full(d.shape[:2], np.inf)
+        who = np.full(d.shape[:2], -1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            for i, (kind, a, b) in enumerate(self.objects):
+                if kind == "sphere":
+                    oc = o - a
+                    qa = np.einsum("hwc,hwc->hw", d, d)
+                    qb = 2.0 * np.einsum("hwc,c->hw", d, oc)
+                    disc = qb * qb - 4.0 * qa * (float(oc @ oc) - b * b)
+                    zs = np.where(disc >= 0.0, (-qb - np.sqrt(np.maximum(disc, 0.0))) / (2.0 * qa), np.inf)
+                else:
+                    t0 = (a - o) / d
+                    t1 = (b - o) / d
+                    tn = np.nanmax(np.minimum(t0, t1), axis=-1)
+                    tf = np.nanmin(np.maximum(t0, t1), axis=-1)
+                    zs = np.where(tn <= tf, tn, np.inf)
+                zs = np.where(zs > 0.0, zs, np.inf)
+                who = np.where(zs < z, i, who)
+                z = np.minimum(z, zs)
+            zw = (self.wall_z - o[2]) / d[..., 2]
+        zw = np.where(np.isfinite(zw) & (zw > 0.0), zw, np.inf)
+        who = np.where(zw < z, -1, who)
+        z = np.minimum(z, zw)
+        return z, who
+
+    def depth(self, cam2base):
+        """z-depth image (metres, fp32); 0 where nothing is hit."""
+        z, _ = self._hit(cam2base)
+        return np.where(np.isfinite(z), z, 0.0).astype(np.float32)
+
+    def ids(self, cam2base):
+        """Index of the object seen at each pixel, int32 [h, w]; -1 for the wall or nothing."""
+        return self._hit(cam2base)[1].astype(np.int32)
