@@ -1,6 +1,6 @@
 // asan_host.cpp -- the product's HOST-side arithmetic (no device code) compiled for the CPU sanitizer run:
 // semantic_slam_amd/csrc/pose_math.h (4x4 multiply / cofactor inverse, ref: src/tsdf.cu:253-403) and
-// semantic_slam_amd/csrc/host_derive.h (wavefront brick choice, guards and margins of the exact shortcuts) and
+// semantic_slam_amd/csrc/host_derive.h (wavefront brick choice, guards and margins of the exact shortcuts, launch policy) and
 // semantic_slam_amd/csrc/host_copy.h (the caller's frame into the pinned ring: streaming stores), behind plain C entry points, linked with tsdf_oracle.c into oracle/_asan/liboracle_asan.so by `make -C oracle asan`
 // (-fsanitize=address,undefined -fno-sanitize-recover=all).  tests/test_sanitizers.py runs the golden vectors, the pose
 // known-answer tests, the writers and these entry points under it.  TEST INFRASTRUCTURE: the headers are
@@ -34,5 +34,43 @@ void asan_projection_guards(const tsdf_config *c, const float *cam2base, float o
 
 // dst / src: any alignment, any size (the product hands it page-aligned ring slots and whole frames)
 void asan_copy_to_pinned(void *dst, const void *src, size_t n) { tsdf_host::copy_to_pinned(dst, src, n); }
+
+// ---- launch policy; mode: 0 adaptive, 1 never, 2 always (tsdf_host::Classify) ----
+static tsdf_host::Classify mode_of(int mode) { return static_cast<tsdf_host::Classify>(mode); }
+
+// out: fuses, scalar, classify mode; returns 1 for a shipped variant, else 0
+int asan_decode_variant(int variant, int32_t out[3])
+{
+    const tsdf_host::Variant v = tsdf_host::decode_variant(variant);
+    out[0] = v.fuses; out[1] = v.scalar; out[2] = static_cast<int32_t>(v.classify);
+    return v.known ? 1 : 0;
+}
+
+int asan_tile_levels(int n) { return tsdf_host::tile_levels(n); }
+int asan_tiles_fit(int tiles_w, int tiles_h) { return tsdf_host::tiles_fit(tiles_w, tiles_h) ? 1 : 0; }
+int asan_tile_edge(const tsdf_config *c, int batch_member) { return tsdf_host::tile_edge(*c, batch_member != 0); }
+int asan_fine_tables(const tsdf_config *c, int tile) { return tsdf_host::fine_tables(*c, tile) ? 1 : 0; }
+size_t asan_launch_table_bytes(const tsdf_config *c, int tile, int fine) { return tsdf_host::launch_table_bytes(*c, tile, fine != 0); }
+int asan_pipelines(const tsdf_config *c) { return tsdf_host::pipelines(*c) ? 1 : 0; }
+int asan_classify_one_frame(int mode, int64_t launch_voxels) { return tsdf_host::classify_one_frame(mode_of(mode), launch_voxels) ? 1 : 0; }
+
+int asan_classify_fused(int mode, int claims_known, double claim_fraction, int launches_unclassified)
+{
+    return tsdf_host::classify_fused(mode_of(mode), claims_known != 0, claim_fraction, launches_unclassified) ? 1 : 0;
+}
+
+// out: cache_lo, cache_hi
+void asan_sweep_window(int nz, int dim_x, int dim_y, int64_t window_bytes, int reverse, int32_t out[2])
+{
+    const tsdf_host::SweepWindow w = tsdf_host::sweep_window(nz, dim_x, dim_y, window_bytes, reverse != 0);
+    out[0] = w.cache_lo; out[1] = w.cache_hi;
+}
+
+int asan_batch_defers(int members, int64_t total_voxels) { return tsdf_host::batch_defers(members, total_voxels) ? 1 : 0; }
+int asan_batch_classifies(int mode, int members, int64_t launch_voxels)
+{
+    return tsdf_host::batch_classifies(mode_of(mode), members, launch_voxels) ? 1 : 0;
+}
+int asan_batch_lanes(int members) { return tsdf_host::batch_lanes(members); }
 
 }  // extern "C"

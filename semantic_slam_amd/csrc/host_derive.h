@@ -2,9 +2,11 @@
 // edge and the guards / margins that make the kernels' shortcuts exact ("Why each shortcut is exact").
 // Plain C++ (no HIP, no device types): tsdf_capi.hip includes it for the product, and the CPU sanitizer run compiles it by
 // itself with -fsanitize=address,undefined (tests/test_sanitizers.py).
+// Also the launch policy: what a kernel variant means, tile tables, pipelining, classification, the sweep's cache window, batches.
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 
 #include "tsdf_hip.h"
@@ -122,5 +124,160 @@ inline ProjectionGuards derive_projection_guards(const tsdf_config &c, const flo
     g.px_margin_v = (float)(0.5625 + 3.2e-5 * (std::fabs(fy) + 4.0 * (c.im_height + std::fabs(cy))));
     return g;
 }
+
+// ---- launch policy ------------------------------------------------------------------------------------------------
+// Constants of the kernels (tsdf_multiframe.hip.h), restated; tsdf_capi.hip checks that they agree.
+constexpr int kMaxFramesPerLaunch = 32;
+constexpr int kTileLdsEntries = 5120;
+constexpr int kFineTile = 4;
+constexpr int kFineLevels = 3;
+
+// Kernel variants (tsdf_set_kernel_variant) of the library as shipped:
+//   0   default: one call = one launch of integrate_tile<2> (rows of a multiple of 256 voxels), of the flat kernel (other
+//       rows of a multiple of 4 voxels) or of the scalar kernel (any other row); collected frames and frame sequences
+//       (tsdf_integrate_frames_device, ..._sequence_timed) are applied up to kMaxFramesPerLaunch (32) per pass over the
+//       volume -- over the brick work list when the depth tile tables earn their keep (decided per launch from the previous
+//       launch's claims), else by the per-voxel fused kernel
+//   3   as 0 but one launch per frame even for sequences
+//   7   as 0 but never classified (the per-voxel fused kernel alone)
+//   8   as 0 but always classified
+//   1   the scalar kernel (any dim_x)
+// Every other number belongs to the measurement build (-DTSDF_EXPERIMENTS: tsdf_experiments.hip.h, `make experiments`), which
+// decodes its own (tsdf_experiments_host.hip.h, experiment_variant).
+enum class Classify { Adaptive, Never, Always };
+
+struct Variant {
+    bool known = false;    // false: not a variant of this build
+    bool fuses = false;    // collected frames and sequences go through the fused kernels (rows of a multiple of 4 voxels)
+    bool scalar = false;   // one-frame launches run the scalar kernel whatever the row length
+    Classify classify = Classify::Adaptive;
+};
+
+inline Variant decode_variant(int variant)
+{
+    switch (variant) {
+        case 0: return {true, true, false, Classify::Adaptive};
+        case 1: return {true, false, true, Classify::Adaptive};
+        case 3: return {true, false, false, Classify::Adaptive};
+        case 7: return {true, true, false, Classify::Never};
+        case 8: return {true, true, false, Classify::Always};
+        default: return {};
+    }
+}
+
+inline int64_t slab_voxels(const tsdf_config &c) { return (int64_t)c.dim_x * c.dim_y * (int64_t)(c.z_end - c.z_begin); }
+
+// Depth tile tables (tsdf_multiframe.hip.h): a sparse table of tile_levels(tw) x tile_levels(th) levels per frame, built
+// only for frames of at most kMaxTableTiles tiles (larger frames are not classified).
+inline int tile_levels(int n) { int l = 0; while (n > 0) { ++l; n >>= 1; } return l; }
+
+inline size_t tile_table_elems(int tiles_w, int tiles_h)
+{
+    return (size_t)tile_levels(tiles_w) * tile_levels(tiles_h) * tiles_w * tiles_h;
+}
+
+constexpr int64_t kMaxTableTiles = 16384;
+inline bool tiles_fit(int tiles_w, int tiles_h) { return (int64_t)tiles_w * tiles_h <= kMaxTableTiles; }
+
+// Pixels per depth tile edge for a slab: 8 where a fused launch is long enough to repay tables four times as large (the finer
+// tiles leave a fifth fewer wavefront-frames to the per-voxel path: tsdf_multiframe.hip.h), 16 otherwise and wherever the finer
+// grid of tiles would not fit the table kernels.  Measured on S-surf, ms per frame with 16 / 8: 128^3 0.0044 / 0.0051 (before
+// the table kernel ran 1024 threads), 200^3 0.00586 / 0.00586, 224^3 0.00642 / 0.00633, 256^3 0.00764 / 0.00741, 288^3 0.0097 /
+// 0.0093, 320^3 0.0114 / 0.0106, 512^3 0.0312 / 0.0270: the finer tiles pay from about 10 M voxels.  Members of a batch share one
+// table layout and keep 16.
+constexpr int64_t kFineTileMinVoxels = 10000000;
+inline int tile_edge(const tsdf_config &c, bool batch_member)
+{
+    const int64_t fine_tiles = (int64_t)((c.im_width + 7) / 8) * ((c.im_height + 7) / 8);
+    return (!batch_member && slab_voxels(c) >= kFineTileMinVoxels && fine_tiles <= kTileLdsEntries) ? 8 : 16;
+}
+
+// Fine (4-pixel) tiles beside the 8-pixel tables: where a fused launch is long enough to repay two more small table kernels and
+// 1.4 MB more table per frame (tsdf_multiframe.hip.h, fine_tile_levels).
+constexpr int64_t kFineLevelMinVoxels = 64000000;      // measured: 512^3 S-surf 0.0255 -> 0.0240 ms per frame, 320^3 0.0102 -> 0.0105
+inline bool fine_tables(const tsdf_config &c, int tile) { return tile == 8 && slab_voxels(c) >= kFineLevelMinVoxels; }
+
+// Bytes of a launch's table slot in the frame store: kMaxFramesPerLaunch coarse sparse tables, then (fine) as many fine ones;
+// 0 when the frame's tiles do not fit the tables.
+inline size_t launch_table_bytes(const tsdf_config &c, int tile, bool fine)
+{
+    const int tw = (c.im_width + tile - 1) / tile, th = (c.im_height + tile - 1) / tile;
+    const int fw = (c.im_width + kFineTile - 1) / kFineTile, fh = (c.im_height + kFineTile - 1) / kFineTile;
+    const size_t fine_elems = fine ? (size_t)kFineLevels * kFineLevels * fw * fh : 0;
+    return tiles_fit(tw, th) ? kMaxFramesPerLaunch * (tile_table_elems(tw, th) + fine_elems) * (2 * sizeof(float)) : 0;
+}
+
+// Pipelining pays where a launch is short enough for its small pre-pass kernels to matter and the chip is not full: measured,
+// same box, sequence path, pre-pass on the handle's stream / beside the previous launch: S-surf 200^3 0.00578 -> 0.00546 ms per
+// frame, 320^3 0.01043 -> 0.01037, 512^3 0.02396 -> 0.02403 (the Integrate kernel runs 76 us longer beside a pre-pass that takes
+// 84 us alone: its latency-bound wavefronts hold slots the Integrate kernel's would use), fr3 trajectory 1024^3 0.1460 -> 0.1458.
+// So: slabs below 64 M voxels; larger ones keep one list (the second would be 134 MB at 1024^3) and one stream.
+constexpr int64_t kPipelineMaxVoxels = 64000000;
+inline bool pipelines(const tsdf_config &c) { return slab_voxels(c) < kPipelineMaxVoxels; }
+
+// One-frame masked launches are classified per workgroup when the launch is large enough to repay the three small
+// dependent dispatches ahead of it (tile summary, sparse table, class table: ~25 us on the stream).  Measured
+// (tools/batch_time.py, instance masks over 12 % of the image): 16 x 200^3 batched 0.275 -> 0.157 ms per frame (wavefront
+// bricks; 0.201 with 1024-voxel workgroup patches), one 400^3 volume 0.095 -> 0.075; but 4 x 200^3 batched 0.083 -> 0.079
+// at best and one 200^3 volume 0.016 -> 0.026.
+// Variant 8 classifies regardless (tests), 7 never.
+constexpr int64_t kClassifyMinVoxels = 48000000;
+inline bool classify_one_frame(Classify mode, int64_t launch_voxels)
+{
+    if (mode == Classify::Never) return false;
+    return mode == Classify::Always || launch_voxels >= kClassifyMinVoxels;
+}
+
+// Fused launches (adaptive): the first launch classifies, every classifying launch counts its claims, and a launch whose
+// predecessor claimed less than a tenth of its wavefront-frames goes without (the tables and the pre-pass cost more than
+// that saves), with a new probe every eighth launch.
+constexpr double kMinClaimFraction = 0.10;
+constexpr int kProbeEvery = 8;
+inline bool classify_fused(Classify mode, bool claims_known, double claim_fraction, int launches_unclassified)
+{
+    if (mode != Classify::Adaptive) return mode == Classify::Always;
+    return !claims_known || claim_fraction >= kMinClaimFraction || launches_unclassified >= kProbeEvery - 1;
+}
+
+// Infinity Cache window of the one-frame kernel (integrate_tile, IntegrateParams::cache_lo/hi): successive launches sweep z
+// in alternate directions and the last slices of each sweep, up to kWindowBytes of TSDF + weight state, are loaded and
+// stored with the default cache policy (the rest streams non-temporal), so the next launch starts on lines still in the
+// 256 MiB Infinity Cache.  Chosen by measurement (tools/window_sweep.py, profiles/r05_window_sweep.txt), S-band 512^3,
+// ms per frame with a window of 0 / 128 / 256 / 384 / 512 / 768 / 1024 MiB: 0.3317 / 0.3242 / 0.3205 / 0.3177 / 0.3161 /
+// 0.3182 / 0.3230 (forward sweeps, no window: 0.3319); loading the slices before the window with the default policy too
+// was slower (0.3232 at 64-192 MiB).  A slab whose state fits the window is swept cacheable throughout.
+constexpr int64_t kWindowBytes = 512ll << 20;
+
+struct SweepWindow { int cache_lo, cache_hi; };   // slices [cache_lo, cache_hi) of the slab, in memory order
+
+inline SweepWindow sweep_window(int nz, int dim_x, int dim_y, int64_t window_bytes, bool reverse)
+{
+    const int64_t slice_bytes = 8 * (int64_t)dim_x * dim_y;
+    const int w = (int)std::min<int64_t>(nz, window_bytes / slice_bytes);
+    return reverse ? SweepWindow{0, w} : SweepWindow{nz - w, nz};
+}
+
+// Deferral of a batch (tsdf_batch_integrate_device): collect the frame and apply 32 at a time with one fused launch per
+// member -- the volumes then move once per 32 frames, but every member costs a launch with its own tile tables per flush, so
+// many small members stay with the one batched launch per frame.  Fitted to tools/batch_time.py (instance masks, ms per frame,
+// batched -> deferred): 1 x 200^3 0.035 -> 0.013, 4 x 200^3 0.082 -> 0.031, 16 x 200^3 0.145 -> 0.100, 2 x 400^3 0.122 -> 0.046,
+// 8 x 128^3 0.059 -> 0.047; but 16 x 64^3 0.035 -> 0.070, 64 x 100^3 0.229 -> 0.307: deferred costs about 4 us per member +
+// 0.8 us per M voxels, batched 20 us + 2.8.
+inline bool batch_defers(int members, int64_t total_voxels) { return 2 * (int64_t)members < 10 + total_voxels / 1000000; }
+
+// A batched launch with instance masks is classified as a one-frame launch is (classify_one_frame), and not for many small
+// volumes: one tile table per object has to be built per frame (64 x 100^3: 0.231 -> 0.262 ms).
+constexpr int64_t kBatchMinVoxelsPerMember = 2000000;
+inline bool batch_classifies(Classify mode, int members, int64_t launch_voxels)
+{
+    const bool big_enough = mode == Classify::Always || launch_voxels >= (int64_t)members * kBatchMinVoxelsPerMember;
+    return big_enough && classify_one_frame(mode, launch_voxels);
+}
+
+// Streams a batch's flush spreads its members' launches over (measured, 200^3 members with instance masks, ms per frame, one
+// stream -> four: 16 members 0.081 -> 0.062, 8 members 0.047 -> 0.045, 4 members 0.027 -> 0.034, 2 members 0.016 -> 0.023: few
+// members fill the GPU one after the other)
+constexpr int kBatchSideStreams = 4;
+inline int batch_lanes(int members) { return members < 8 ? 1 : kBatchSideStreams; }
 
 }  // namespace tsdf_host

@@ -155,8 +155,8 @@ struct tsdf_volume {
     int chunks_per_slice = 0;  // ceil(dim_x*dim_y / 256)
     bool flat = false;         // dim_x % 256 != 0: summary-maintaining launches use the flat mapping
     int brick_q = 0, brick_r = 0, brick_s = 0;   // wavefront brick of the classified launches (choose_brick / tsdf_set_brick_shape); q = 0: none
-    int tile = 0;                    // pixels per edge of the depth tiles of this handle's classified launches (tile_edge_for)
-    bool fine_tables = false;        // ... and, beside them, 4-pixel tiles for brick-sized boxes (fine_tables_for)
+    int tile = 0;                    // pixels per edge of the depth tiles of this handle's classified launches (tsdf_host::tile_edge)
+    bool fine_tables = false;        // ... and, beside them, 4-pixel tiles for brick-sized boxes (tsdf_host::fine_tables)
     bool flags_known_zero = false;
 #ifdef TSDF_EXPERIMENTS
     DevPtr<unsigned int> d_super;    // per super-brick frame words of the current fused brick launch (classify_superbricks)
@@ -181,12 +181,7 @@ struct tsdf_volume {
     Event pre_done[2], list_free[2], seq_ready;
     int list_parity = 0;
     bool list_used[2] = {false, false};
-    // Pipelining pays where a launch is short enough for its small pre-pass kernels to matter and the chip is not full: measured,
-    // same box, sequence path, pre-pass on the handle's stream / beside the previous launch: S-surf 200^3 0.00578 -> 0.00546 ms per
-    // frame, 320^3 0.01043 -> 0.01037, 512^3 0.02396 -> 0.02403 (the Integrate kernel runs 76 us longer beside a pre-pass that takes
-    // 84 us alone: its latency-bound wavefronts hold slots the Integrate kernel's would use), fr3 trajectory 1024^3 0.1460 -> 0.1458.
-    // So: slabs below 64 M voxels; larger ones keep one list (the second would be 134 MB at 1024^3) and one stream.
-    bool pipeline_ok = false;
+    bool pipeline_ok = false;       // sequence calls are pipelined (tsdf_host::pipelines)
     bool claims_pending = false, claims_known = false;
     double claims_total = 0.0;      // workgroup-frames of the launch the pending read-back belongs to
     double claim_fraction = 0.0;    // claimed / total of the last launch that was read back
@@ -207,7 +202,7 @@ struct tsdf_volume {
     HostPtr<tsdfk::TrackState> h_track;
 };
 
-constexpr int kBatchSideStreams = 4;
+using tsdf_host::kBatchSideStreams;
 
 // Many volumes integrated by one launch per frame (include/tsdf_hip.h, tsdf_batch_*).
 struct tsdf_batch {
@@ -422,55 +417,13 @@ void pose_from_params(tsdfk::FramePose &fp, const tsdfk::IntegrateParams &q)
     fp.cz_short = q.cz_short; fp.cz_pad = q.cz_pad;
 }
 
-int tile_levels_host(int n) { int l = 0; while (n > 0) { ++l; n >>= 1; } return l; }
-
-size_t tile_table_elems_host(int tiles_w, int tiles_h)
-{
-    return (size_t)tile_levels_host(tiles_w) * tile_levels_host(tiles_h) * tiles_w * tiles_h;
-}
-
-bool tiles_fit(const tsdfk::IntegrateParams &p) { return (int64_t)p.tiles_w * p.tiles_h <= 16384; }
-
-// Pixels per depth tile edge for a slab: 8 where a fused launch is long enough to repay tables four times as large (the finer
-// tiles leave a fifth fewer wavefront-frames to the per-voxel path: tsdf_multiframe.hip.h), 16 otherwise and wherever the finer
-// grid of tiles would not fit the table kernels.  Measured on S-surf, ms per frame with 16 / 8: 128^3 0.0044 / 0.0051 (before
-// the table kernel ran 1024 threads), 200^3 0.00586 / 0.00586, 224^3 0.00642 / 0.00633, 256^3 0.00764 / 0.00741, 288^3 0.0097 /
-// 0.0093, 320^3 0.0114 / 0.0106, 512^3 0.0312 / 0.0270: the finer tiles pay from about 10 M voxels.  Members of a batch share one
-// table layout and keep 16.
-constexpr int64_t kFineTileMinVoxels = 10000000;
-thread_local bool g_create_for_batch = false;
-int tile_edge_for(const tsdf_config &c)
-{
-    const int64_t n = (int64_t)c.dim_x * c.dim_y * (int64_t)(c.z_end - c.z_begin);
-    const int64_t fine_tiles = (int64_t)((c.im_width + 7) / 8) * ((c.im_height + 7) / 8);
-    return (!g_create_for_batch && n >= kFineTileMinVoxels && fine_tiles <= tsdfk::kTileLdsEntries) ? 8 : 16;
-}
-
-// Fine (4-pixel) tiles beside the 8-pixel tables: where a fused launch is long enough to repay two more small table kernels and
-// 1.4 MB more table per frame (tsdf_multiframe.hip.h, fine_tile_levels).
-constexpr int64_t kFineLevelMinVoxels = 64000000;      // measured: 512^3 S-surf 0.0255 -> 0.0240 ms per frame, 320^3 0.0102 -> 0.0105
-bool fine_tables_for(const tsdf_config &c, int tile)
-{
-    const int64_t n = (int64_t)c.dim_x * c.dim_y * (int64_t)(c.z_end - c.z_begin);
-    bool on = tile == 8 && n >= kFineLevelMinVoxels;
-#ifdef TSDF_EXPERIMENTS
-    if (const char *e = std::getenv("TSDF_FINE_TILES")) on = tile == 8 && std::atoi(e) != 0;     // A/B knob of the measurement build
-#endif
-    return on;
-}
-
-// One-frame masked launches are classified per workgroup when the launch is large enough to repay the three small
-// dependent dispatches ahead of it (tile summary, sparse table, class table: ~25 us on the stream).  Measured
-// (tools/batch_time.py, instance masks over 12 % of the image): 16 x 200^3 batched 0.275 -> 0.157 ms per frame (wavefront
-// bricks; 0.201 with 1024-voxel workgroup patches), one 400^3 volume 0.095 -> 0.075; but 4 x 200^3 batched 0.083 -> 0.079
-// at best and one 200^3 volume 0.016 -> 0.026.
-// Variant 8 classifies regardless (tests), 7 never.
-constexpr int64_t kClassifyMinVoxels = 48000000;
-bool classify_one_frame(const tsdf_volume *v, int64_t launch_voxels)
-{
-    if (v->variant == 7) return false;
-    return v->variant == 8 || (kExperiments && v->variant >= 11 && v->variant <= 13) || launch_voxels >= kClassifyMinVoxels;
-}
+// The launch policy (tile tables, pipelining, classification, sweeps, batches) is host arithmetic in host_derive.h, which
+// restates the kernels' constants it needs.
+static_assert(tsdf_host::kMaxFramesPerLaunch == tsdfk::kMaxFramesPerLaunch, "host_derive.h: kMaxFramesPerLaunch");
+static_assert(tsdf_host::kTileLdsEntries == tsdfk::kTileLdsEntries, "host_derive.h: kTileLdsEntries");
+static_assert(tsdf_host::kFineTile == tsdfk::kFineTile, "host_derive.h: kFineTile");
+static_assert(tsdf_host::kFineLevels == tsdfk::kFineLevels, "host_derive.h: kFineLevels");
+using tsdf_host::tiles_fit;
 
 // Depth tile tables (summary + sparse table, tsdf_multiframe.hip.h) of n images depth[i] x mask[i] into tables[i], queued
 // on `stream`; two small launches per 32 images.
@@ -483,7 +436,7 @@ int build_tile_tables(hipStream_t stream, const tsdf_config &c, const tsdfk::Int
                       const uint8_t *const *masks, int n, float2 *tables, unsigned long long *zero_me = nullptr, float2 *fine = nullptr,
                       bool beside_a_launch = false)
 {
-    const size_t per = tile_table_elems_host(p.tiles_w, p.tiles_h);
+    const size_t per = tsdf_host::tile_table_elems(p.tiles_w, p.tiles_h);
     if (fine != nullptr && (p.tile_inv != 0.125f || n > tsdfk::kMaxFramesPerLaunch))
         return fail(TSDF_ERR_INVALID, "build_tile_tables: fine tables go with 8-pixel tiles, one launch at a time");
     for (int k = 0; k < n; k += tsdfk::kMaxFramesPerLaunch) {
@@ -509,11 +462,11 @@ int build_tile_tables(hipStream_t stream, const tsdf_config &c, const tsdfk::Int
             // (1024 threads when the frame has thousands of tiles: each of the kernel's ~12 barrier-separated passes visits every tile)
             const unsigned threads = (p.tiles_w * p.tiles_h > 2048 && !beside_a_launch) ? 1024 : 256;
             const unsigned fine_blocks = fine ? ((unsigned)(p.fine_w * p.fine_h) + threads - 1) / threads : 0u;   // the fine tables' upper levels ride along
-            hipLaunchKernelGGL(tsdfk::tile_sparse_table, dim3((unsigned)tile_levels_host(p.tiles_w) + fine_blocks, m), dim3(threads), 0, stream, tp.tiles,
+            hipLaunchKernelGGL(tsdfk::tile_sparse_table, dim3((unsigned)tsdf_host::tile_levels(p.tiles_w) + fine_blocks, m), dim3(threads), 0, stream, tp.tiles,
                                p.tiles_w, p.tiles_h, k == 0 ? zero_me : (unsigned long long *)nullptr, fine, p.fine_w, p.fine_h);
         } else {
             if (zero_me && k == 0) HIP_TRY(hipMemsetAsync(zero_me, 0, tsdfk::kCounterBytes, stream));
-            hipLaunchKernelGGL(tsdfk::tile_sparse_table_scan, dim3((unsigned)tile_levels_host(p.tiles_w), m), dim3(256), 0, stream, tp.tiles,
+            hipLaunchKernelGGL(tsdfk::tile_sparse_table_scan, dim3((unsigned)tsdf_host::tile_levels(p.tiles_w), m), dim3(256), 0, stream, tp.tiles,
                                p.tiles_w, p.tiles_h);
             if (fine)
                 hipLaunchKernelGGL(tsdfk::fine_tile_levels, dim3((unsigned)((p.fine_w * p.fine_h + 255) / 256), m), dim3(256), 0, stream, fine, p.fine_w, p.fine_h);
@@ -550,20 +503,6 @@ int launch_masked_bricks(tsdf_volume *v, tsdfk::IntegrateParams &p)
     HIP_TRY(hipGetLastError());
     return tables_end(v);
 }
-
-// Kernel variants (tsdf_set_kernel_variant) of the library as shipped:
-//   0   default: one call = one launch of integrate_tile<2> (rows of a multiple of 256 voxels), of the flat kernel (other
-//       rows of a multiple of 4 voxels) or of the scalar kernel (any other row); collected frames and frame sequences
-//       (tsdf_integrate_frames_device, ..._sequence_timed) are applied up to kMaxFramesPerLaunch (32) per pass over the
-//       volume -- over the brick work list when the depth tile tables earn their keep (decided per launch from the previous
-//       launch's claims), else by the per-voxel fused kernel
-//   3   as 0 but one launch per frame even for sequences
-//   7   as 0 but never classified (the per-voxel fused kernel alone)
-//   8   as 0 but always classified
-//   1   the scalar kernel (any dim_x)
-// Every other number belongs to the measurement build (-DTSDF_EXPERIMENTS: tsdf_experiments.hip.h, `make experiments`).
-
-bool shipped_variant(int variant) { return variant == 0 || variant == 1 || variant == 3 || variant == 7 || variant == 8; }
 
 // Kernels that do not maintain the free-space summary must not leave stale "all ones" flags behind.
 int drop_summary(tsdf_volume *v)
@@ -602,7 +541,7 @@ double claims_read_back(const tsdf_volume *v)
 }
 
 #ifdef TSDF_EXPERIMENTS
-bool experiment_variant(int variant);
+tsdf_host::Variant experiment_variant(int variant);
 void experiment_adjust(const tsdf_volume *v, bool labels, bool *classify, int *z_fastest);
 int launch_integrate_experiment(tsdf_volume *v, const float *depth_dev, const uint8_t *mask_dev, const float *c2b);
 int launch_multi_experiment(tsdf_volume *v, tsdfk::MultiParamsInline &mi, const float *const *depth_dev, const uint8_t *const *masks_dev,
@@ -612,30 +551,32 @@ int launch_single_experiment(tsdf_volume *v, tsdfk::IntegrateParams &common, tsd
                              const float *c2b, bool *handled);
 #endif
 
-// Infinity Cache window of the one-frame kernel (integrate_tile, IntegrateParams::cache_lo/hi): successive launches sweep z
-// in alternate directions and the last slices of each sweep, up to kWindowBytes of TSDF + weight state, are loaded and
-// stored with the default cache policy (the rest streams non-temporal), so the next launch starts on lines still in the
-// 256 MiB Infinity Cache.  Chosen by measurement (tools/window_sweep.py, profiles/r05_window_sweep.txt), S-band 512^3,
-// ms per frame with a window of 0 / 128 / 256 / 384 / 512 / 768 / 1024 MiB: 0.3317 / 0.3242 / 0.3205 / 0.3177 / 0.3161 /
-// 0.3182 / 0.3230 (forward sweeps, no window: 0.3319); loading the slices before the window with the default policy too
-// was slower (0.3232 at 64-192 MiB).  A slab whose state fits the window is swept cacheable throughout.
-constexpr int64_t kWindowBytes = 512ll << 20;
+// What a kernel variant number means (tsdf_host::decode_variant), the measurement build's own numbers first.  A handle holds
+// only numbers its build knows (tsdf_set_kernel_variant).
+tsdf_host::Variant variant_of(int variant)
+{
+#ifdef TSDF_EXPERIMENTS
+    const tsdf_host::Variant e = experiment_variant(variant);
+    if (e.known) return e;
+#endif
+    return tsdf_host::decode_variant(variant);
+}
 
+// Direction and Infinity Cache window of a one-frame sweep (tsdf_host::sweep_window): the handle's launches alternate.
 void set_sweep(tsdf_volume *v, tsdfk::IntegrateParams &p)
 {
-    int64_t window = kWindowBytes;
+    int64_t window = tsdf_host::kWindowBytes;
     bool forward_only = false;
 #ifdef TSDF_EXPERIMENTS
     if (const char *e = std::getenv("TSDF_MALL_WINDOW_MB")) window = (int64_t)std::atoi(e) << 20;    // A/B knobs of the measurement build
     forward_only = std::getenv("TSDF_SWEEP_FORWARD") && std::atoi(std::getenv("TSDF_SWEEP_FORWARD")) != 0;
     p.head_plain_loads = std::getenv("TSDF_HEAD_PLAIN_LOADS") && std::atoi(std::getenv("TSDF_HEAD_PLAIN_LOADS")) != 0;
 #endif
-    const int64_t slice_bytes = 8 * (int64_t)p.dim_x * p.dim_y;
-    const int w = (int)std::min<int64_t>(p.nz, window / slice_bytes);
     p.sweep_reverse = forward_only ? 0 : v->sweep_parity;
     v->sweep_parity ^= 1;
-    p.cache_lo = p.sweep_reverse ? 0 : p.nz - w;
-    p.cache_hi = p.sweep_reverse ? w : p.nz;
+    const tsdf_host::SweepWindow w = tsdf_host::sweep_window(p.nz, p.dim_x, p.dim_y, window, p.sweep_reverse != 0);
+    p.cache_lo = w.cache_lo;
+    p.cache_hi = w.cache_hi;
 }
 
 // Queue one Integrate launch.  Shapes are validated at tsdf_create, so the grid covers exactly
@@ -650,7 +591,8 @@ int launch_integrate(tsdf_volume *v, const float *depth_dev, const uint8_t *mask
 #ifdef TSDF_EXPERIMENTS
     if (c.dim_x % 4 == 0 && (v->variant == 2 || (v->variant >= 16 && !mask_dev))) return launch_integrate_experiment(v, depth_dev, mask_dev, c2b);
 #endif
-    if (c.dim_x % 4 != 0 || v->variant == 1) {
+    const tsdf_host::Variant var = variant_of(v->variant);
+    if (c.dim_x % 4 != 0 || var.scalar) {
         // rows that are not 16-byte aligned (or the scalar kernel asked for): one voxel per lane; it does not keep the summary
         int rc = drop_summary(v);
         if (rc) return rc;
@@ -671,12 +613,13 @@ int launch_integrate(tsdf_volume *v, const float *depth_dev, const uint8_t *mask
     if (mask_dev) {
         // per-object volumes see their instance only, so the bricks the tile table of depth x mask proves untouched are
         // told to leave (variant 7: never; small launches: not worth the three small dispatches ahead of it)
-        if (classify_one_frame(v, v->n_vox) && tiles_fit(p) && p.brick_q > 0 && (!kExperiments || v->variant != 11)) {
+        const bool classify = tsdf_host::classify_one_frame(var.classify, v->n_vox) && tiles_fit(p.tiles_w, p.tiles_h);
+        if (classify && p.brick_q > 0 && (!kExperiments || v->variant != 11)) {
             int rc = launch_masked_bricks(v, p);    // per wavefront brick: skipped by rows, slices and columns
             if (rc) return rc;
         } else {
 #ifdef TSDF_EXPERIMENTS
-            if (v->variant == 11 && classify_one_frame(v, v->n_vox) && tiles_fit(p)) return launch_integrate_experiment(v, depth_dev, mask_dev, c2b);
+            if (v->variant == 11 && classify) return launch_integrate_experiment(v, depth_dev, mask_dev, c2b);
 #endif
             set_sweep(v, p);
             hipLaunchKernelGGL((tsdfk::integrate_tile<2, true>), grid, block, 0, v->stream, p);
@@ -724,7 +667,8 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
             if (rc || handled) return rc;
         }
 #endif
-        if (v->flat && pose.mask != nullptr && classify_one_frame(v, v->n_vox) && tiles_fit(common) && common.brick_q > 0) {
+        if (v->flat && pose.mask != nullptr && tsdf_host::classify_one_frame(variant_of(v->variant).classify, v->n_vox) &&
+            tiles_fit(common.tiles_w, common.tiles_h) && common.brick_q > 0) {
             // one masked frame into a flat-mapped volume (the reference's 200^3 object grids), large enough to repay a class table
             tsdfk::IntegrateParams cp = make_params(v, depth_dev[0], pose.mask, c2b, 4);
             return launch_masked_bricks(v, cp);
@@ -751,11 +695,8 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
     bool any_mask = false;
     for (int f = 0; f < n && masks_dev; ++f) any_mask = any_mask || masks_dev[f] != nullptr;
 
-    // Patch classification: tables of at most 4 MiB per frame.  Variant 8: always; variant 7: never;
-    // default: while it pays -- the first launch classifies, every classifying launch counts its claims, and a launch whose
-    // predecessor claimed less than a tenth of its wavefront-frames goes without (the tables and the pre-pass cost more than
-    // that saves), with a new probe every eighth launch.  The count is read back asynchronously: a decision never waits
-    // for the GPU.
+    // Patch classification: tables of at most 4 MiB per frame, used while they pay
+    // (tsdf_host::classify_fused).  The count is read back asynchronously: a decision never waits for the GPU.
     if (v->claims_pending) {
         const hipError_t qe = hipEventQuery(v->claims_done);
         if (qe == hipSuccess) {
@@ -773,13 +714,13 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
         }
     }
     // classified launches run over wavefront bricks (every grid whose rows are a multiple of 4 voxels has a brick view)
-    bool classify = tiles_fit(mi.common) && v->variant != 7 && mi.common.brick_q > 0;
+    bool classify = tiles_fit(mi.common.tiles_w, mi.common.tiles_h) && mi.common.brick_q > 0;
     mi.z_fastest = 2;
 #ifdef TSDF_EXPERIMENTS
     experiment_adjust(v, label_ims != nullptr, &classify, &mi.z_fastest);
 #endif
-    const bool forced = v->variant == 8 || (kExperiments && v->variant >= 11 && v->variant <= 13);
-    if (classify && !forced) classify = !v->claims_known || v->claim_fraction >= 0.10 || v->launches_unclassified >= 7;
+    classify = classify && tsdf_host::classify_fused(variant_of(v->variant).classify, v->claims_known, v->claim_fraction,
+                                                     v->launches_unclassified);
     v->launches_unclassified = classify ? 0 : v->launches_unclassified + 1;
     const bool count_claims = classify && !v->claims_pending;
     if (classify && !v->d_claims) {
@@ -803,7 +744,7 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
     unsigned long long *const claims_p = classify ? v->d_claims + (size_t)P * (kClaimBlockBytes / sizeof(unsigned long long)) : nullptr;
     bool pipelined = classify && inputs_ready != nullptr && v->pipeline_ok;
 #ifdef TSDF_EXPERIMENTS
-    if (!shipped_variant(v->variant) || std::getenv("TSDF_NO_PIPELINE")) pipelined = false;   // the measurement build's own kernels run on the handle's stream
+    if (!tsdf_host::decode_variant(v->variant).known || std::getenv("TSDF_NO_PIPELINE")) pipelined = false;   // the measurement build's own kernels run on the handle's stream
 #endif
     if (pipelined && !v->pre_stream) {
         // the two side streams of a pipelined handle, at its first pipelined launch (a stream costs about 2 MiB of device memory:
@@ -884,7 +825,7 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
     if (count_claims) mi.common.claim_counter = claims_p + 1;   // bucket 0's claims word (the pre-pass adds the bucket's offset)
     if (classify) {
         // depth tile tables of the n frames (two small launches), then the kernels that consult them
-        const size_t per_frame = tile_table_elems_host(mi.common.tiles_w, mi.common.tiles_h);
+        const size_t per_frame = tsdf_host::tile_table_elems(mi.common.tiles_w, mi.common.tiles_h);
         float2 *tiles = nullptr;
         int rc = tables_begin(v, &tiles, ps);
         if (rc) return unwind(rc);
@@ -988,11 +929,7 @@ int frames_per_launch(const tsdf_volume *)
     return tsdfk::kMaxFramesPerLaunch;
 }
 
-bool can_fuse(const tsdf_volume *v)
-{
-    // (the measurement build's variants 4 .. 13 are flavours of the fused path)
-    return (v->variant == 0 || v->variant == 7 || v->variant == 8 || (kExperiments && v->variant >= 4 && v->variant <= 13)) && v->cfg.dim_x % 4 == 0;
-}
+bool can_fuse(const tsdf_volume *v) { return variant_of(v->variant).fuses && v->cfg.dim_x % 4 == 0; }
 
 // A sequence of frames: fused frames_per_launch() at a time when the default kernel is selected.
 int integrate_frames(tsdf_volume *v, const float *const *depth_dev, const uint8_t *const *masks_dev,
@@ -1317,9 +1254,9 @@ int tsdf_config_default(tsdf_config *cfg, int32_t im_height, int32_t im_width)
     return TSDF_OK;
 }
 
-int tsdf_create(const tsdf_config *cfg, tsdf_volume **out)
+// tsdf_create, and tsdf_batch_create for its members (batch_member: one table layout for all of them, tsdf_host::tile_edge)
+static int create_volume(const tsdf_config *cfg, bool batch_member, tsdf_volume **out)
 {
-    if (!cfg || !out) return fail(TSDF_ERR_INVALID, "tsdf_create: NULL argument");
     *out = nullptr;
     if (cfg->dim_x <= 0 || cfg->dim_y <= 0 || cfg->dim_z <= 0)
         return fail(TSDF_ERR_INVALID, "tsdf_create: grid dims must be positive (%d,%d,%d)",
@@ -1371,28 +1308,30 @@ int tsdf_create(const tsdf_config *cfg, tsdf_volume **out)
         return cleanup(fail(TSDF_ERR_HIP, "tsdf_create: hipMalloc of the summary: %s", hipGetErrorString(e)));
     // staging, deferral and tile-table memory: the store shared by every handle of this device and image size (nothing is
     // allocated until a frame arrives)
-    v->tile = tile_edge_for(*cfg);
-    v->fine_tables = fine_tables_for(*cfg, v->tile);
-    v->pipeline_ok = (int64_t)cfg->dim_x * cfg->dim_y * (int64_t)(cfg->z_end - cfg->z_begin) < kFineLevelMinVoxels;
+    v->tile = tsdf_host::tile_edge(*cfg, batch_member);
+    v->fine_tables = tsdf_host::fine_tables(*cfg, v->tile);
+    v->pipeline_ok = tsdf_host::pipelines(*cfg);
 #ifdef TSDF_EXPERIMENTS
-    if (const char *e = std::getenv("TSDF_PIPELINE")) v->pipeline_ok = std::atoi(e) != 0;     // A/B knob of the measurement build
+    // A/B knobs of the measurement build
+    if (const char *e = std::getenv("TSDF_FINE_TILES")) v->fine_tables = v->tile == 8 && std::atoi(e) != 0;
+    if (const char *e = std::getenv("TSDF_PIPELINE")) v->pipeline_ok = std::atoi(e) != 0;
 #endif
-    {
-        const int tw = (cfg->im_width + v->tile - 1) / v->tile, th = (cfg->im_height + v->tile - 1) / v->tile;
-        const int fw = (cfg->im_width + tsdfk::kFineTile - 1) / tsdfk::kFineTile, fh = (cfg->im_height + tsdfk::kFineTile - 1) / tsdfk::kFineTile;
-        // a launch's tables: kMaxFramesPerLaunch coarse sparse tables, then (fine_tables) as many fine ones
-        const size_t table_bytes = (int64_t)tw * th <= 16384
-            ? tsdfk::kMaxFramesPerLaunch * (tile_table_elems_host(tw, th) + (v->fine_tables ? tsdfk::fine_table_elems(fw, fh) : 0)) * sizeof(float2) : 0;
-        if ((e = tsdf_store::store_ref(cfg->device, (size_t)cfg->im_height * cfg->im_width, table_bytes, &v->store)) != hipSuccess ||
-            (e = event_create(v->flush_done[0])) != hipSuccess ||
-            (e = event_create(v->flush_done[1])) != hipSuccess ||
-            (e = event_create(v->pend_copied)) != hipSuccess)
-            return cleanup(fail(TSDF_ERR_HIP, "tsdf_create: frame store: %s", hipGetErrorString(e)));
-        v->copy_stream = v->store->copy_stream;   // the store's: shared by its handles (thread-safe; copies share one PCIe pipe anyway)
-    }
+    const size_t table_bytes = tsdf_host::launch_table_bytes(*cfg, v->tile, v->fine_tables);
+    if ((e = tsdf_store::store_ref(cfg->device, (size_t)cfg->im_height * cfg->im_width, table_bytes, &v->store)) != hipSuccess ||
+        (e = event_create(v->flush_done[0])) != hipSuccess ||
+        (e = event_create(v->flush_done[1])) != hipSuccess ||
+        (e = event_create(v->pend_copied)) != hipSuccess)
+        return cleanup(fail(TSDF_ERR_HIP, "tsdf_create: frame store: %s", hipGetErrorString(e)));
+    v->copy_stream = v->store->copy_stream;   // the store's: shared by its handles (thread-safe; copies share one PCIe pipe anyway)
     if ((rc = fill(v)) != TSDF_OK) return cleanup(rc);
     *out = v;
     return TSDF_OK;
+}
+
+int tsdf_create(const tsdf_config *cfg, tsdf_volume **out)
+{
+    if (!cfg || !out) return fail(TSDF_ERR_INVALID, "tsdf_create: NULL argument");
+    return create_volume(cfg, false, out);
 }
 
 int tsdf_destroy(tsdf_volume *v)
@@ -1773,11 +1712,7 @@ int tsdf_get_stream(tsdf_volume *v, void **hip_stream)
 int tsdf_set_kernel_variant(tsdf_volume *v, int32_t variant)
 {
     if (!v) return fail(TSDF_ERR_INVALID, "tsdf_set_kernel_variant: NULL handle");
-    bool ok = shipped_variant(variant);
-#ifdef TSDF_EXPERIMENTS
-    ok = ok || experiment_variant(variant);
-#endif
-    if (!ok)
+    if (!variant_of(variant).known)
         return fail(TSDF_ERR_INVALID, "tsdf_set_kernel_variant: unknown variant %d (this build knows 0, 1, 3, 7, 8%s)", variant,
                     kExperiments ? " and the experiments" : "; the others live in the -DTSDF_EXPERIMENTS build");
     v->variant = variant;
@@ -1907,10 +1842,10 @@ int tsdf_selftest_tile_tables(int32_t device, const float *depth_dev, const uint
         return fail(TSDF_ERR_INVALID, "tsdf_selftest_tile_tables: bad argument");
     HIP_TRY(hipSetDevice(device));
     uint64_t bad = 0;
-    for (const int tile : {16, 8}) {      // both tile sizes the library uses (tile_edge_for)
+    for (const int tile : {16, 8}) {      // both tile sizes the library uses (tsdf_host::tile_edge)
         const int tw = (im_width + tile - 1) / tile, th = (im_height + tile - 1) / tile;
-        if ((int64_t)tw * th > 16384) continue;
-        const size_t per = tile_table_elems_host(tw, th);
+        if (!tiles_fit(tw, th)) continue;
+        const size_t per = tsdf_host::tile_table_elems(tw, th);
         DevPtr<float2> d_a, d_b;
         HIP_TRY(dev_alloc(d_a, per * sizeof(float2)));
         if (dev_alloc(d_b, per * sizeof(float2)) != hipSuccess) return fail(TSDF_ERR_HIP, "tsdf_selftest_tile_tables: hipMalloc");
@@ -1919,7 +1854,7 @@ int tsdf_selftest_tile_tables(int32_t device, const float *depth_dev, const uint
         tsdfk::TileSummaryParams tp;
         for (int f = 0; f < tsdfk::kMaxFramesPerLaunch; ++f) { tp.depth[f] = depth_dev; tp.mask[f] = mask_dev; }
         tp.H = im_height; tp.W = im_width; tp.tiles_w = tw; tp.tiles_h = th; tp.max_depth = max_depth;
-        const unsigned lj = (unsigned)tile_levels_host(tw);
+        const unsigned lj = (unsigned)tsdf_host::tile_levels(tw);
         // a: the kernels the library launches (strips of 64 pixels; doubling in LDS when the frame's tiles fit)
         tp.tiles = d_a;
         if (tile == 16)
@@ -1975,14 +1910,14 @@ int tsdf_selftest_tile_tables(int32_t device, const float *depth_dev, const uint
                 const int tw = (im_width + 7) / 8, th = (im_height + 7) / 8;
                 if ((int64_t)tw * th > tsdfk::kTileLdsEntries) break;
                 DevPtr<float2> d_c;
-                if (dev_alloc(d_c, tile_table_elems_host(tw, th) * sizeof(float2)) != hipSuccess) { e = hipErrorOutOfMemory; break; }
+                if (dev_alloc(d_c, tsdf_host::tile_table_elems(tw, th) * sizeof(float2)) != hipSuccess) { e = hipErrorOutOfMemory; break; }
                 tsdfk::TileSummaryParams tp;
                 for (int f = 0; f < tsdfk::kMaxFramesPerLaunch; ++f) { tp.depth[f] = depth_dev; tp.mask[f] = mask_dev; }
                 tp.H = im_height; tp.W = im_width; tp.tiles_w = tw; tp.tiles_h = th; tp.max_depth = max_depth;
                 tp.tiles = d_c; tp.fine = d_a; tp.fw = fw; tp.fh = fh;
                 hipLaunchKernelGGL(tsdfk::depth_tile_summary<8>, dim3((unsigned)((((tw + 7) / 8) * th + 3) / 4), 1), dim3(64, 4), 0, 0, tp);
                 const unsigned threads = tw * th > 2048 ? 1024 : 256;
-                hipLaunchKernelGGL(tsdfk::tile_sparse_table, dim3((unsigned)tile_levels_host(tw) + ((unsigned)(fw * fh) + threads - 1) / threads, 1), dim3(threads), 0, 0,
+                hipLaunchKernelGGL(tsdfk::tile_sparse_table, dim3((unsigned)tsdf_host::tile_levels(tw) + ((unsigned)(fw * fh) + threads - 1) / threads, 1), dim3(threads), 0, 0,
                                    d_c, tw, th, (unsigned long long *)nullptr, d_a, fw, fh);
                 e = hipGetLastError();
                 if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -2301,9 +2236,7 @@ int batch_flush(tsdf_batch *b)
     int rc = TSDF_OK;
     if (hipSetDevice(b->device) != hipSuccess) rc = fail(TSDF_ERR_HIP, "tsdf_batch: hipSetDevice failed");
     // fork: the side streams start when everything queued on the batch's stream so far (the frames' copies) is done
-    // (measured, 200^3 members with instance masks, ms per frame, one stream -> four: 16 members 0.081 -> 0.062, 8 members
-    // 0.047 -> 0.045, 4 members 0.027 -> 0.034, 2 members 0.016 -> 0.023: few members fill the GPU one after the other)
-    const int lanes = members < 8 ? 1 : kBatchSideStreams;
+    const int lanes = tsdf_host::batch_lanes(members);
     hipError_t e = hipSuccess;
     if (rc == TSDF_OK && lanes > 1) {
         if (!b->collected) {      // all or none
@@ -2425,9 +2358,7 @@ int tsdf_batch_create(const tsdf_config *cfgs, int32_t n, tsdf_batch **out)
     std::vector<int2> map;
     for (int i = 0; i < n; ++i) {
         tsdf_volume *v = nullptr;
-        g_create_for_batch = true;        // one table layout for all members (tile_edge_for)
-        int rc = tsdf_create(&cfgs[i], &v);
-        g_create_for_batch = false;
+        int rc = create_volume(&cfgs[i], true, &v);
         if (rc) return cleanup(rc);
         b->vols.push_back(v);
         const int nz = cfgs[i].z_end - cfgs[i].z_begin;
@@ -2485,17 +2416,12 @@ int tsdf_batch_integrate_device(tsdf_batch *b, const float *depth_dev, const uin
     const int n = (int)b->vols.size();
     for (tsdf_volume *v : b->vols)
         if (v->pend_count > 0) { int rc = flush_pending(v); if (rc) return rc; }   // frames given to a borrowed handle come first
-    // Deferral as for a single handle (tsdf_set_deferral on the FIRST member switches it): collect the frame and apply 32 at
-    // a time with one fused launch per member -- the volumes then move once per 32 frames, but every member costs a launch
-    // with its own tile tables per flush, so many small members stay with the one batched launch per frame.  Fitted to
-    // tools/batch_time.py (instance masks, ms per frame, batched -> deferred): 1 x 200^3 0.035 -> 0.013, 4 x 200^3 0.082
-    // -> 0.031, 16 x 200^3 0.145 -> 0.100, 2 x 400^3 0.122 -> 0.046, 8 x 128^3 0.059 -> 0.047; but 16 x 64^3 0.035 ->
-    // 0.070, 64 x 100^3 0.229 -> 0.307: deferred costs about 4 us per member + 0.8 us per M voxels, batched 20 us + 2.8.
+    // Deferral as for a single handle (tsdf_set_deferral on the FIRST member switches it), where it pays (tsdf_host::batch_defers)
     {
         bool defer = b->vols[0]->defer_n > 1;
         int64_t total = 0;
         for (tsdf_volume *v : b->vols) { defer = defer && can_fuse(v); total += v->n_vox; }
-        defer = defer && 2 * (int64_t)n < 10 + total / 1000000;
+        defer = defer && tsdf_host::batch_defers(n, total);
         if (defer) return batch_collect(b, depth_dev, masks_dev, cam2world);
         int rc = batch_flush(b);   // the policy changed between calls (tsdf_set_deferral, a kernel variant)
         if (rc) return rc;
@@ -2522,12 +2448,11 @@ int tsdf_batch_integrate_device(tsdf_batch *b, const float *depth_dev, const uin
     for (int i = 1; i < n; ++i) same_range = same_range && b->vols[i]->cfg.max_depth == b->vols[0]->cfg.max_depth;
     int64_t launch_voxels = 0;
     for (tsdf_volume *v : b->vols) launch_voxels += v->n_vox;
-    // ... and not for many small volumes: one tile table per object has to be built per frame (64 x 100^3: 0.231 -> 0.262 ms)
-    const bool big_enough = b->vols[0]->variant == 8 || (kExperiments && b->vols[0]->variant >= 11 && b->vols[0]->variant <= 13) || launch_voxels >= (int64_t)n * 2000000;
-    const bool classify = any_mask && same_range && big_enough && classify_one_frame(b->vols[0], launch_voxels) &&
-                          tiles_fit(b->h_params[s][0]);
+    // ... when the launch is large enough, and not for many small volumes (tsdf_host::batch_classifies)
+    const bool classify = any_mask && same_range && tsdf_host::batch_classifies(variant_of(b->vols[0]->variant).classify, n, launch_voxels) &&
+                          tiles_fit(b->h_params[s][0].tiles_w, b->h_params[s][0].tiles_h);
     if (classify) {
-        const size_t per = tile_table_elems_host(b->h_params[s][0].tiles_w, b->h_params[s][0].tiles_h);
+        const size_t per = tsdf_host::tile_table_elems(b->h_params[s][0].tiles_w, b->h_params[s][0].tiles_h);
         if (!b->d_tiles) {      // (and, in the measurement build, the class table beside them: both or neither)
             DevPtr<float2> tiles;
             DevPtr<uint8_t> wg_class;

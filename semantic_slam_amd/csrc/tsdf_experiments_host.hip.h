@@ -21,11 +21,17 @@
 //   112 + c  as 80 + c with the depth pixels of each workgroup's patch staged in LDS (c = 3, 7: R = 1, 2)
 #pragma once
 
-bool experiment_variant(int variant)
+// What the numbers of this build mean (the shipped ones, tsdf_host::decode_variant, are not decoded here): 2 and the ladder
+// are one-frame kernels, 4 .. 6, 9, 10 flavours of the fused path and 11 .. 13 fused and always classified.
+tsdf_host::Variant experiment_variant(int variant)
 {
+    using tsdf_host::Classify;
     const int c = (variant - 32) & 15;
     const bool sum_ok = (variant >= 32 && variant < 112 && c < 12 && ((c >> 1) & 1)) || variant == 115 || variant == 119;
-    return (variant >= 0 && variant <= 13) || (variant >= 16 && variant < 28) || sum_ok;
+    if (variant == 2 || (variant >= 16 && variant < 28) || sum_ok) return {true, false, false, Classify::Adaptive};
+    if ((variant >= 4 && variant <= 6) || variant == 9 || variant == 10) return {true, true, false, Classify::Adaptive};
+    if (variant >= 11 && variant <= 13) return {true, true, false, Classify::Always};
+    return {};
 }
 
 void experiment_adjust(const tsdf_volume *v, bool labels, bool *classify, int *z_fastest)
@@ -150,7 +156,9 @@ int launch_single_experiment(tsdf_volume *v, tsdfk::IntegrateParams &common, tsd
                              const float *c2b, bool *handled)
 {
     *handled = false;
-    if (!(v->variant == 11 && v->flat && pose.mask != nullptr && classify_one_frame(v, v->n_vox) && tiles_fit(common))) return TSDF_OK;
+    if (!(v->variant == 11 && v->flat && pose.mask != nullptr && tsdf_host::classify_one_frame(variant_of(v->variant).classify, v->n_vox) &&
+          tiles_fit(common.tiles_w, common.tiles_h)))
+        return TSDF_OK;
     const int nz = v->cfg.z_end - v->cfg.z_begin;
     dim3 block(64, 4, 1), grid((v->chunks_per_slice + 3) / 4, 1, nz);
     tsdfk::IntegrateParams cp = make_params(v, depth_dev, pose.mask, c2b, 4);

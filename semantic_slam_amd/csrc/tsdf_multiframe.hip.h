@@ -42,7 +42,7 @@ struct FramePose {
 };
 
 // ---- depth tile summaries ---------------------------------------------------------------------------------
-// Per tile of a depth frame (16 x 16 pixels, or 8 x 8: the host chooses per slab, see tile_edge_for): x = the smallest depth
+// Per tile of a depth frame (16 x 16 pixels, or 8 x 8: the host chooses per slab, see tsdf_host::tile_edge): x = the smallest depth
 // if EVERY pixel of the tile passes the reference's depth-range test (0 < d <= max_depth, ref: src/tsdf.cu:46), else -inf;
 // y = the largest depth among the pixels that pass it, -inf if none does.  A NaN anywhere in the tile (NaN passes the
 // reference's tests and updates the voxel) makes the tile claim nothing: (-inf, +inf).

@@ -138,6 +138,79 @@ def main():
             if not np.all(np.isfinite(pose)):
                 ok(g[1] == 0.0 and g[0] >= 3.0e38 and g[3] >= 3.0e38, "a pose that is not finite must switch every shortcut off")
 
+    # ---- launch policy (csrc/host_derive.h): each threshold on both sides and known answers of the rules it replaced ----------
+    ADAPTIVE, NEVER, ALWAYS = 0, 1, 2
+    cp = C.POINTER(Cfg)
+    for name, args, res in (("asan_decode_variant", [C.c_int, C.POINTER(C.c_int32 * 3)], C.c_int), ("asan_tile_levels", [C.c_int], C.c_int),
+                            ("asan_tiles_fit", [C.c_int, C.c_int], C.c_int), ("asan_tile_edge", [cp, C.c_int], C.c_int),
+                            ("asan_fine_tables", [cp, C.c_int], C.c_int), ("asan_launch_table_bytes", [cp, C.c_int, C.c_int], C.c_size_t),
+                            ("asan_pipelines", [cp], C.c_int), ("asan_classify_one_frame", [C.c_int, C.c_int64], C.c_int),
+                            ("asan_classify_fused", [C.c_int, C.c_int, C.c_double, C.c_int], C.c_int),
+                            ("asan_sweep_window", [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_int32 * 2)], None),
+                            ("asan_batch_defers", [C.c_int, C.c_int64], C.c_int), ("asan_batch_classifies", [C.c_int, C.c_int, C.c_int64], C.c_int),
+                            ("asan_batch_lanes", [C.c_int], C.c_int)):
+        getattr(L, name).argtypes, getattr(L, name).restype = args, res
+
+    def grid(n, im=(480, 640)):
+        return cfg_from({"im": list(im), "dims": [n, n, n], "z": [0, n], "voxel_size": 2.56 / n, "trunc": 0.05, "max_depth": 6.0,
+                         "origin": [-1.28, -1.28, 1.0], "K": [535.4, 0, 320.1, 0, 539.2, 247.6, 0, 0, 1]})
+
+    # what a kernel variant means: fuses, scalar, classification mode; the shipped decoder knows 0, 1, 3, 7, 8 only
+    for variant, want in ((0, [1, 0, ADAPTIVE]), (1, [0, 1, ADAPTIVE]), (3, [0, 0, ADAPTIVE]), (7, [1, 0, NEVER]), (8, [1, 0, ALWAYS])):
+        out = (C.c_int32 * 3)()
+        ok(L.asan_decode_variant(variant, C.byref(out)) == 1 and list(out) == want, (variant, list(out)))
+    for variant in (2, 4, 5, 6, 9, 10, 11, 12, 13, 16, 119, -1, 1 << 30):
+        ok(L.asan_decode_variant(variant, C.byref((C.c_int32 * 3)())) == 0, variant)
+    # tile tables: levels = bit length, at most 16384 tiles
+    ok(all(L.asan_tile_levels(n) == n.bit_length() for n in list(range(0, 300)) + [4095, 4096, 16384, 65535, 1 << 30]))
+    ok(L.asan_tiles_fit(128, 128) == 1 and L.asan_tiles_fit(129, 128) == 0 and L.asan_tiles_fit(16384, 1) == 1 and L.asan_tiles_fit(16385, 1) == 0)
+    # tile edge (10 M voxels; 8-pixel tiles within the table kernel's LDS; batch members 16), fine tables (64 M, 8-pixel tiles
+    # only), pipelining (below 64 M voxels)
+    for cfg, member, edge, fine, piped in ((grid(200), 0, 16, 0, 1), (grid(224), 0, 8, 0, 1), (grid(399), 0, 8, 0, 1), (grid(400), 0, 8, 1, 0),
+                                          (grid(512), 0, 8, 1, 0), (grid(512), 1, 16, 0, 0), (grid(512, (960, 1280)), 0, 16, 0, 0)):
+        got = (L.asan_tile_edge(C.byref(cfg), member), L.asan_fine_tables(C.byref(cfg), edge), L.asan_pipelines(C.byref(cfg)))
+        ok(got == (edge, fine, piped), (cfg.dim_x, member, cfg.im_width, got))
+    c10 = grid(200)
+    c10.dim_z, c10.z_end = 250, 250                                  # 200 x 200 x 250 = 10 M voxels exactly
+    ok(L.asan_tile_edge(C.byref(c10), 0) == 8)
+    c10.z_end = 249
+    ok(L.asan_tile_edge(C.byref(c10), 0) == 16)
+    c64 = grid(400)
+    ok(L.asan_fine_tables(C.byref(c64), 16) == 0)                   # fine tables go with 8-pixel tiles only
+    c64.z_end = 399                                                  # 400 x 400 x 399: one slice short of 64 M voxels
+    ok(L.asan_fine_tables(C.byref(c64), 8) == 0 and L.asan_pipelines(C.byref(c64)) == 1)
+    c5120, c5121 = grid(512, (512, 640)), grid(512, (520, 640))      # 80 x 64 = 5120 8-pixel tiles fit the LDS, 80 x 65 do not
+    ok(L.asan_tile_edge(C.byref(c5120), 0) == 8 and L.asan_tile_edge(C.byref(c5121), 0) == 16)
+    # a launch's table slot: 32 coarse tables (+ 32 fine ones), 0 when the frame's tiles do not fit the tables
+    c = grid(512)
+    ok(L.asan_launch_table_bytes(C.byref(c), 16, 0) == 9216000 and L.asan_launch_table_bytes(C.byref(c), 8, 0) == 51609600)
+    ok(L.asan_launch_table_bytes(C.byref(c), 8, 1) == 95846400)
+    ok(L.asan_launch_table_bytes(C.byref(grid(64, (2048, 2064))), 16, 0) == 0)
+    ok(L.asan_launch_table_bytes(C.byref(grid(64, (2048, 2048))), 16, 0) == 32 * 8 * 8 * 8 * 128 * 128)
+    # one-frame classification: 48 M voxels
+    ok(L.asan_classify_one_frame(ADAPTIVE, 47999999) == 0 and L.asan_classify_one_frame(ADAPTIVE, 48000000) == 1)
+    ok(L.asan_classify_one_frame(NEVER, 1 << 40) == 0 and L.asan_classify_one_frame(ALWAYS, 0) == 1)
+    # fused launches (adaptive): classify until a launch claims less than a tenth, then probe every eighth launch
+    fused_cases = ((0, 0.0, 0, 1), (1, 0.0999, 6, 0), (1, 0.10, 0, 1), (1, 0.0, 7, 1), (1, 0.0, 6, 0), (1, 0.5, 3, 1))
+    for known, frac, idle, want in fused_cases:
+        ok(L.asan_classify_fused(ADAPTIVE, known, frac, idle) == want, (known, frac, idle))
+        ok(L.asan_classify_fused(NEVER, known, frac, idle) == 0 and L.asan_classify_fused(ALWAYS, known, frac, idle) == 1)
+    # the one-frame sweep's cache window: 512 MiB of TSDF + weight slices at the end of the sweep
+    win = (C.c_int32 * 2)()
+    for nz, d, rev, want in ((512, 512, 0, [256, 512]), (512, 512, 1, [0, 256]), (200, 200, 0, [0, 200]), (200, 200, 1, [0, 200]),
+                             (1, 16384, 0, [1, 1]), (1, 16384, 1, [0, 0])):       # a 2 GiB slice: no slice fits the window
+        L.asan_sweep_window(nz, d, d, 512 << 20, rev, C.byref(win))
+        ok(list(win) == want, (nz, d, rev, list(win)))
+    # batches: deferral (deferred 4 us per member + 0.8 per M voxels against batched 20 + 2.8), classification, side streams
+    for members, n, want in ((16, 200, 1), (1, 200, 1), (64, 100, 0), (16, 64, 0)):
+        ok(L.asan_batch_defers(members, members * n ** 3) == want, (members, n))
+    ok(L.asan_batch_defers(10, 11000000) == 1 and L.asan_batch_defers(10, 10999999) == 0)    # 2 x 10 < 10 + 11, not < 10 + 10
+    for members, n, want in ((16, 200, 1), (4, 200, 0), (64, 100, 0)):
+        ok(L.asan_batch_classifies(ADAPTIVE, members, members * n ** 3) == want, (members, n))
+        ok(L.asan_batch_classifies(ALWAYS, members, members * n ** 3) == 1 and L.asan_batch_classifies(NEVER, members, members * n ** 3) == 0)
+    ok(L.asan_batch_classifies(ADAPTIVE, 24, 48000000) == 1 and L.asan_batch_classifies(ADAPTIVE, 25, 48000000) == 0)   # 2 M voxels per member
+    ok([L.asan_batch_lanes(m) for m in (1, 7, 8, 64)] == [1, 1, 4, 4])
+
     # ---- the caller's frame into the pinned ring (csrc/host_copy.h: 32-byte streaming stores from 64 KiB, memcpy below) ---------------
     L.asan_copy_to_pinned.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     src = rng.integers(0, 256, 1228800 + 300).astype(np.uint8)
