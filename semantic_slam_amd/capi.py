@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/tsdf_hip.h (libtsdf_hip.so).
+"""ctypes binding of the C ABI in include/tsdf_hip.h and include/tsdf_hip_diag.h (libtsdf_hip.so).
 
 This is plumbing for tests and bench.py: the same entry points a C++ caller reaches through
 include/tsdf.hpp.  There is no fallback of any kind here: if the shared library is missing
@@ -13,7 +13,9 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # TSDF_HIP_LIB overrides the library path (A/B timing of two builds on one GPU box; tools/sweep.py)
 LIB_PATH = os.environ.get("TSDF_HIP_LIB") or os.path.join(_PKG, "libtsdf_hip.so")
 
-# every symbol include/tsdf_hip.h declares (tests check the .so exports exactly these)
+# every symbol the library exports: what include/tsdf_hip.h (the drop-in contract) and include/tsdf_hip_diag.h (measurement
+# and tuning aids) declare together; DIAG_SYMBOLS is the second header's part (tests check both headers against these
+# lists and the .so against the headers)
 ABI_SYMBOLS = [
     "tsdf_config_default", "tsdf_create", "tsdf_destroy", "tsdf_reset", "tsdf_integrate",
     "tsdf_integrate_u16", "tsdf_convert_depth_u16", "tsdf_set_deferral",
@@ -36,6 +38,13 @@ ABI_SYMBOLS = [
     "tsdf_group_integrate", "tsdf_group_integrate_frames", "tsdf_group_set_deferral", "tsdf_group_sync", "tsdf_group_reset", "tsdf_group_download",
     "tsdf_group_extract_surface", "tsdf_group_extract_crossings", "tsdf_group_extract_mesh",
     "tsdf_group_save_ply", "tsdf_group_save_mesh_ply", "tsdf_group_save_bin",
+]
+DIAG_SYMBOLS = [
+    "tsdf_integrate_sequence_timed", "tsdf_integrate_frames_timed",
+    "tsdf_probe_graph_replay", "tsdf_probe_stream",
+    "tsdf_selftest_fastdiv", "tsdf_selftest_fastdiv_band", "tsdf_selftest_round", "tsdf_selftest_tile_tables",
+    "tsdf_shortcut_stats", "tsdf_brick_list_stats", "tsdf_classification_info", "tsdf_frames_per_launch", "tsdf_last_cam2base",
+    "tsdf_set_kernel_variant", "tsdf_set_brick_shape", "tsdf_brick_shape", "tsdf_default_brick_shape",
 ]
 
 

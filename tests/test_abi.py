@@ -1,7 +1,9 @@
 """The C-ABI boundary without a GPU: the library loads, exports exactly the functions
-include/tsdf_hip.h declares, its struct layout matches the ctypes mirror, and compute entry
-points fail loudly (no CPU fallback) when no device is present."""
+include/tsdf_hip.h (the drop-in contract) and include/tsdf_hip_diag.h (measurement and tuning aids)
+declare, the drop-in compiles against the contract alone, its struct layout matches the ctypes
+mirror, and compute entry points fail loudly (no CPU fallback) when no device is present."""
 import ctypes as C
+import glob
 import os
 import re
 import subprocess
@@ -13,23 +15,51 @@ from semantic_slam_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "tsdf_hip.h")
+DIAG_HEADER = os.path.join(ROOT, "include", "tsdf_hip_diag.h")
 
 
-def declared_functions():
-    src = open(HEADER).read()
+def declared_functions(header):
+    src = open(header).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     return sorted(set(re.findall(r"\b(tsdf_[a-z0-9_]+)\s*\(", src)))
 
 
-def test_header_and_binding_agree():
-    assert declared_functions() == sorted(capi.ABI_SYMBOLS)
+def test_headers_and_binding_agree():
+    assert sorted(declared_functions(HEADER) + declared_functions(DIAG_HEADER)) == sorted(capi.ABI_SYMBOLS)
+
+
+def test_headers_split_contract_from_diagnostics():
+    assert declared_functions(HEADER) == sorted(set(capi.ABI_SYMBOLS) - set(capi.DIAG_SYMBOLS))
+    assert declared_functions(DIAG_HEADER) == sorted(capi.DIAG_SYMBOLS)
+    contract = open(HEADER).read()
+    for name in capi.DIAG_SYMBOLS:
+        assert not re.search(rf"\b{name}\b", contract), f"tsdf_hip.h names {name}"
 
 
 def test_library_exports_every_declared_symbol():
     lib = capi.load()
-    for name in declared_functions():
+    for name in declared_functions(HEADER) + declared_functions(DIAG_HEADER):
         assert hasattr(lib, name), f"libtsdf_hip.so does not export {name}"
     assert b"gfx950" in lib.tsdf_version()
+
+
+# (source, with the cv::Mat overloads): csrc/tsdf_dropin.cpp both ways, every reference call site of tests/
+DROPIN_SOURCES = [("semantic_slam_amd/csrc/tsdf_dropin.cpp", False), ("semantic_slam_amd/csrc/tsdf_dropin.cpp", True)] + [
+    (os.path.relpath(p, ROOT), p.endswith("_cv.cpp")) for p in sorted(glob.glob(os.path.join(ROOT, "tests", "dropin_*.cpp")))]
+
+
+@pytest.mark.parametrize("source,opencv", DROPIN_SOURCES,
+                         ids=[os.path.basename(s) + ("+opencv" if cv else "") for s, cv in DROPIN_SOURCES])
+def test_dropin_compiles_against_the_contract_alone(source, opencv):
+    """The drop-in and the call sites it serves compile as C++11 against include/ (the cv::Mat overloads against
+    tests/fake_opencv), and none of the headers they read (g++ -H lists them) is tsdf_hip_diag.h."""
+    cv = ["-I", os.path.join(ROOT, "tests", "fake_opencv")] if opencv else []
+    r = subprocess.run(["g++", "-std=c++11", "-fsyntax-only", "-H", *cv, "-I", os.path.join(ROOT, "include"),
+                        os.path.join(ROOT, source)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    headers = [os.path.basename(line.lstrip(".").strip()) for line in r.stderr.splitlines() if line.startswith(".")]
+    assert "tsdf_hip.h" in headers
+    assert "tsdf_hip_diag.h" not in headers
 
 
 def test_no_oracle_in_product():
