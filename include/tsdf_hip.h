@@ -533,6 +533,83 @@ int tsdf_batch_associate(tsdf_batch *batch, const tsdf_associate_params *p, cons
                          int32_t *assign_out, float *iou_out);
 
 /*
+ * Geometric segmentation of a live depth frame and the refinement of instance masks by it -- what the reference runs before
+ * it touches any object: mpDoN->extract (ref: src/DoN.cpp:129-270: normals at a small and a large radius, the points where
+ * they differ -- difference of normals, "DoN" -- clustered by Euclidean distance) and fuse_segments (ref:
+ * src/Engine.cpp:300-338: a cluster goes to an instance only if more than mOverlap of it lies mnDist pixels inside the
+ * instance's mask, and only those pixels go on into the object, :216-217).  There it is a PCL pipeline on the CPU; here the
+ * rule is this project's own, stated operation by operation in csrc/tsdf_segment.hip.h and restated in
+ * tests/segment_spec.py; the device's outputs equal the restatement's bit for bit.
+ *   Points    p = (u, v) with d = depth[p] is valid iff isfinite(d) && near_m < d && d <= far_m (tsdf_track's test); its point
+ *             ((u - cx) / fx * d, (v - cy) / fy * d, d), float32 in this order, is quantised per coordinate to the int32
+ *             clamp(rintf(c * 8192.0f), -2^29, 2^29): 2^-13 m.
+ *   Normal    at radius r: a lattice of 17 x 17 taps around p, tap (i, j) at pixel (u + i sx, v + j sy), sx = ceil(hx / 8) with
+ *             hx = clamp(floorf(fx * r / d), 1, W) (sy, hy from fy, H); a tap counts iff inside the image, valid and within
+ *             rintf(r * 8192) quanta of p's point (integer squared distance).  Integer count n, first and second moments of
+ *             Q - P; the covariance S2 / n - (S1 / n)(S1 / n)^T in double; 5 cyclic Jacobi sweeps in double; the normal is the
+ *             eigenvector of the smallest eigenvalue, turned toward the camera (n . P <= 0).  No normal when n < 3 or the
+ *             middle eigenvalue is not above 1.0 (one squared quantum).
+ *   DoN       don = 0.5 * |n_small - n_large| in double; kept iff both normals exist and don > (double)don_thresh; the image
+ *             holds (float)don, 0 where a normal is missing.
+ *   Clusters  kept 4-neighbours are joined iff their points lie within rintf(seg_radius_m * 8192) quanta; components of fewer
+ *             than min_cluster or more than max_cluster pixels are dropped, the others numbered 1..C by their smallest flat
+ *             pixel index.  The cluster image is int32, 0 = none.
+ *   Refine    masks: K contiguous H*W byte images (tsdf_batch_associate's layout), in(k, p) iff the byte >= 128; deep(k, p)
+ *             iff in(k, q) for every q of the (2 inset + 1)^2 square around p (outside the image: not in).  uint32 counts in
+ *             one block of C + C*K words: size[c] at c - 1, inside[c][k] = #{p in cluster c: deep(k, p)} at C + (c - 1) K + k.
+ *             accept(c, k) iff (float)inside / (float)size > overlap (float32, strict).  out[k][p] = 255 iff p is in a
+ *             cluster c, deep(k, p) and accept(c, k); otherwise 0.  The refined masks are {0, 255} images in the layout
+ *             tsdf_batch_integrate_device, tsdf_batch_associate and tsdf_track take.
+ * Deviations from the reference: a subsampled lattice stands in for PCL's full radius neighbourhood; connectivity is
+ * 4-neighbour in the image, not a kd-tree search; normals face the camera, not PCL's (FLT_MAX, ...) viewpoint; the erosion is
+ * a square window, not the distance to the mask's polygon; the cloud has no RGB.
+ *   near_m, far_m    0 <= near < far <= 32, finite       small / large / seg radius   finite, in (0, 32], small < large
+ *   don_thresh       finite, > 0                         min_cluster >= 1, max_cluster >= min_cluster
+ *   overlap          in (0, 1]                           inset   0..16
+ * tsdf_segment_params_default: cam_K and the image size of cfg, near 0, far = cfg->max_depth, radii 0.05 / 0.5 m, don_thresh
+ * 0.1, seg_radius 0.05 m (ref: config/TUM3.yaml:75-78), min_cluster 15 and max_cluster 1000000 (ref: src/DoN.cpp:47), overlap
+ * 0.5 (ref: config/TUM3.yaml:90), inset 2 (mnDist = 1.0, :85: a contour runs through the mask's boundary pixels, so a
+ * distance above 1 needs the two rings around a pixel in the mask).  Host arithmetic only: needs no device.
+ */
+typedef struct tsdf_segment_params {
+    float cam_K[9];
+    int32_t im_height, im_width;
+    float near_m, far_m;
+    float small_radius_m, large_radius_m;
+    float don_thresh;
+    float seg_radius_m;
+    int32_t min_cluster, max_cluster;
+    float overlap;
+    int32_t inset;
+} tsdf_segment_params;
+int tsdf_segment_params_default(const tsdf_config *cfg, tsdf_segment_params *out);
+/*
+ * A segmenter owns the scratch of one image size on one device (about 40 bytes per pixel) and a stream; every call below
+ * queues its work on that stream (tsdf_segmenter_set_stream: the caller's, NULL = its own again), only reads its inputs and
+ * returns when its work is done and the host outputs are there.  Refused, with tsdf_last_error set: an invalid parameter (see
+ * above; checked first), a NULL argument other than those marked, k outside 1..256, p->im_height / im_width unlike the
+ * segmenter's, masks_out_dev == masks_dev, and a count block C + C*k above 2^24 words.
+ */
+typedef struct tsdf_segmenter tsdf_segmenter;
+int tsdf_segmenter_create(int32_t device, int32_t im_height, int32_t im_width, tsdf_segmenter **out);
+int tsdf_segmenter_destroy(tsdf_segmenter *seg);
+int tsdf_segmenter_set_stream(tsdf_segmenter *seg, void *hip_stream);
+/* depth_dev: H*W floats (metres); don_dev: H*W floats or NULL; cluster_dev: H*W int32; *n_clusters = C. */
+int tsdf_segment_depth_device(tsdf_segmenter *seg, const tsdf_segment_params *p, const float *depth_dev,
+                              float *don_dev /* may be NULL */, int32_t *cluster_dev, int32_t *n_clusters);
+/*
+ * Refines k masks by any cluster image with labels in 0..n_clusters (a value outside 1..n_clusters counts as none);
+ * masks_out_dev: k*H*W bytes; counts_host: n_clusters + n_clusters*k words, or NULL.
+ */
+int tsdf_segment_refine_masks_device(tsdf_segmenter *seg, const tsdf_segment_params *p, const int32_t *cluster_dev,
+                                     int32_t n_clusters, const uint8_t *masks_dev, int32_t k, uint8_t *masks_out_dev,
+                                     uint32_t *counts_host /* may be NULL */);
+/* The product call: tsdf_segment_depth_device, then the refinement of the k masks by its clusters. */
+int tsdf_segment_frame(tsdf_segmenter *seg, const tsdf_segment_params *p, const float *depth_dev,
+                       const uint8_t *masks_dev, int32_t k, uint8_t *masks_out_dev,
+                       int32_t *cluster_dev /* may be NULL */, int32_t *n_clusters);
+
+/*
  * One grid over several devices in ONE process.  The reference's host is a C++ program that owns its TSDFs directly
  * (ref: include/tsdf.hpp:22-43; src/Engine.cpp:170-172 drives distinct TSDFs from one loop), so a C++ caller must be
  * able to span the node without a process per GPU.  tsdf_group_create cuts the grid of *cfg (its z_begin / z_end /

@@ -32,6 +32,8 @@ ABI_SYMBOLS = [
     "tsdf_raycast_params_default", "tsdf_raycast_device", "tsdf_raycast", "tsdf_batch_raycast_device",
     "tsdf_track_params_default", "tsdf_track", "tsdf_track_system",
     "tsdf_associate_params_default", "tsdf_associate_count", "tsdf_associate_assign", "tsdf_batch_associate",
+    "tsdf_segment_params_default", "tsdf_segmenter_create", "tsdf_segmenter_destroy", "tsdf_segmenter_set_stream",
+    "tsdf_segment_depth_device", "tsdf_segment_refine_masks_device", "tsdf_segment_frame",
     "tsdf_object_origin", "tsdf_batch_create", "tsdf_batch_destroy", "tsdf_batch_size", "tsdf_batch_volume",
     "tsdf_batch_integrate_device", "tsdf_batch_sync",
     "tsdf_group_create", "tsdf_group_destroy", "tsdf_group_size", "tsdf_group_voxels", "tsdf_group_volume",
@@ -117,6 +119,15 @@ class AssociateLabels(C.Structure):
     """Mirror of `struct tsdf_associate_labels` (include/tsdf_hip.h): four host arrays."""
     _fields_ = [("mask_label", C.c_void_p), ("mask_score", C.c_void_p), ("member_label", C.c_void_p),
                 ("member_score", C.c_void_p)]
+
+
+class SegmentParams(C.Structure):
+    """Mirror of `struct tsdf_segment_params` (include/tsdf_hip.h)."""
+    _fields_ = [
+        ("cam_K", C.c_float * 9), ("im_height", C.c_int32), ("im_width", C.c_int32), ("near_m", C.c_float), ("far_m", C.c_float),
+        ("small_radius_m", C.c_float), ("large_radius_m", C.c_float), ("don_thresh", C.c_float), ("seg_radius_m", C.c_float),
+        ("min_cluster", C.c_int32), ("max_cluster", C.c_int32), ("overlap", C.c_float), ("inset", C.c_int32),
+    ]
 
 
 TRACK_STATUS = {0: "converged", 1: "iterations exhausted", 2: "lost"}
@@ -221,6 +232,13 @@ def load():
                                         vp]
     L.tsdf_batch_associate.argtypes = [vp, C.POINTER(AssociateParams), vp, vp, vp, C.c_int32, C.POINTER(AssociateLabels),
                                        vp, vp, vp]
+    L.tsdf_segment_params_default.argtypes = [C.POINTER(TsdfConfig), C.POINTER(SegmentParams)]
+    L.tsdf_segmenter_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
+    L.tsdf_segmenter_destroy.argtypes = [vp]
+    L.tsdf_segmenter_set_stream.argtypes = [vp, vp]
+    L.tsdf_segment_depth_device.argtypes = [vp, C.POINTER(SegmentParams), vp, vp, vp, C.POINTER(C.c_int32)]
+    L.tsdf_segment_refine_masks_device.argtypes = [vp, C.POINTER(SegmentParams), vp, C.c_int32, vp, C.c_int32, vp, vp]
+    L.tsdf_segment_frame.argtypes = [vp, C.POINTER(SegmentParams), vp, vp, C.c_int32, vp, vp, C.POINTER(C.c_int32)]
     L.tsdf_object_origin.argtypes = [C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp]
     L.tsdf_batch_create.argtypes = [C.POINTER(TsdfConfig), C.c_int32, C.POINTER(vp)]
     L.tsdf_batch_destroy.argtypes = [vp]
@@ -387,6 +405,75 @@ def associate_assign(params, counts, k, n_members, labels=None):
                                        iou.ctypes.data), "tsdf_associate_assign")
     del keep
     return assign, iou
+
+
+def segment_params_default(cfg):
+    """Segmentation parameters from a config (include/tsdf_hip.h): its K and image size, near 0, far = max_depth, radii 0.05 /
+    0.5 m, don_thresh 0.1, seg_radius 0.05 m, clusters of 15..1000000 pixels, overlap 0.5, inset 2 (no device)."""
+    p = SegmentParams()
+    check(load().tsdf_segment_params_default(C.byref(cfg), C.byref(p)), "tsdf_segment_params_default")
+    return p
+
+
+def segment_split(counts, n_clusters, k):
+    """The two count arrays of a refinement block, as views: size [C], inside [C, k]."""
+    return counts[:n_clusters], counts[n_clusters:].reshape(n_clusters, k)
+
+
+class Segmenter:
+    """A tsdf_segmenter: geometric segmentation of depth frames of one size on one device and the refinement of instance
+    masks by it.  Every argument named *_ptr is a device pointer; every call returns when its outputs are written."""
+
+    def __init__(self, im_height, im_width, device=0):
+        self.lib = load()
+        self.h, self.w = int(im_height), int(im_width)
+        self._h = C.c_void_p()
+        check(self.lib.tsdf_segmenter_create(device, self.h, self.w, C.byref(self._h)), "tsdf_segmenter_create")
+
+    def close(self):
+        if self._h:
+            self.lib.tsdf_segmenter_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, hip_stream):
+        """Queue on the caller's stream (a hipStream_t as an integer; None or 0: the segmenter's own again)."""
+        check(self.lib.tsdf_segmenter_set_stream(self._h, hip_stream or None), "tsdf_segmenter_set_stream")
+
+    def segment_depth(self, params, depth_ptr, cluster_ptr, don_ptr=None):
+        """DoN and clusters of a depth frame into cluster_ptr (int32 [h, w]) and, unless None, don_ptr (float32 [h, w]);
+        returns the number of clusters."""
+        n = C.c_int32()
+        check(self.lib.tsdf_segment_depth_device(self._h, C.byref(params), depth_ptr, don_ptr, cluster_ptr, C.byref(n)),
+              "tsdf_segment_depth_device")
+        return n.value
+
+    def refine_masks(self, params, cluster_ptr, n_clusters, masks_ptr, k, masks_out_ptr, want_counts=True):
+        """Refines k masks (uint8 [k, h, w]) by a cluster image with labels 0..n_clusters into masks_out_ptr; returns the
+        count block (size [C], inside [C, k]) or None."""
+        counts = np.zeros(n_clusters + n_clusters * k, np.uint32) if want_counts else None
+        check(self.lib.tsdf_segment_refine_masks_device(self._h, C.byref(params), cluster_ptr, n_clusters, masks_ptr, k,
+                                                        masks_out_ptr, counts.ctypes.data if want_counts else None),
+              "tsdf_segment_refine_masks_device")
+        return segment_split(counts, n_clusters, k) if want_counts else None
+
+    def segment_frame(self, params, depth_ptr, masks_ptr, k, masks_out_ptr, cluster_ptr=None):
+        """The product call: clusters of the frame, then the k masks refined by them; returns the number of clusters."""
+        n = C.c_int32()
+        check(self.lib.tsdf_segment_frame(self._h, C.byref(params), depth_ptr, masks_ptr, k, masks_out_ptr, cluster_ptr,
+                                          C.byref(n)), "tsdf_segment_frame")
+        return n.value
 
 
 def selftest_round(device=0):
