@@ -408,6 +408,40 @@ int tsdf_track_system(tsdf_volume *vol, const tsdf_track_params *p, const float 
                       const float ref_cam2world[16], const float cam2world[16], int32_t level, double system_out[29]);
 
 /*
+ * Merging and re-gridding: every voxel of dst samples src at its own position (trilinear, through both handles' base2world,
+ * origin and voxel size) and folds the sample in as one observation whose weight is the smallest of the 8 corner weights.  Two
+ * uses: a duplicate object (tsdf_batch_associate answered -1 for a partial view, so one physical object lives in two volumes)
+ * is first compared with write = 0 and then merged with write = 1; an object that has outgrown the grid placed from its first
+ * frame (tsdf_object_origin) is resampled into a fresh handle with another origin, size or voxel size.  Not a reference
+ * function (ref: src/Object.cpp:37-49 places an object's grid once and never moves it); the rule is stated exactly in
+ * csrc/tsdf_fuse.hip.h and restated in tests/fuse_spec.py.
+ *   weight_thresh   finite: a source corner counts as observed when its weight is > this; a sample needs all 8 corners
+ *   agree_tol       finite, > 0: two TSDF values (destination truncation units) agree when they differ by at most this
+ *   write           1: update dst; 0: a dry run -- the counts only, not one bit of dst is written
+ * Counts, over the destination voxels with a valid sample that the band test did not skip (sample * trunc_src / trunc_dst
+ * <= -1: skipped, as Integrate skips diff <= -trunc), with dst's values BEFORE the update:
+ *   sampled      all of them                       both_band    of both, |dst tsdf| < 1 and |sample| < 1 (near a surface in both)
+ *   both         of those, dst weight > thresh     agree_band   of both_band, |dst tsdf - sample| <= agree_tol
+ * Whether two volumes show the same object is the caller's decision from agree_band / both_band; the library makes none.
+ * Deviation: labels and colours of dst are neither read nor written.  src is only read.
+ * Results are specified bit for bit (tests/fuse_spec.py), with one exception: where dst already held a NaN, an infinity or a
+ * weight that is not positive the update can yield a NaN, and which NaN (sign, payload) is the hardware's choice; such a voxel
+ * is specified as "a NaN".  A valid sample is always finite, so a dst of finite values and weights >= 0 never gets one.
+ * tsdf_fuse_params_default: weight_thresh 0.9 (the extraction and raycast default), agree_tol 0.4 (two voxels of the default
+ * band of 5 voxels: a choice, not a measurement), write 1.  Host arithmetic only: needs no device.
+ * tsdf_fuse_volume: dst and src are plain handles or borrowed batch members, whole-grid handles on the same device.  The
+ * collected frames of both are applied first (through their batches where they have one); the kernel runs on dst's stream after
+ * everything queued on src's stream so far, and src's stream waits for it, so a later write to src cannot overtake the read; after
+ * a writing call dst's free-space summary is rebuilt.  Synchronous like tsdf_batch_associate: returns when the counts are on the
+ * host.  Refused with TSDF_ERR_INVALID: a NULL dst, src or p; dst == src; a z-slab or a tsdf_group slab on either side; different
+ * devices; a weight_thresh that is not finite; an agree_tol that is not finite or not > 0; a write outside {0, 1}.
+ */
+typedef struct tsdf_fuse_params { float weight_thresh; float agree_tol; int32_t write; } tsdf_fuse_params;
+typedef struct tsdf_fuse_counts { uint64_t sampled, both, both_band, agree_band; } tsdf_fuse_counts;
+int tsdf_fuse_params_default(const tsdf_config *dst_cfg, tsdf_fuse_params *out);   /* host arithmetic only */
+int tsdf_fuse_volume(tsdf_volume *dst, tsdf_volume *src, const tsdf_fuse_params *p, tsdf_fuse_counts *counts /* may be NULL */);
+
+/*
  * Grid origin of a new object volume from its first (masked) depth frame, on the device: the per-axis
  * minimum over pixels with depth > 0 of the back-projected point, starting from 1000 -- what
  * Object::Object computes on the host before it constructs its TSDF (ref: src/Object.cpp:37-49, with the

@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "tsdf_colour_enable", "tsdf_integrate_colour_device", "tsdf_integrate_rgbd", "tsdf_download_colour",
     "tsdf_raycast_params_default", "tsdf_raycast_device", "tsdf_raycast", "tsdf_batch_raycast_device",
     "tsdf_track_params_default", "tsdf_track", "tsdf_track_system",
+    "tsdf_fuse_params_default", "tsdf_fuse_volume",
     "tsdf_associate_params_default", "tsdf_associate_count", "tsdf_associate_assign", "tsdf_batch_associate",
     "tsdf_segment_params_default", "tsdf_segmenter_create", "tsdf_segmenter_destroy", "tsdf_segmenter_set_stream",
     "tsdf_segment_depth_device", "tsdf_segment_refine_masks_device", "tsdf_segment_frame",
@@ -105,6 +106,16 @@ class TrackResult(C.Structure):
         ("cam2world", C.c_float * 16), ("status", C.c_int32), ("iters_run", C.c_int32 * 3), ("inliers", C.c_int32),
         ("rmse", C.c_float),
     ]
+
+
+class FuseParams(C.Structure):
+    """Mirror of `struct tsdf_fuse_params` (include/tsdf_hip.h)."""
+    _fields_ = [("weight_thresh", C.c_float), ("agree_tol", C.c_float), ("write", C.c_int32)]
+
+
+class FuseCounts(C.Structure):
+    """Mirror of `struct tsdf_fuse_counts` (include/tsdf_hip.h)."""
+    _fields_ = [("sampled", C.c_uint64), ("both", C.c_uint64), ("both_band", C.c_uint64), ("agree_band", C.c_uint64)]
 
 
 class AssociateParams(C.Structure):
@@ -226,6 +237,8 @@ def load():
     L.tsdf_track_params_default.argtypes = [C.POINTER(TsdfConfig), C.POINTER(TrackParams)]
     L.tsdf_track.argtypes = [vp, C.POINTER(TrackParams), vp, vp, vp, C.POINTER(TrackResult)]
     L.tsdf_track_system.argtypes = [vp, C.POINTER(TrackParams), vp, vp, vp, vp, C.c_int32, vp]
+    L.tsdf_fuse_params_default.argtypes = [C.POINTER(TsdfConfig), C.POINTER(FuseParams)]
+    L.tsdf_fuse_volume.argtypes = [vp, vp, C.POINTER(FuseParams), C.POINTER(FuseCounts)]
     L.tsdf_associate_params_default.argtypes = [C.POINTER(TsdfConfig), C.POINTER(AssociateParams)]
     L.tsdf_associate_count.argtypes = [C.c_int32, C.POINTER(AssociateParams), vp, vp, C.c_int32, vp, vp, C.c_int32, vp]
     L.tsdf_associate_assign.argtypes = [C.POINTER(AssociateParams), vp, C.c_int32, C.c_int32, C.POINTER(AssociateLabels), vp,
@@ -357,6 +370,14 @@ def track_params_default(cfg):
     {10, 5, 4}, 0.10 m, cos(20 deg), min_inliers 300, eps 1e-5 rad / 1e-5 m (no device)."""
     p = TrackParams()
     check(load().tsdf_track_params_default(C.byref(cfg), C.byref(p)), "tsdf_track_params_default")
+    return p
+
+
+def fuse_params_default(cfg):
+    """Merge parameters for a destination config (include/tsdf_hip.h): weight_thresh 0.9, agree_tol 0.4, write 1 (no
+    device)."""
+    p = FuseParams()
+    check(load().tsdf_fuse_params_default(C.byref(cfg), C.byref(p)), "tsdf_fuse_params_default")
     return p
 
 
@@ -826,6 +847,17 @@ class Volume:
         A[np.triu_indices(6)] = out[:21]
         A = A + np.triu(A, 1).T
         return A, out[21:27].copy(), float(out[27]), int(out[28])
+
+    # -- merging ----------------------------------------------------------------------------
+    def fuse_from(self, src, params=None):
+        """Merge the volume `src` into this one by trilinear resampling (csrc/tsdf_fuse.hip.h): every voxel of this grid
+        samples src at its own position.  params: a FuseParams, default fuse_params_default(cfg); write = 0 compares only.
+        Returns the counts as a dict: sampled, both, both_band, agree_band."""
+        p = fuse_params_default(self.cfg) if params is None else params
+        c = FuseCounts()
+        check(self.lib.tsdf_fuse_volume(self._h, src._h, C.byref(p), C.byref(c)), "tsdf_fuse_volume")
+        return {"sampled": int(c.sampled), "both": int(c.both), "both_band": int(c.both_band),
+                "agree_band": int(c.agree_band)}
 
     # -- outputs ----------------------------------------------------------------------------
     def count_surface(self, weight_thresh=0.9):

@@ -1,0 +1,173 @@
+"""The merge rule (csrc/tsdf_fuse.hip.h) in its NumPy restatement tests/fuse_spec.py, without a GPU: the C structs and
+defaults, the identities the rule was built to have (identical and lattice-shifted grids copy bits), the counts' order, and
+merging two halves of a sequence against fusing the whole sequence."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+import fuse_spec as fs
+from semantic_slam_amd import capi, synth
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+f32 = np.float32
+VS = 2.0 ** -8          # a power of two, with origins that are multiples of it: voxel centres and (p - origin) / vs are exact
+EYE = np.eye(4, dtype=f32).ravel()
+
+
+def grid(dims, origin, vs=VS, trunc=None, base2world=EYE):
+    return (tuple(dims), np.asarray(origin, f32), f32(vs), f32(vs) * f32(5) if trunc is None else f32(trunc),
+            np.asarray(base2world, f32))
+
+
+def random_state(rng, n, p_fresh=0.3):
+    t = rng.uniform(-1.0, 1.0, n).astype(f32)
+    w = rng.choice(np.array([1.0, 2.0, 3.0, 7.0], f32), n)
+    fresh = rng.uniform(0, 1, n) < p_fresh
+    t[fresh], w[fresh] = 1.0, 0.0
+    return t, w
+
+
+def test_fuse_params_default_and_struct_layout(tmp_path):
+    p = capi.fuse_params_default(capi.default_config())
+    assert f32(p.weight_thresh) == f32(0.9) and f32(p.agree_tol) == f32(0.4) and p.write == 1
+    lib = capi.load()
+    assert lib.tsdf_fuse_params_default(None, C.byref(p)) == -1 and b"NULL" in lib.tsdf_last_error()
+    mirrors = {"tsdf_fuse_params": capi.FuseParams, "tsdf_fuse_counts": capi.FuseCounts}
+    body = ""
+    for name, cls in mirrors.items():
+        body += f'printf("{name} size %zu\\n", sizeof({name}));\n'
+        body += "".join(f'printf("{name} {f} %zu\\n", offsetof({name}, {f}));\n' for f, _ in cls._fields_)
+    prog = tmp_path / "layout.c"
+    prog.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "tsdf_hip.h"\nint main(void){\n' + body + "return 0;}\n")
+    exe = tmp_path / "layout"
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(prog), "-o", str(exe)])
+    got = {tuple(line.split()[:2]): int(line.split()[2]) for line in subprocess.check_output([str(exe)]).decode().splitlines()}
+    for name, cls in mirrors.items():
+        assert got[(name, "size")] == C.sizeof(cls), name
+        for f, _ in cls._fields_:
+            assert got[(name, f)] == getattr(cls, f).offset, (name, f)
+
+
+def test_identical_grids_copy_bits_into_a_fresh_destination():
+    """(VS is a power of two: with a voxel size like 0.004 the float32 quotient (origin + x * vs - origin) / vs is not always
+    the integer x, and the rule then interpolates between two neighbours, as it should.)"""
+    rng = np.random.default_rng(1)
+    dims = (21, 14, 9)
+    g = grid(dims, [-8 * VS, 3 * VS, 200 * VS])
+    n = int(np.prod(dims))
+    t, w = random_state(rng, n)
+    t[rng.choice(n, 40, replace=False)] = -1.0          # skipped by the band test
+    w[rng.choice(n, 40, replace=False)] = f32(0.9)      # at the threshold: not observed
+    info = {}
+    out_t, out_w, counts = fs.fuse(np.ones(n, f32), np.zeros(n, f32), g, t, w, g, info=info)
+    assert not info["f"].any()
+    take = (w > f32(0.9)) & (t > f32(-1))
+    assert 0.4 * n < take.sum() < n
+    assert np.array_equal(out_t[take].view(np.uint32), t[take].view(np.uint32))
+    assert np.array_equal(out_w[take].view(np.uint32), w[take].view(np.uint32))
+    assert np.all(out_t[~take] == 1.0) and np.all(out_w[~take] == 0.0)
+    assert counts == {"sampled": int(take.sum()), "both": 0, "both_band": 0, "agree_band": 0}
+
+
+def lattice_shift_case(seed=2):
+    """Source (24, 18, 10) at an origin that is a multiple of VS; the destination is larger and starts (8, 4, 0) voxels
+    before it.  Returns (dst grid, src grid, src t, src w, and what a fresh destination must hold afterwards: t, w, the
+    number of voxels taken over) -- the source's bits in the shifted block wherever weight > 0.9 and t > -1, (1, 0) elsewhere."""
+    rng = np.random.default_rng(seed)
+    sdims, ddims = (24, 18, 10), (40, 30, 13)
+    so = np.array([-12 * VS, -9 * VS, 230 * VS], f32)
+    do = so - np.array([8 * VS, 4 * VS, 0], f32)
+    t, w = random_state(rng, int(np.prod(sdims)), p_fresh=0.2)
+    box = (slice(0, 10), slice(4, 4 + 18), slice(8, 8 + 24))      # z, y, x
+    t3, w3 = t.reshape(sdims[::-1]), w.reshape(sdims[::-1])
+    take = (w3 > f32(0.9)) & (t3 > f32(-1))
+    want_t, want_w = np.ones(ddims[::-1], f32), np.zeros(ddims[::-1], f32)
+    want_t[box] = np.where(take, t3, f32(1))
+    want_w[box] = np.where(take, w3, f32(0))
+    assert take.sum() > 0.5 * t.size
+    return grid(ddims, do), grid(sdims, so), t, w, want_t.ravel(), want_w.ravel(), int(take.sum())
+
+
+def test_lattice_shift_copies_the_block_and_touches_nothing_else():
+    dg, sg, t, w, want_t, want_w, taken = lattice_shift_case()
+    n = want_t.size
+    info = {}
+    out_t, out_w, counts = fs.fuse(np.ones(n, f32), np.zeros(n, f32), dg, t, w, sg, info=info)
+    assert info["inside"].sum() == t.size and not info["f"].any()       # f_i == 0: one source voxel per sample
+    assert np.array_equal(out_t.view(np.uint32), want_t.view(np.uint32))
+    assert np.array_equal(out_w.view(np.uint32), want_w.view(np.uint32))
+    assert counts == {"sampled": taken, "both": 0, "both_band": 0, "agree_band": 0}
+
+
+def test_counts_are_nested_and_do_not_depend_on_write():
+    rng = np.random.default_rng(3)
+    ddims, sdims = (19, 17, 11), (16, 20, 12)
+    R = synth.rot_z(0.2) @ synth.rot_x(-0.1)
+    b2w_src = fs.pose_about(R, [0.0, 0.0, 0.92], [0.01, -0.005, 0.004])   # about the middle of both grids
+    dg = grid(ddims, [-0.04, -0.035, 0.9], vs=0.004)
+    sg = grid(sdims, [-0.05, -0.04, 0.89], vs=0.005, base2world=b2w_src)
+    dt, dw = random_state(rng, int(np.prod(ddims)))
+    st, sw = random_state(rng, int(np.prod(sdims)), p_fresh=0.05)
+    t1, w1, c1 = fs.fuse(dt, dw, dg, st, sw, sg, write=1)
+    t0, w0, c0 = fs.fuse(dt, dw, dg, st, sw, sg, write=0)
+    assert c0 == c1
+    assert c1["sampled"] >= c1["both"] >= c1["both_band"] >= c1["agree_band"] > 0
+    assert c1["sampled"] > c1["both"] > c1["agree_band"]
+    assert np.array_equal(t0.view(np.uint32), dt.view(np.uint32)) and np.array_equal(w0.view(np.uint32), dw.view(np.uint32))
+    assert (t1.view(np.uint32) != dt.view(np.uint32)).sum() >= c1["sampled"] // 2
+    tight = fs.fuse(dt, dw, dg, st, sw, sg, agree_tol=1e-3, write=0)[2]
+    assert tight["both_band"] == c1["both_band"] and tight["agree_band"] < c1["agree_band"]
+
+
+# Each running-mean step of Integrate, (t * w + v) / (w + 1), rounds three times on values of magnitude <= 1, and the error
+# carried in shrinks by w_old / w_new, so after n frames a voxel is within 3 n roundings of 2^-24 of the exact mean of its
+# samples.  Here the all-frames volume (<= 16 frames) and each of the two halves are within 3 * 16 of it, which puts the exact
+# merge of the halves within 6 * 16 of the all-frames value (the halves' errors enter with weights w_a / w_n and w_b / w_n,
+# which sum to one); the merge step itself adds four more roundings (two products, a sum, a quotient), each on a magnitude
+# <= 2: 8 units.
+MERGE_TOL = (6 * 16 + 8) * 2.0 ** -24
+
+
+def test_merging_two_halves_equals_fusing_all_frames(oracle):
+    dims, vs = (48, 48, 48), 2.0 ** -6
+    origin = np.array([-24 * vs, -24 * vs, 52 * vs], f32)
+    h, w = 120, 160
+    K = synth.TUM_K.copy()
+    K[[0, 2, 4, 5]] *= 0.25
+    scene = synth.SurfScene(dims, vs, origin, K=K, h=h, w=w)
+    trunc = float(f32(vs) * f32(5))
+    vols = {name: oracle.init_grid(dims) for name in ("all", "even", "odd")}
+    for k in range(16):
+        c2w = scene.pose(k, n=16)
+        depth = scene.depth(c2w, quantize=True)
+        c2b = oracle.cam2base(EYE, c2w)
+        for name in ("all", "even" if k % 2 == 0 else "odd"):
+            oracle.integrate(K, c2b, depth, dims, origin, vs, trunc, *vols[name])
+    g = grid(dims, origin, vs=vs, trunc=trunc)
+    info = {}
+    t, wgt, counts = fs.fuse(*vols["even"], g, *vols["odd"], g, weight_thresh=0.0, info=info)
+    assert not info["f"].any()
+    all_t, all_w = vols["all"]
+    assert counts["sampled"] == int((vols["odd"][1] > 0).sum()) > 0.2 * all_w.size
+    assert counts["both"] > 0.5 * counts["sampled"] and info["fresh"] > 0
+    assert all_w.max() == 16.0
+    assert np.array_equal(wgt.view(np.uint32), all_w.view(np.uint32))
+    err = np.abs(t.astype(np.float64) - all_t.astype(np.float64)).max()
+    assert err <= MERGE_TOL, f"max |merged - all| = {err / 2.0 ** -24:.1f} x 2^-24, bound {MERGE_TOL / 2.0 ** -24:.0f}"
+
+
+def test_the_gpu_parity_cases_are_not_vacuous():
+    """The inputs of tests/test_gpu_fuse.py's parity test, through the restatement: in every case at least 10 % of the
+    destination's voxels take a valid sample, at least 1 % lie inside the source box but are rejected (a corner not
+    observed, a sample that is not finite) or skipped by the band test, and both branches of the update occur."""
+    import fuse_cases as fc
+    for dims in fc.DST_SHAPES:
+        for pose in range(fc.N_POSES):
+            for state in fc.STATES:
+                sampled, rejected, fresh, observed = fc.vacuity(dims, pose, state)
+                assert sampled >= 0.10 and rejected >= 0.01 and fresh > 0 and observed > 0, (dims, pose, state, sampled, rejected)
+    ratios = {f32(fc.configs(fc.DST_SHAPES[0], p)[1].trunc_margin) / f32(fc.configs(fc.DST_SHAPES[0], p)[0].trunc_margin)
+              for p in range(fc.N_POSES)}
+    assert min(ratios) < 1 < max(ratios)
