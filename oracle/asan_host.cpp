@@ -1,6 +1,6 @@
 // asan_host.cpp -- the product's HOST-side arithmetic (no device code) compiled for the CPU sanitizer run:
 // semantic_slam_amd/csrc/pose_math.h (4x4 multiply / cofactor inverse, ref: src/tsdf.cu:253-403) and
-// semantic_slam_amd/csrc/host_derive.h (wavefront brick choice, guards and margins of the exact shortcuts, launch policy) and
+// semantic_slam_amd/csrc/host_derive.h (wavefront brick choice, guards and margins of the exact shortcuts, launch policy, scratch block layout) and
 // semantic_slam_amd/csrc/host_copy.h (the caller's frame into the pinned ring: streaming stores), behind plain C entry points, linked with tsdf_oracle.c into oracle/_asan/liboracle_asan.so by `make -C oracle asan`
 // (-fsanitize=address,undefined -fno-sanitize-recover=all).  tests/test_sanitizers.py runs the golden vectors, the pose
 // known-answer tests, the writers and these entry points under it.  TEST INFRASTRUCTURE: the headers are
@@ -72,5 +72,13 @@ int asan_batch_classifies(int mode, int members, int64_t launch_voxels)
     return tsdf_host::batch_classifies(mode_of(mode), members, launch_voxels) ? 1 : 0;
 }
 int asan_batch_lanes(int members) { return tsdf_host::batch_lanes(members); }
+
+// ---- scratch blocks: offsets[i] of n regions of bytes[i] carved in turn out of one block; returns the block's size ----
+size_t asan_regions(const size_t *bytes, int n, size_t *offsets)
+{
+    tsdf_host::Regions r;
+    for (int i = 0; i < n; ++i) offsets[i] = r.add(bytes[i]);
+    return r.total();
+}
 
 }  // extern "C"

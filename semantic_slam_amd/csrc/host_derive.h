@@ -280,4 +280,12 @@ inline bool batch_classifies(Classify mode, int members, int64_t launch_voxels)
 constexpr int kBatchSideStreams = 4;
 inline int batch_lanes(int members) { return members < 8 ? 1 : kBatchSideStreams; }
 
+// One block carved into regions that each start on a 256-byte boundary: add(bytes) gives the next region's offset, total() the
+// bytes of the block so far (the last region is not padded).
+struct Regions {
+    size_t add(size_t bytes) { const size_t at = (end_ + 255) / 256 * 256; end_ = at + bytes; return at; }
+    size_t total() const { return end_; }
+    size_t end_ = 0;
+};
+
 }  // namespace tsdf_host

@@ -1,5 +1,6 @@
-// tsdf_capi.hip -- implementation of include/tsdf_hip.h (libtsdf_hip.so); include/tsdf_hip_diag.h, the measurement and
-// tuning aids, is implemented in tsdf_diag.hip.h, included at the end.
+// tsdf_capi.hip -- implementation of include/tsdf_hip.h (libtsdf_hip.so).  Handles, integration, batches, extraction and files
+// are here; raycasting, tracking, merging, association and segmentation each in a tsdf_<feature>_host.hip.h beside its kernels,
+// the group in tsdf_group.hip.h and include/tsdf_hip_diag.h in tsdf_diag.hip.h, all included at the end (one translation unit).
 //
 // One handle = one z-slab of the voxel grid resident in HBM on one device + one HIP stream.
 // Host work per frame is the 4x4 pose composition (pose_math.h) and one kernel launch; the
@@ -135,11 +136,7 @@ struct tsdf_volume {
     int sweep_parity = 0;    // direction of the next integrate_tile sweep (flips every launch; a performance hint only)
 #ifdef TSDF_EXPERIMENTS
     // per-launch frame blocks of integrate_multi: pinned host ring -> device ring (allocated on first use)
-    HostPtr<tsdfk::FramePose> h_frames[kStageSlots];
-    DevPtr<tsdfk::FramePose> d_frames[kStageSlots];
-    Event frames_done[kStageSlots];
-    bool frames_used[kStageSlots] = {};
-    int frames_next = 0;
+    StageRing<Staged<tsdfk::FramePose>, kStageSlots> frames;
 #endif
     // per-voxel label fusion (allocated by tsdf_labels_enable)
     DevPtr<uint16_t> d_label;
@@ -147,11 +144,7 @@ struct tsdf_volume {
     float prob_thd = 0.0f;
     // per-voxel colour (allocated by tsdf_colour_enable): packed 0x00BBGGRR; staging of the RGB frames of tsdf_integrate_rgbd
     DevPtr<uint32_t> d_colour;
-    DevPtr<uint8_t> d_rgb[kStageSlots];
-    HostPtr<uint8_t> h_rgb[kStageSlots];
-    Event rgb_done[kStageSlots];
-    bool rgb_used[kStageSlots] = {};
-    int rgb_next = 0;
+    StageRing<Staged<uint8_t>, kStageSlots> rgb;
     // free-space summary (one word per 256-voxel row segment), see tsdf_kernels.hip.h
     DevPtr<uint32_t> d_flags;
     size_t n_flags = 0;
@@ -163,11 +156,10 @@ struct tsdf_volume {
     bool fine_tables = false;        // ... and, beside them, 4-pixel tiles for brick-sized boxes (tsdf_host::fine_tables)
     bool flags_known_zero = false;
 #ifdef TSDF_EXPERIMENTS
-    DevPtr<unsigned int> d_super;    // per super-brick frame words of the current fused brick launch (classify_superbricks)
-    size_t super_words = 0;
+    DevBuf<unsigned int> d_super;    // per super-brick frame words of the current fused brick launch (classify_superbricks)
 #endif
-    DevPtr<uint4> d_work;        // work list of the current fused brick launch: {brick, slice group, free frames, skipped frames}
-    size_t work_entries = 0;     // per live brick (classify_brick_list); capacity = every brick of the slab
+    DevBuf<uint4> d_work;        // work list of the current fused brick launch: {brick, slice group, free frames, skipped frames}
+                                 // per live brick (classify_brick_list); capacity = every brick of the slab, once per list parity
     int64_t work_nsuper = 0, work_bucket_supers = 0;   // super-bricks of the shape the list was sized for; most of them in one sub-list
     int work_wedge_mode = -1;                  // ... and the list_bucket mode they were counted under
     // optional diagnostic counters (tsdf_shortcut_stats)
@@ -191,18 +183,14 @@ struct tsdf_volume {
     double claim_fraction = 0.0;    // claimed / total of the last launch that was read back
     int launches_unclassified = 0;  // since the last classifying launch
     // scratch for surface extraction (allocated on first use)
-    DevPtr<char> d_scratch;
-    size_t scratch_bytes = 0;
+    DevBuf<char> d_scratch;
     // class of every workgroup of a one-frame masked launch (classify_workgroups), grown on demand
-    DevPtr<uint8_t> d_wg_class;
-    size_t wg_class_bytes = 0;
+    DevBuf<uint8_t> d_wg_class;
     // output list of the extraction passes (points / vertices / triangles), grown on demand and kept
-    DevPtr<char> d_list;
-    size_t list_bytes = 0;
+    DevBuf<char> d_list;
     // tracking (tsdf_track*), allocated on first use and grown with the image: the model render (depth | normal), the partial
     // rows of an association pass and the pose state, in one block; the state's pinned host copy
-    DevPtr<char> d_track;
-    size_t track_bytes = 0;
+    DevBuf<char> d_track;
     HostPtr<tsdfk::TrackState> h_track;
     // merging (tsdf_fuse_volume with this handle as the destination), allocated on first use, all or none: the four counts in
     // HBM and pinned; src_ready is recorded on the source's stream before the kernel, done on this handle's stream after it
@@ -219,13 +207,8 @@ struct tsdf_batch {
     std::vector<tsdf_volume *> vols;
     Stream stream;
     // per-frame parameter blocks: pinned host ring -> device ring
-    HostPtr<tsdfk::IntegrateParams> h_params[kStageSlots];
-    DevPtr<tsdfk::IntegrateParams> d_params[kStageSlots];
-    HostPtr<tsdfk::FramePose> h_poses[kStageSlots];
-    DevPtr<tsdfk::FramePose> d_poses[kStageSlots];
-    Event slot_done[kStageSlots];
-    bool slot_used[kStageSlots] = {};
-    int slot_next = 0;
+    struct FrameBlocks { Staged<tsdfk::IntegrateParams> params; Staged<tsdfk::FramePose> poses; };
+    StageRing<FrameBlocks, kStageSlots> blocks;
     DevPtr<int2> d_slice_map;
     int total_slices = 0, max_blocks = 0;
     DevPtr<int2> d_group_map;    // {object, slice group}: the brick launches' z index (a brick spans brick_s slices)
@@ -235,8 +218,7 @@ struct tsdf_batch {
     DevPtr<float2> d_tiles;
     size_t tiles_per_object = 0;
     DevPtr<uint8_t> d_wg_class;
-    DevPtr<uint8_t> d_brick_class;   // class per wavefront brick of the launch (classify_bricks_batched), on first use
-    size_t brick_class_bytes = 0;
+    DevBuf<uint8_t> d_brick_class;   // class per wavefront brick of the launch (classify_bricks_batched), on first use
     // Deferred integration of a batch of large members (tsdf_batch_integrate_device): frames are collected in HBM -- the
     // depth image once, every member's mask beside it -- and applied by ONE fused launch per member per 32 frames
     // (the volume then moves once per 32 frames instead of once per frame); flushed by anything that observes a member.
@@ -253,23 +235,17 @@ struct tsdf_batch {
     Event side_done[kBatchSideStreams];
     Event collected;
     // the members as tsdf_batch_raycast_device's kernel reads them: pinned host block -> HBM (allocated on first use); the host
-    // block is refilled only after the copy out of it (ray_copied) has run
-    HostPtr<tsdfk::RayVolume> h_ray;
-    DevPtr<tsdfk::RayVolume> d_ray;
-    Event ray_copied;
-    bool ray_used = false;
+    // block is refilled only after the copy out of it has run: a ring of one slot
+    StageRing<Staged<tsdfk::RayVolume>, 1> ray;
     // association (tsdf_batch_associate), allocated on first use and grown with the image and the count block: the render
     // (member | depth) and the counts in HBM; the counts' pinned host copy
-    DevPtr<char> d_assoc;
-    size_t assoc_bytes = 0;
-    HostPtr<uint32_t> h_assoc;
-    size_t h_assoc_words = 0;
+    DevBuf<char> d_assoc;
+    HostBuf<uint32_t> h_assoc;
 };
 
 namespace {
 
 int flush_pending(tsdf_volume *v);
-int fail(int code, const char *fmt, ...);
 int batch_flush(tsdf_batch *b);
 int group_flush(tsdf_group *g);   // tsdf_group.hip.h
 int batch_collect(tsdf_batch *b, const float *depth_dev, const uint8_t *const *masks_dev, const float cam2world[16]);
@@ -493,11 +469,7 @@ int launch_masked_bricks(tsdf_volume *v, tsdfk::IntegrateParams &p)
     int rc0 = tables_begin(v, &tiles);
     if (rc0) return rc0;
     const size_t n_bricks = (size_t)blocks * nz * 4;
-    if (v->wg_class_bytes < n_bricks) {
-        v->wg_class_bytes = 0;
-        HIP_TRY(dev_alloc(v->d_wg_class, n_bricks));
-        v->wg_class_bytes = n_bricks;
-    }
+    HIP_TRY(v->d_wg_class.ensure(n_bricks));
     const float *d = p.depth;
     const uint8_t *m = p.mask;
     int rc = build_tile_tables(v->stream, v->cfg, p, &d, &m, 1, tiles);
@@ -777,6 +749,7 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
 #endif
     tsdfk::BrickListParams bl;
     int64_t n_super = 0, cap = 0;
+    const size_t lists = v->pipeline_ok ? 2 : 1;     // one list per parity
     if (listed) {
         // A pre-pass compacts the bricks some frame may touch into a work list and the launch runs one wavefront per entry.
         bl.nsx = (mi.common.bricks_per_group + tsdfk::kSuperBX - 1) / tsdfk::kSuperBX;
@@ -807,15 +780,11 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
         cap = v->work_bucket_supers * tsdfk::kSuperBricks;
         const int64_t total = cap * tsdfk::kListBuckets;
         if (total > 0x7fffffffll - 1024) return fail(TSDF_ERR_INVALID, "fused launch: %lld bricks exceed the work list's 32-bit index", (long long)total);
-        if (v->work_entries < (size_t)total) {
-            if (v->d_work) {      // (a list in flight on either stream is done before its memory goes)
-                if (v->pre_stream) HIP_TRY(hipStreamSynchronize(v->pre_stream));
-                HIP_TRY(hipStreamSynchronize(v->stream));
-            }
-            v->work_entries = 0;
-            HIP_TRY(dev_alloc(v->d_work, (v->pipeline_ok ? 2 : 1) * (size_t)total * sizeof(uint4)));     // one list per parity
-            v->work_entries = (size_t)total;
+        if (!v->d_work.fits(lists * (size_t)total) && v->d_work) {      // (a list in flight on either stream is done before its memory goes)
+            if (v->pre_stream) HIP_TRY(hipStreamSynchronize(v->pre_stream));
+            HIP_TRY(hipStreamSynchronize(v->stream));
         }
+        HIP_TRY(v->d_work.ensure(lists * (size_t)total));
     }
     const hipStream_t ps = pipelined ? v->pre_stream : v->stream;
     // a failure from here on joins the side stream back into the handle's stream and gives the table slot back
@@ -856,7 +825,7 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
 #endif
     if (listed) {
         const int64_t per_group = (int64_t)mi.common.brick_groups * mi.common.bricks_per_group;
-        uint4 *const work_p = v->d_work + (size_t)P * v->work_entries;
+        uint4 *const work_p = v->d_work + (size_t)P * (v->d_work.capacity() / lists);
         bl.list = work_p;
         bl.counters = reinterpret_cast<unsigned char *>(claims_p);
         bl.bucket_cap = (unsigned int)cap;
@@ -1094,24 +1063,6 @@ int fill(tsdf_volume *v)
         HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)v->d_flags, 3, v->n_flags, v->stream));
         v->flags_known_zero = false;
     }
-    return TSDF_OK;
-}
-
-int ensure_list(tsdf_volume *v, size_t bytes)
-{
-    if (v->list_bytes >= bytes) return TSDF_OK;
-    v->list_bytes = 0;
-    HIP_TRY(dev_alloc(v->d_list, bytes));
-    v->list_bytes = bytes;
-    return TSDF_OK;
-}
-
-int ensure_scratch(tsdf_volume *v, size_t bytes)
-{
-    if (v->scratch_bytes >= bytes) return TSDF_OK;
-    v->scratch_bytes = 0;
-    HIP_TRY(dev_alloc(v->d_scratch, bytes));
-    v->scratch_bytes = bytes;
     return TSDF_OK;
 }
 
@@ -1808,33 +1759,23 @@ int tsdf_integrate_rgbd(tsdf_volume *v, const float *depth_host, const uint8_t *
     const size_t px = (size_t)v->cfg.im_height * v->cfg.im_width, img = px * sizeof(float);
     // the colour image has a small ring of its own (pinned + HBM, allocated on first use; one event per slot: the colour
     // kernel that read it), the depth frame goes through the shared store like any other host frame
-    const int s = v->rgb_next;
-    v->rgb_next = (s + 1) % kStageSlots;
-    if (!v->d_rgb[s]) {      // all three or none
-        DevPtr<uint8_t> d;
-        HostPtr<uint8_t> h;
-        Event done;
-        HIP_TRY(dev_alloc(d, px * 3));
-        HIP_TRY(host_alloc(h, px * 3, hipHostMallocDefault));
-        HIP_TRY(event_create(done));
-        v->d_rgb[s] = std::move(d); v->h_rgb[s] = std::move(h); v->rgb_done[s] = std::move(done);
-    }
-    if (v->rgb_used[s]) HIP_TRY(hipEventSynchronize(v->rgb_done[s]));
-    std::memcpy(v->h_rgb[s], rgb_host, px * 3);           // the caller may free both images after we return
+    decltype(v->rgb)::Slot *s = nullptr;
+    HIP_TRY(v->rgb.take(&s));
+    if (!s->dev) HIP_TRY(staged_alloc(*s, s->done, px * 3));
+    std::memcpy(s->host, rgb_host, px * 3);           // the caller may free both images after we return
     int slot = -1;
     void *dev = nullptr;
     rc = stage_begin(v, img, [&](float *pinned) { tsdf_host::copy_to_pinned(pinned, depth_host, img); }, &slot, &dev);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(v->d_rgb[s], v->h_rgb[s], px * 3, hipMemcpyHostToDevice, v->copy_stream));
+    HIP_TRY(hipMemcpyAsync(s->dev, s->host, px * 3, hipMemcpyHostToDevice, v->copy_stream));
     rc = stream_waits_for_copies(v);
     if (rc) return rc;
     float c2b[16];
     compose_cam2base(v, cam2world, c2b);
     rc = launch_integrate(v, static_cast<const float *>(dev), nullptr, c2b);
-    if (rc == TSDF_OK) rc = launch_colour(v, static_cast<const float *>(dev), v->d_rgb[s], c2b);
+    if (rc == TSDF_OK) rc = launch_colour(v, static_cast<const float *>(dev), s->dev, c2b);
     if (rc) return rc;
-    HIP_TRY(hipEventRecord(v->rgb_done[s], v->stream));
-    v->rgb_used[s] = true;
+    HIP_TRY(v->rgb.consumed(s, v->stream));
     return stage_end(v, &slot, 1);
 }
 
@@ -2003,12 +1944,12 @@ int tsdf_batch_create(const tsdf_config *cfgs, int32_t n, tsdf_batch **out)
     if (e == hipSuccess) e = stream_create(b->stream);
     if (e == hipSuccess && !map.empty()) e = dev_alloc(b->d_slice_map, map.size() * sizeof(int2));
     if (e == hipSuccess && !map.empty()) e = hipMemcpy(b->d_slice_map, map.data(), map.size() * sizeof(int2), hipMemcpyHostToDevice);
-    for (int i = 0; i < kStageSlots && e == hipSuccess; ++i) {
-        e = host_alloc(b->h_params[i], n * sizeof(tsdfk::IntegrateParams), hipHostMallocDefault);
-        if (e == hipSuccess) e = dev_alloc(b->d_params[i], n * sizeof(tsdfk::IntegrateParams));
-        if (e == hipSuccess) e = host_alloc(b->h_poses[i], n * sizeof(tsdfk::FramePose), hipHostMallocDefault);
-        if (e == hipSuccess) e = dev_alloc(b->d_poses[i], n * sizeof(tsdfk::FramePose));
-        if (e == hipSuccess) e = event_create(b->slot_done[i]);
+    for (auto &s : b->blocks.slots) {
+        if (e == hipSuccess) e = host_alloc(s.params.host, n * sizeof(tsdfk::IntegrateParams), hipHostMallocDefault);
+        if (e == hipSuccess) e = dev_alloc(s.params.dev, n * sizeof(tsdfk::IntegrateParams));
+        if (e == hipSuccess) e = host_alloc(s.poses.host, n * sizeof(tsdfk::FramePose), hipHostMallocDefault);
+        if (e == hipSuccess) e = dev_alloc(s.poses.dev, n * sizeof(tsdfk::FramePose));
+        if (e == hipSuccess) e = event_create(s.done);
     }
     if (e != hipSuccess) return cleanup(fail(TSDF_ERR_HIP, "tsdf_batch_create: %s", hipGetErrorString(e)));
     for (tsdf_volume *v : b->vols) {   // creation fills ran on each volume's own stream: finish them, then share ours
@@ -2058,17 +1999,18 @@ int tsdf_batch_integrate_device(tsdf_batch *b, const float *depth_dev, const uin
         int rc = batch_flush(b);   // the policy changed between calls (tsdf_set_deferral, a kernel variant)
         if (rc) return rc;
     }
-    const int s = b->slot_next;
-    b->slot_next = (s + 1) % kStageSlots;
-    if (b->slot_used[s]) HIP_TRY(hipEventSynchronize(b->slot_done[s]));
+    decltype(b->blocks)::Slot *s = nullptr;
+    HIP_TRY(b->blocks.take(&s));
+    tsdfk::IntegrateParams *const h_params = s->params.host, *const d_params = s->params.dev;
+    tsdfk::FramePose *const h_poses = s->poses.host, *const d_poses = s->poses.dev;
     for (int i = 0; i < n; ++i) {
         tsdf_volume *v = b->vols[i];
         float c2b[16];
         compose_cam2base(v, cam2world, c2b);   // each object has its own base frame (ref: src/Object.cpp:23-29)
         std::memcpy(v->last_cam2base, c2b, sizeof c2b);
         const tsdfk::IntegrateParams q = make_params(v, depth_dev, masks_dev ? masks_dev[i] : nullptr, c2b, 4);
-        b->h_params[s][i] = q;
-        pose_from_params(b->h_poses[s][i], q);
+        h_params[i] = q;
+        pose_from_params(h_poses[i], q);
         v->flags_known_zero = false;           // the batched kernel maintains the summary
     }
     // Instance masks given: every object sees only its own instance (ref: src/Engine.cpp:192-193), so most workgroups of
@@ -2082,9 +2024,9 @@ int tsdf_batch_integrate_device(tsdf_batch *b, const float *depth_dev, const uin
     for (tsdf_volume *v : b->vols) launch_voxels += v->n_vox;
     // ... when the launch is large enough, and not for many small volumes (tsdf_host::batch_classifies)
     const bool classify = any_mask && same_range && tsdf_host::batch_classifies(variant_of(b->vols[0]->variant).classify, n, launch_voxels) &&
-                          tiles_fit(b->h_params[s][0].tiles_w, b->h_params[s][0].tiles_h);
+                          tiles_fit(h_params[0].tiles_w, h_params[0].tiles_h);
     if (classify) {
-        const size_t per = tsdf_host::tile_table_elems(b->h_params[s][0].tiles_w, b->h_params[s][0].tiles_h);
+        const size_t per = tsdf_host::tile_table_elems(h_params[0].tiles_w, h_params[0].tiles_h);
         if (!b->d_tiles) {      // (and, in the measurement build, the class table beside them: both or neither)
             DevPtr<float2> tiles;
             DevPtr<uint8_t> wg_class;
@@ -2094,30 +2036,30 @@ int tsdf_batch_integrate_device(tsdf_batch *b, const float *depth_dev, const uin
             b->tiles_per_object = per;
         }
         std::vector<const float *> depths((size_t)n, depth_dev);
-        int rc = build_tile_tables(b->stream, b->vols[0]->cfg, b->h_params[s][0], depths.data(), masks_dev, n, b->d_tiles);
+        int rc = build_tile_tables(b->stream, b->vols[0]->cfg, h_params[0], depths.data(), masks_dev, n, b->d_tiles);
         if (rc) return rc;
-        for (int i = 0; i < n; ++i) b->h_poses[s][i].tiles = b->d_tiles + (size_t)i * per;
+        for (int i = 0; i < n; ++i) h_poses[i].tiles = b->d_tiles + (size_t)i * per;
     }
-    HIP_TRY(hipMemcpyAsync(b->d_params[s], b->h_params[s], n * sizeof(tsdfk::IntegrateParams), hipMemcpyHostToDevice, b->stream));
-    HIP_TRY(hipMemcpyAsync(b->d_poses[s], b->h_poses[s], n * sizeof(tsdfk::FramePose), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(d_params, h_params, n * sizeof(tsdfk::IntegrateParams), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(d_poses, h_poses, n * sizeof(tsdfk::FramePose), hipMemcpyHostToDevice, b->stream));
     dim3 block(64, 4, 1), grid(b->max_blocks, 1, b->total_slices);
     // a class per wavefront brick (every member has a brick view: dim_x % 4 == 0 is a condition of tsdf_batch_create)
     int brick_blocks = 0;
     bool bricks = classify && !(kExperiments && b->vols[0]->variant == 11);
     for (int i = 0; i < n && bricks; ++i) {
-        const tsdfk::IntegrateParams &q = b->h_params[s][i];
+        const tsdfk::IntegrateParams &q = h_params[i];
         bricks = q.brick_q > 0;
         brick_blocks = std::max(brick_blocks, (q.brick_groups * q.bricks_per_group + 3) / 4);
     }
     if (bricks) {
         // z index of the brick launches: slice groups (rebuilt when a member's brick depth changed: tsdf_set_brick_shape)
         bool same = b->d_group_map != nullptr && (int)b->group_s.size() == n;
-        for (int i = 0; i < n && same; ++i) same = b->group_s[i] == b->h_params[s][i].brick_s;
+        for (int i = 0; i < n && same; ++i) same = b->group_s[i] == h_params[i].brick_s;
         if (!same) {
             std::vector<int2> gmap;
             b->group_s.assign((size_t)n, 1);
             for (int i = 0; i < n; ++i) {
-                const tsdfk::IntegrateParams &q = b->h_params[s][i];
+                const tsdfk::IntegrateParams &q = h_params[i];
                 b->group_s[i] = q.brick_s;
                 for (int g = 0; g < (q.nz + q.brick_s - 1) / q.brick_s; ++g) gmap.push_back(make_int2(i, g));
             }
@@ -2127,30 +2069,25 @@ int tsdf_batch_integrate_device(tsdf_batch *b, const float *depth_dev, const uin
             b->total_groups = (int)gmap.size();
         }
         const size_t n_bricks = (size_t)brick_blocks * b->total_groups * 4;
-        if (b->brick_class_bytes < n_bricks) {
-            b->brick_class_bytes = 0;
-            HIP_TRY(dev_alloc(b->d_brick_class, n_bricks));
-            b->brick_class_bytes = n_bricks;
-        }
+        HIP_TRY(b->d_brick_class.ensure(n_bricks));
         hipLaunchKernelGGL(tsdfk::classify_bricks_batched, dim3((unsigned)((n_bricks + 255) / 256)), dim3(256), 0, b->stream,
-                           b->d_params[s], b->d_poses[s], b->d_group_map, b->d_brick_class, brick_blocks, b->total_groups);
+                           d_params, d_poses, b->d_group_map, b->d_brick_class, brick_blocks, b->total_groups);
         hipLaunchKernelGGL((tsdfk::integrate_multi_batched_bricks<kBrickNT>), dim3(brick_blocks, 1, b->total_groups), block, 0, b->stream,
-                           b->d_params[s], b->d_poses[s], b->d_group_map, b->d_brick_class);
+                           d_params, d_poses, b->d_group_map, b->d_brick_class);
 #ifdef TSDF_EXPERIMENTS
     } else if (classify) {   // variant 11: a class per 1024-voxel workgroup patch (round 2a's shape)
         const size_t n_wg = (size_t)b->max_blocks * b->total_slices;
         hipLaunchKernelGGL(tsdfk::classify_workgroups_batched, dim3((unsigned)((n_wg + 255) / 256)), dim3(256), 0, b->stream,
-                           b->d_params[s], b->d_poses[s], b->d_slice_map, b->d_wg_class, b->max_blocks, b->total_slices);
-        hipLaunchKernelGGL((tsdfk::integrate_multi_batched_cls<true, true>), grid, block, 0, b->stream, b->d_params[s], b->d_poses[s],
+                           d_params, d_poses, b->d_slice_map, b->d_wg_class, b->max_blocks, b->total_slices);
+        hipLaunchKernelGGL((tsdfk::integrate_multi_batched_cls<true, true>), grid, block, 0, b->stream, d_params, d_poses,
                            b->d_slice_map, b->d_wg_class);
 #endif
     } else {
-        hipLaunchKernelGGL((tsdfk::integrate_multi_batched<true>), grid, block, 0, b->stream, b->d_params[s], b->d_poses[s],
+        hipLaunchKernelGGL((tsdfk::integrate_multi_batched<true>), grid, block, 0, b->stream, d_params, d_poses,
                            b->d_slice_map);
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(b->slot_done[s], b->stream));
-    b->slot_used[s] = true;
+    HIP_TRY(b->blocks.consumed(s, b->stream));
     return TSDF_OK;
 }
 
@@ -2173,8 +2110,7 @@ static int surface_pass(tsdf_volume *v, float weight_thresh, float *xyz_host, in
     size_t off_offsets = ((size_t)n_chunks * sizeof(uint32_t) + 255) & ~(size_t)255;
     size_t off_total = off_offsets + (size_t)n_chunks * sizeof(int64_t);
     size_t need = off_total + 256;
-    rc = ensure_scratch(v, need);
-    if (rc) return rc;
+    HIP_TRY(v->d_scratch.ensure(need));
     char *s = (char *)v->d_scratch;
     uint32_t *d_counts = (uint32_t *)(s + off_counts);
     int64_t *d_offsets = (int64_t *)(s + off_offsets);
@@ -2192,8 +2128,7 @@ static int surface_pass(tsdf_volume *v, float weight_thresh, float *xyz_host, in
     if ((!xyz_host && !keep_on_device) || capacity <= 0 || total == 0) return TSDF_OK;
 
     int64_t n_out = total < capacity ? total : capacity;
-    rc = ensure_list(v, (size_t)total * 3 * sizeof(float));
-    if (rc) return rc;
+    HIP_TRY(v->d_list.ensure((size_t)total * 3 * sizeof(float)));
     float *d_xyz = reinterpret_cast<float *>(v->d_list.get());
     const tsdf_config &c = v->cfg;
     hipLaunchKernelGGL(tsdfx::surface_emit, dim3((unsigned)n_chunks), dim3(256), 0, v->stream,
@@ -2240,8 +2175,7 @@ static int crossing_pass(tsdf_volume *v, const float *halo_tsdf, const float *ha
     size_t off_offsets = ((size_t)n_chunks * sizeof(uint32_t) + 255) & ~(size_t)255;
     size_t off_total = off_offsets + (size_t)n_chunks * sizeof(int64_t);
     size_t off_halo = (off_total + 256 + 255) & ~(size_t)255;
-    rc = ensure_scratch(v, off_halo + 2 * slice * sizeof(float));
-    if (rc) return rc;
+    HIP_TRY(v->d_scratch.ensure(off_halo + 2 * slice * sizeof(float)));
     char *s = (char *)v->d_scratch;
     uint32_t *d_counts = (uint32_t *)s;
     int64_t *d_offsets = (int64_t *)(s + off_offsets);
@@ -2267,8 +2201,7 @@ static int crossing_pass(tsdf_volume *v, const float *halo_tsdf, const float *ha
     *count = total;
     if (!xyz_host || capacity <= 0 || total == 0) return TSDF_OK;
     const int64_t n_out = total < capacity ? total : capacity;
-    rc = ensure_list(v, (size_t)total * item_floats * sizeof(float));
-    if (rc) return rc;
+    HIP_TRY(v->d_list.ensure((size_t)total * item_floats * sizeof(float)));
     float *d_xyz = reinterpret_cast<float *>(v->d_list.get());
     if (mesh) hipLaunchKernelGGL(tsdfx::mesh_emit_kernel, dim3((unsigned)n_chunks), dim3(256), 0, v->stream, g, d_offsets, d_xyz);
     else hipLaunchKernelGGL(tsdfx::crossing_emit, dim3((unsigned)n_chunks), dim3(256), 0, v->stream, g, d_offsets, d_xyz);
@@ -2505,995 +2438,12 @@ int tsdf_load_state(tsdf_volume *v, const char *path)
     return tsdf_upload(v, t.data(), w.data());
 }
 
-// ---------------------------------------------------------------------------------------------
-// raycasting (csrc/tsdf_raycast.hip.h states the rule)
-// ---------------------------------------------------------------------------------------------
-static int ray_params_ok(const char *who, const tsdf_raycast_params *p)
-{
-    if (!p) return fail(TSDF_ERR_INVALID, "%s: NULL parameters", who);
-    for (int i = 0; i < 9; ++i)
-        if (!std::isfinite(p->cam_K[i])) return fail(TSDF_ERR_INVALID, "%s: cam_K[%d] is not finite", who, i);
-    if (p->cam_K[0] == 0.0f || p->cam_K[4] == 0.0f) return fail(TSDF_ERR_INVALID, "%s: fx and fy must be non-zero", who);
-    if (p->im_height <= 0 || p->im_width <= 0 || (p->im_height + 15) / 16 > 65535 ||
-        (int64_t)p->im_height * p->im_width > (int64_t)1 << 30)
-        return fail(TSDF_ERR_INVALID, "%s: bad image size %dx%d", who, p->im_height, p->im_width);
-    if (!std::isfinite(p->near_m) || !std::isfinite(p->far_m) || !(p->near_m >= 0.0f) || !(p->near_m < p->far_m))
-        return fail(TSDF_ERR_INVALID, "%s: need 0 <= near < far, both finite (near %g, far %g)", who, (double)p->near_m,
-                    (double)p->far_m);
-    return TSDF_OK;
-}
-
-static int ray_volume_ok(const char *who, const tsdf_volume *v)
-{
-    const tsdf_config &c = v->cfg;
-    if (c.z_begin != 0 || c.z_end != c.dim_z)
-        return fail(TSDF_ERR_INVALID, "%s: the handle is the z-slab [%d,%d) of %d slices; raycasting needs a whole-grid handle",
-                    who, c.z_begin, c.z_end, c.dim_z);
-    if (c.dim_x < 2 || c.dim_y < 2 || c.dim_z < 2)
-        return fail(TSDF_ERR_INVALID, "%s: every dim must be >= 2 (%d,%d,%d)", who, c.dim_x, c.dim_y, c.dim_z);
-    return TSDF_OK;
-}
-
-// The volume as the march sees it, under the relative pose c2b (host float32 arithmetic: go and s_free are part of the rule).
-static tsdfk::RayVolume ray_volume(const tsdf_volume *v, const float c2b[16])
-{
-    const tsdf_config &c = v->cfg;
-    tsdfk::RayVolume V;
-    V.tsdf = v->d_tsdf;
-    V.weight = v->d_weight;
-    const int dims[3] = {c.dim_x, c.dim_y, c.dim_z};
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) V.r[3 * i + j] = c2b[4 * i + j];
-        V.go[i] = (c2b[4 * i + 3] - c.origin[i]) / c.voxel_size;
-        V.hi[i] = (float)(dims[i] - 1);
-        V.dim[i] = dims[i];
-    }
-    V.vs = c.voxel_size;
-    V.s_free = 0.8f * c.trunc_margin;
-    V.max_steps = (int)std::min<int64_t>(2 * ((int64_t)c.dim_x + c.dim_y + c.dim_z) + 8, INT32_MAX);
-    return V;
-}
-
-extern "C++" template <typename P>
-static void ray_camera(P &k, const tsdf_raycast_params *p)
-{
-    k.fx = p->cam_K[0]; k.fy = p->cam_K[4]; k.cx = p->cam_K[2]; k.cy = p->cam_K[5];
-    k.near_m = p->near_m; k.far_m = p->far_m; k.wthr = p->weight_thresh;
-    k.H = p->im_height; k.W = p->im_width;
-}
-
-static dim3 ray_grid(const tsdf_raycast_params *p) { return dim3((p->im_width + 15) / 16, (p->im_height + 15) / 16); }
-
-static int raycast_checks(const char *who, tsdf_volume *v, const tsdf_raycast_params *p, const float *cam2world, bool any_out,
-                          bool want_label, bool want_colour)
-{
-    if (!v || !cam2world) return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
-    if (!any_out) return fail(TSDF_ERR_INVALID, "%s: every output is NULL", who);
-    int rc = ray_params_ok(who, p);
-    if (rc == TSDF_OK) rc = ray_volume_ok(who, v);
-    if (rc) return rc;
-    if (want_label && !v->d_label) return fail(TSDF_ERR_INVALID, "%s: a label image needs tsdf_labels_enable", who);
-    if (want_colour && !v->d_colour) return fail(TSDF_ERR_INVALID, "%s: a colour image needs tsdf_colour_enable", who);
-    return bind_device(v);   // the collected frames first
-}
-
-static int launch_raycast(tsdf_volume *v, const tsdf_raycast_params *p, const float cam2world[16], float *depth, float *normal,
-                          uint16_t *label, uint32_t *colour)
-{
-    float c2b[16];
-    compose_cam2base(v, cam2world, c2b);
-    tsdfk::RaycastParams k;
-    k.vol = ray_volume(v, c2b);
-    k.label = v->d_label; k.colour = v->d_colour;
-    k.depth = depth; k.normal = normal; k.label_out = label; k.colour_out = colour;
-    ray_camera(k, p);
-    hipLaunchKernelGGL(tsdfk::raycast_volume, ray_grid(p), dim3(256), 0, v->stream, k);
-    HIP_TRY(hipGetLastError());
-    return TSDF_OK;
-}
-
-int tsdf_raycast_params_default(const tsdf_config *cfg, tsdf_raycast_params *out)
-{
-    if (!cfg || !out) return fail(TSDF_ERR_INVALID, "tsdf_raycast_params_default: NULL argument");
-    std::memcpy(out->cam_K, cfg->cam_K, sizeof out->cam_K);
-    out->im_height = cfg->im_height;
-    out->im_width = cfg->im_width;
-    out->near_m = 0.0f;
-    out->far_m = cfg->max_depth;
-    out->weight_thresh = 0.9f;
-    return TSDF_OK;
-}
-
-int tsdf_raycast_device(tsdf_volume *v, const tsdf_raycast_params *p, const float cam2world[16], float *depth_dev,
-                        float *normal_dev, uint16_t *label_dev, uint32_t *colour_dev)
-{
-    int rc = raycast_checks("tsdf_raycast_device", v, p, cam2world, depth_dev || normal_dev || label_dev || colour_dev,
-                            label_dev != nullptr, colour_dev != nullptr);
-    if (rc) return rc;
-    return launch_raycast(v, p, cam2world, depth_dev, normal_dev, label_dev, colour_dev);
-}
-
-int tsdf_raycast(tsdf_volume *v, const tsdf_raycast_params *p, const float cam2world[16], float *depth_host,
-                 float *normal_host, uint16_t *label_host, uint32_t *colour_host)
-{
-    int rc = raycast_checks("tsdf_raycast", v, p, cam2world, depth_host || normal_host || label_host || colour_host,
-                            label_host != nullptr, colour_host != nullptr);
-    if (rc) return rc;
-    // the images go through the handle's output list buffer (kept between calls), one copy each, then one wait
-    const size_t px = (size_t)p->im_height * p->im_width;
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t o_n = up(px * 4), o_l = o_n + up(px * 12), o_c = o_l + up(px * 2), bytes = o_c + px * 4;
-    rc = ensure_list(v, bytes);
-    if (rc) return rc;
-    char *base = static_cast<char *>(v->d_list);
-    float *d = depth_host ? reinterpret_cast<float *>(base) : nullptr;
-    float *n = normal_host ? reinterpret_cast<float *>(base + o_n) : nullptr;
-    uint16_t *l = label_host ? reinterpret_cast<uint16_t *>(base + o_l) : nullptr;
-    uint32_t *c = colour_host ? reinterpret_cast<uint32_t *>(base + o_c) : nullptr;
-    rc = launch_raycast(v, p, cam2world, d, n, l, c);
-    if (rc) return rc;
-    if (d) HIP_TRY(hipMemcpyAsync(depth_host, d, px * 4, hipMemcpyDeviceToHost, v->stream));
-    if (n) HIP_TRY(hipMemcpyAsync(normal_host, n, px * 12, hipMemcpyDeviceToHost, v->stream));
-    if (l) HIP_TRY(hipMemcpyAsync(label_host, l, px * 2, hipMemcpyDeviceToHost, v->stream));
-    if (c) HIP_TRY(hipMemcpyAsync(colour_host, c, px * 4, hipMemcpyDeviceToHost, v->stream));
-    HIP_TRY(hipStreamSynchronize(v->stream));
-    return TSDF_OK;
-}
-
-// The checks of a batch render, then the members' collected frames.
-static int batch_render_checks(const char *who, tsdf_batch *b, const tsdf_raycast_params *p)
-{
-    int rc = ray_params_ok(who, p);
-    for (size_t i = 0; i < b->vols.size() && rc == TSDF_OK; ++i) rc = ray_volume_ok(who, b->vols[i]);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(b->device));
-    for (tsdf_volume *v : b->vols) {   // the batch's collected frames, then any a member collected through its own handle
-        rc = bind_device(v);
-        if (rc) return rc;
-    }
-    return TSDF_OK;
-}
-
-// Every member into one image, queued on the batch's stream.
-static int batch_render(tsdf_batch *b, const tsdf_raycast_params *p, const float cam2world[16], float *depth_dev,
-                        float *normal_dev, int32_t *member_dev)
-{
-    const int n = (int)b->vols.size();
-    if (!b->d_ray) {      // all three or none
-        HostPtr<tsdfk::RayVolume> h;
-        DevPtr<tsdfk::RayVolume> d;
-        Event copied;
-        HIP_TRY(host_alloc(h, n * sizeof(tsdfk::RayVolume), hipHostMallocDefault));
-        HIP_TRY(dev_alloc(d, n * sizeof(tsdfk::RayVolume)));
-        HIP_TRY(event_create(copied));
-        b->h_ray = std::move(h); b->d_ray = std::move(d); b->ray_copied = std::move(copied);
-    }
-    if (b->ray_used) HIP_TRY(hipEventSynchronize(b->ray_copied));
-    for (int i = 0; i < n; ++i) {
-        float c2b[16];
-        compose_cam2base(b->vols[i], cam2world, c2b);   // each object has its own base frame (ref: src/Object.cpp:23-29)
-        b->h_ray[i] = ray_volume(b->vols[i], c2b);
-    }
-    HIP_TRY(hipMemcpyAsync(b->d_ray, b->h_ray, n * sizeof(tsdfk::RayVolume), hipMemcpyHostToDevice, b->stream));
-    HIP_TRY(hipEventRecord(b->ray_copied, b->stream));
-    b->ray_used = true;
-    tsdfk::BatchRaycastParams k;
-    k.members = b->d_ray;
-    k.n = n;
-    k.depth = depth_dev; k.normal = normal_dev; k.member = member_dev;
-    ray_camera(k, p);
-    hipLaunchKernelGGL(tsdfk::raycast_batch, ray_grid(p), dim3(256), 0, b->stream, k);
-    HIP_TRY(hipGetLastError());
-    return TSDF_OK;
-}
-
-int tsdf_batch_raycast_device(tsdf_batch *b, const tsdf_raycast_params *p, const float cam2world[16], float *depth_dev,
-                              float *normal_dev, int32_t *member_dev)
-{
-    const char *who = "tsdf_batch_raycast_device";
-    if (!b || !cam2world) return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
-    if (!depth_dev && !normal_dev && !member_dev) return fail(TSDF_ERR_INVALID, "%s: every output is NULL", who);
-    int rc = batch_render_checks(who, b, p);
-    if (rc) return rc;
-    return batch_render(b, p, cam2world, depth_dev, normal_dev, member_dev);
-}
-
-// ---------------------------------------------------------------------------------------------
-// tracking (csrc/tsdf_track.hip.h states the rule)
-// ---------------------------------------------------------------------------------------------
-static int track_params_ok(const char *who, const tsdf_track_params *p)
-{
-    if (!p) return fail(TSDF_ERR_INVALID, "%s: NULL parameters", who);
-    int rc = ray_params_ok(who, &p->ray);
-    if (rc) return rc;
-    if (p->n_levels < 1 || p->n_levels > 3) return fail(TSDF_ERR_INVALID, "%s: n_levels %d is outside 1..3", who, p->n_levels);
-    for (int l = 0; l < p->n_levels; ++l) {
-        if (p->iters[l] < 0) return fail(TSDF_ERR_INVALID, "%s: iters[%d] = %d is negative", who, l, p->iters[l]);
-        if (!(std::isfinite(p->dist_thresh[l]) && p->dist_thresh[l] > 0.0f))
-            return fail(TSDF_ERR_INVALID, "%s: dist_thresh[%d] must be finite and > 0 (%g)", who, l, (double)p->dist_thresh[l]);
-    }
-    if (!(p->cos_normal_thresh >= -1.0f && p->cos_normal_thresh <= 1.0f))
-        return fail(TSDF_ERR_INVALID, "%s: cos_normal_thresh must lie in [-1, 1] (%g)", who, (double)p->cos_normal_thresh);
-    if (p->min_inliers < 0) return fail(TSDF_ERR_INVALID, "%s: min_inliers %d is negative", who, p->min_inliers);
-    if (!(std::isfinite(p->eps_rot) && p->eps_rot > 0.0f && std::isfinite(p->eps_trans) && p->eps_trans > 0.0f))
-        return fail(TSDF_ERR_INVALID, "%s: eps_rot and eps_trans must be finite and > 0 (%g, %g)", who, (double)p->eps_rot,
-                    (double)p->eps_trans);
-    return TSDF_OK;
-}
-
-static int track_checks(const char *who, tsdf_volume *v, const tsdf_track_params *p, const float *depth_dev,
-                        const float *pose, const void *out)
-{
-    if (!v || !pose) return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
-    if (!depth_dev) return fail(TSDF_ERR_INVALID, "%s: NULL depth frame", who);
-    if (!out) return fail(TSDF_ERR_INVALID, "%s: NULL result", who);
-    int rc = track_params_ok(who, p);
-    if (rc == TSDF_OK) rc = ray_volume_ok(who, v);
-    if (rc) return rc;
-    if (v->group_owner) return fail(TSDF_ERR_INVALID, "%s: the handle is a slab of a tsdf_group; tracking needs a whole-grid handle", who);
-    return bind_device(v);   // the collected frames first
-}
-
-// The scratch block: model depth | model normal | partial rows | state (kept on the handle, grown with the image).
-struct TrackScratch {
-    float *depth, *normal;
-    double *partials;
-    tsdfk::TrackState *state;
-};
-
-static int track_scratch(tsdf_volume *v, const tsdf_track_params *p, TrackScratch *sc)
-{
-    const size_t px = (size_t)p->ray.im_height * p->ray.im_width;
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t o_n = up(px * 4), o_p = o_n + up(px * 12), o_s = o_p + up(sizeof(double) * tsdfk::kTrackMaxBlocks * tsdfk::kTrackTerms);
-    const size_t bytes = o_s + sizeof(tsdfk::TrackState);
-    if (!v->h_track) HIP_TRY(host_alloc(v->h_track, sizeof(tsdfk::TrackState), hipHostMallocDefault));
-    if (v->track_bytes < bytes) {
-        v->track_bytes = 0;
-        HIP_TRY(dev_alloc(v->d_track, bytes));
-        v->track_bytes = bytes;
-    }
-    char *base = v->d_track;
-    sc->depth = reinterpret_cast<float *>(base);
-    sc->normal = reinterpret_cast<float *>(base + o_n);
-    sc->partials = reinterpret_cast<double *>(base + o_p);
-    sc->state = reinterpret_cast<tsdfk::TrackState *>(base + o_s);
-    return TSDF_OK;
-}
-
-// M = C_ref^-1 * C_cur with the rigid inverse, in double from the float32 entries (the rule's "Poses").
-static void track_relative(const float cr[16], const float cc[16], double M[12])
-{
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j)
-            M[4 * i + j] = ((double)cr[i] * (double)cc[j] + (double)cr[4 + i] * (double)cc[4 + j]) +
-                           (double)cr[8 + i] * (double)cc[8 + j];
-        M[4 * i + 3] = ((double)cr[i] * ((double)cc[3] - (double)cr[3]) + (double)cr[4 + i] * ((double)cc[7] - (double)cr[7])) +
-                       (double)cr[8 + i] * ((double)cc[11] - (double)cr[11]);
-    }
-}
-
-static tsdfk::TrackState track_initial(const double M[12])
-{
-    tsdfk::TrackState s = {};
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 4; ++j) s.M[4 * i + j] = M[4 * i + j];
-        for (int j = 0; j < 3; ++j) s.Rm[3 * i + j] = (float)M[4 * i + j];
-        s.tm[i] = (float)M[4 * i + 3];
-    }
-    return s;
-}
-
-// The render at ref_cam2world and the initial state, queued on the handle's stream.
-static int track_begin(tsdf_volume *v, const tsdf_track_params *p, const TrackScratch &sc, const float ref_cam2world[16],
-                       const double M[12])
-{
-    int rc = launch_raycast(v, &p->ray, ref_cam2world, sc.depth, sc.normal, nullptr, nullptr);
-    if (rc) return rc;
-    hipLaunchKernelGGL(tsdfk::track_init, dim3(1), dim3(64), 0, v->stream, sc.state, track_initial(M));
-    HIP_TRY(hipGetLastError());
-    return TSDF_OK;
-}
-
-// One iteration of level l: the association pass and the solve (system_only: the summed system, no step).
-static int track_iteration(tsdf_volume *v, const tsdf_track_params *p, const TrackScratch &sc, const float *depth_dev,
-                           const uint8_t *mask_dev, int level, bool system_only)
-{
-    const int s = 1 << level, W = p->ray.im_width, H = p->ray.im_height;
-    tsdfk::TrackPairsParams k;
-    k.depth = depth_dev; k.mask = mask_dev; k.model_depth = sc.depth; k.model_normal = sc.normal;
-    k.state = sc.state; k.partials = sc.partials;
-    k.fx = p->ray.cam_K[0]; k.fy = p->ray.cam_K[4]; k.cx = p->ray.cam_K[2]; k.cy = p->ray.cam_K[5];
-    k.near_m = p->ray.near_m; k.far_m = p->ray.far_m;
-    k.dist2 = p->dist_thresh[level] * p->dist_thresh[level];
-    k.cos_thresh = p->cos_normal_thresh;
-    k.H = H; k.W = W; k.s = s; k.level = level;
-    k.ni = W > s ? (W - 1 - s) / s + 1 : 0;
-    k.nj = H > s ? (H - 1 - s) / s + 1 : 0;
-    const int64_t n = (int64_t)k.ni * k.nj;
-    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, tsdfk::kTrackMaxBlocks));
-    hipLaunchKernelGGL(tsdfk::track_pairs, dim3(nb), dim3(256), 0, v->stream, k);
-    HIP_TRY(hipGetLastError());
-    tsdfk::TrackSolveParams q;
-    q.state = sc.state; q.partials = sc.partials; q.n_rows = nb; q.level = level; q.min_inliers = p->min_inliers;
-    q.system_only = system_only ? 1 : 0;
-    q.eps_rot = p->eps_rot; q.eps_trans = p->eps_trans;
-    hipLaunchKernelGGL(tsdfk::track_solve, dim3(1), dim3(256), 0, v->stream, q);
-    HIP_TRY(hipGetLastError());
-    return TSDF_OK;
-}
-
-static int track_fetch(tsdf_volume *v, const TrackScratch &sc)
-{
-    HIP_TRY(hipMemcpyAsync(v->h_track.get(), sc.state, sizeof(tsdfk::TrackState), hipMemcpyDeviceToHost, v->stream));
-    HIP_TRY(hipStreamSynchronize(v->stream));
-    return TSDF_OK;
-}
-
-int tsdf_track_params_default(const tsdf_config *cfg, tsdf_track_params *out)
-{
-    if (!cfg || !out) return fail(TSDF_ERR_INVALID, "tsdf_track_params_default: NULL argument");
-    int rc = tsdf_raycast_params_default(cfg, &out->ray);
-    if (rc) return rc;
-    out->n_levels = 3;
-    out->iters[0] = 10; out->iters[1] = 5; out->iters[2] = 4;
-    for (int l = 0; l < 3; ++l) out->dist_thresh[l] = 0.10f;
-    out->cos_normal_thresh = (float)std::cos(20.0 * M_PI / 180.0);
-    out->min_inliers = 300;
-    out->eps_rot = 1e-5f;
-    out->eps_trans = 1e-5f;
-    return TSDF_OK;
-}
-
-int tsdf_track(tsdf_volume *v, const tsdf_track_params *p, const float *depth_dev, const uint8_t *mask_dev,
-               const float guess_cam2world[16], tsdf_track_result *out)
-{
-    const char *who = "tsdf_track";
-    int rc = track_checks(who, v, p, depth_dev, guess_cam2world, out);
-    if (rc) return rc;
-    TrackScratch sc;
-    rc = track_scratch(v, p, &sc);
-    if (rc) return rc;
-    const double eye[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    rc = track_begin(v, p, sc, guess_cam2world, eye);
-    for (int l = p->n_levels - 1; l >= 0 && rc == TSDF_OK; --l)
-        for (int it = 0; it < p->iters[l] && rc == TSDF_OK; ++it) rc = track_iteration(v, p, sc, depth_dev, mask_dev, l, false);
-    if (rc == TSDF_OK) rc = track_fetch(v, sc);
-    if (rc) return rc;
-    const tsdfk::TrackState &st = *v->h_track.get();
-    std::memset(out, 0, sizeof *out);
-    for (int l = 0; l < 3; ++l) out->iters_run[l] = st.iters_run[l];
-    out->inliers = st.inliers;
-    out->rmse = st.inliers > 0 ? (float)std::sqrt(st.r2 / (double)st.inliers) : 0.0f;
-    if (st.lost) {
-        out->status = 2;
-        std::memcpy(out->cam2world, guess_cam2world, sizeof out->cam2world);
-        return TSDF_OK;
-    }
-    int last = -1;                         // the finest level that ran
-    for (int l = p->n_levels - 1; l >= 0; --l)
-        if (p->iters[l] > 0) last = l;
-    out->status = last >= 0 && st.done[last] ? 0 : 1;
-    // cam2world = (base2world * C_ref) * M, double, sums over k left to right
-    float cr[16];
-    compose_cam2base(v, guess_cam2world, cr);
-    const float *bw = v->cfg.base2world;
-    double X[16];
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) {
-            double acc = (double)bw[4 * i] * (double)cr[j];
-            for (int k = 1; k < 4; ++k) acc = acc + (double)bw[4 * i + k] * (double)cr[4 * k + j];
-            X[4 * i + j] = acc;
-        }
-    double M4[16] = {};
-    for (int k = 0; k < 12; ++k) M4[k] = st.M[k];
-    M4[15] = 1.0;
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) {
-            double acc = X[4 * i] * M4[j];
-            for (int k = 1; k < 4; ++k) acc = acc + X[4 * i + k] * M4[4 * k + j];
-            out->cam2world[4 * i + j] = (float)acc;
-        }
-    return TSDF_OK;
-}
-
-int tsdf_track_system(tsdf_volume *v, const tsdf_track_params *p, const float *depth_dev, const uint8_t *mask_dev,
-                      const float ref_cam2world[16], const float cam2world[16], int32_t level, double system_out[29])
-{
-    const char *who = "tsdf_track_system";
-    if (!cam2world) return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
-    if (p && (level < 0 || level >= p->n_levels))
-        return fail(TSDF_ERR_INVALID, "%s: level %d is outside [0, n_levels = %d)", who, level, p->n_levels);
-    int rc = track_checks(who, v, p, depth_dev, ref_cam2world, system_out);
-    if (rc) return rc;
-    TrackScratch sc;
-    rc = track_scratch(v, p, &sc);
-    if (rc) return rc;
-    float cr[16], cc[16];
-    compose_cam2base(v, ref_cam2world, cr);
-    compose_cam2base(v, cam2world, cc);
-    double M[12];
-    track_relative(cr, cc, M);
-    rc = track_begin(v, p, sc, ref_cam2world, M);
-    if (rc == TSDF_OK) rc = track_iteration(v, p, sc, depth_dev, mask_dev, level, true);
-    if (rc == TSDF_OK) rc = track_fetch(v, sc);
-    if (rc) return rc;
-    std::memcpy(system_out, v->h_track.get()->sys, sizeof(double) * tsdfk::kTrackTerms);
-    return TSDF_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// merging and re-gridding (csrc/tsdf_fuse.hip.h states the rule)
-// ---------------------------------------------------------------------------------------------
-static int fuse_handle_ok(const char *who, const char *side, const tsdf_volume *v)
-{
-    const tsdf_config &c = v->cfg;
-    if (v->group_owner) return fail(TSDF_ERR_INVALID, "%s: %s is a slab of a tsdf_group; merging needs whole-grid handles", who, side);
-    if (c.z_begin != 0 || c.z_end != c.dim_z)
-        return fail(TSDF_ERR_INVALID, "%s: %s is the z-slab [%d,%d) of %d slices; merging needs whole-grid handles", who, side,
-                    c.z_begin, c.z_end, c.dim_z);
-    return TSDF_OK;
-}
-
-int tsdf_fuse_params_default(const tsdf_config *dst_cfg, tsdf_fuse_params *out)
-{
-    if (!dst_cfg || !out) return fail(TSDF_ERR_INVALID, "tsdf_fuse_params_default: NULL argument");
-    out->weight_thresh = 0.9f;
-    out->agree_tol = 0.4f;   // two voxels of the default band of five: a choice
-    out->write = 1;
-    return TSDF_OK;
-}
-
-int tsdf_fuse_volume(tsdf_volume *dst, tsdf_volume *src, const tsdf_fuse_params *p, tsdf_fuse_counts *counts)
-{
-    const char *who = "tsdf_fuse_volume";
-    if (!dst || !src || !p) return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
-    if (dst == src) return fail(TSDF_ERR_INVALID, "%s: dst and src are the same handle", who);
-    int rc = fuse_handle_ok(who, "dst", dst);
-    if (rc == TSDF_OK) rc = fuse_handle_ok(who, "src", src);
-    if (rc) return rc;
-    if (dst->cfg.device != src->cfg.device)
-        return fail(TSDF_ERR_INVALID, "%s: dst is on device %d, src on device %d", who, dst->cfg.device, src->cfg.device);
-    if (!std::isfinite(p->weight_thresh)) return fail(TSDF_ERR_INVALID, "%s: weight_thresh is not finite", who);
-    if (!std::isfinite(p->agree_tol) || !(p->agree_tol > 0.0f))
-        return fail(TSDF_ERR_INVALID, "%s: agree_tol must be finite and > 0 (%g)", who, (double)p->agree_tol);
-    if (p->write != 0 && p->write != 1) return fail(TSDF_ERR_INVALID, "%s: write must be 0 or 1 (%d)", who, p->write);
-    rc = bind_device(dst);               // the collected frames of both, through their batches where they have one
-    if (rc == TSDF_OK) rc = bind_device(src);
-    if (rc) return rc;
-    if (!dst->d_fuse) {                  // all four or none
-        DevPtr<unsigned long long> d;
-        HostPtr<unsigned long long> h;
-        Event ready, done;
-        HIP_TRY(dev_alloc(d, 4 * sizeof(unsigned long long)));
-        HIP_TRY(host_alloc(h, 4 * sizeof(unsigned long long), hipHostMallocDefault));
-        HIP_TRY(event_create(ready));
-        HIP_TRY(event_create(done));
-        dst->d_fuse = std::move(d); dst->h_fuse = std::move(h);
-        dst->fuse_src_ready = std::move(ready); dst->fuse_done = std::move(done);
-    }
-    const tsdf_config &cd = dst->cfg, &cs = src->cfg;
-    float M[16];
-    tsdf_host::multiply_matrix(src->base2world_inv, cd.base2world, M);
-    tsdfk::FuseParams k;
-    k.dt = dst->d_tsdf; k.dw = dst->d_weight;
-    k.st = src->d_tsdf; k.sw = src->d_weight;
-    for (int i = 0; i < 12; ++i) k.m[i] = M[i];
-    const int sd[3] = {cs.dim_x, cs.dim_y, cs.dim_z}, dd[3] = {cd.dim_x, cd.dim_y, cd.dim_z};
-    for (int i = 0; i < 3; ++i) {
-        k.od[i] = cd.origin[i]; k.os[i] = cs.origin[i];
-        k.hi[i] = (float)(sd[i] - 1);
-        k.sdim[i] = sd[i]; k.ddim[i] = dd[i];
-    }
-    k.vsd = cd.voxel_size; k.vss = cs.voxel_size;
-    k.ratio = cs.trunc_margin / cd.trunc_margin;
-    k.wthr = p->weight_thresh; k.tol = p->agree_tol;
-    k.write = p->write;
-    k.counts = dst->d_fuse;
-    HIP_TRY(hipMemsetAsync(dst->d_fuse, 0, 4 * sizeof(unsigned long long), dst->stream));
-    if (src->stream != dst->stream) {    // after everything queued on src's stream so far
-        HIP_TRY(hipEventRecord(dst->fuse_src_ready, src->stream));
-        HIP_TRY(hipStreamWaitEvent(dst->stream, dst->fuse_src_ready, 0));
-    }
-    const int quads = (cd.dim_x + 3) / 4;
-    const dim3 grid((quads + 7) / 8, (cd.dim_y + 7) / 8, (cd.dim_z + 4 * tsdfk::kFuseZRun - 1) / (4 * tsdfk::kFuseZRun));
-    if (cd.dim_x % 4 == 0)
-        hipLaunchKernelGGL(tsdfk::fuse_volume<true>, grid, dim3(256), 0, dst->stream, k);
-    else
-        hipLaunchKernelGGL(tsdfk::fuse_volume<false>, grid, dim3(256), 0, dst->stream, k);
-    HIP_TRY(hipGetLastError());
-    if (src->stream != dst->stream) {    // a later write to src must not overtake the read
-        HIP_TRY(hipEventRecord(dst->fuse_done, dst->stream));
-        HIP_TRY(hipStreamWaitEvent(src->stream, dst->fuse_done, 0));
-    }
-    if (p->write) {                      // later fused / classified Integrate launches must not trust stale summary words
-        rc = rebuild_summary(dst);
-        if (rc) return rc;
-    }
-    HIP_TRY(hipMemcpyAsync(dst->h_fuse.get(), dst->d_fuse, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, dst->stream));
-    HIP_TRY(hipStreamSynchronize(dst->stream));
-    if (counts) {
-        counts->sampled = dst->h_fuse.get()[0];
-        counts->both = dst->h_fuse.get()[1];
-        counts->both_band = dst->h_fuse.get()[2];
-        counts->agree_band = dst->h_fuse.get()[3];
-    }
-    return TSDF_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// association (csrc/tsdf_associate.hip.h states the counting rule, include/tsdf_hip.h the assignment)
-// ---------------------------------------------------------------------------------------------
-constexpr int kAssocMaxMembers = 65536;   // keeps the member tiles within the launch's y limit (MT >= 9 at K = 256)
-
-static int assoc_params_ok(const char *who, const tsdf_associate_params *p)
-{
-    if (!p) return fail(TSDF_ERR_INVALID, "%s: NULL parameters", who);
-    int rc = ray_params_ok(who, &p->ray);
-    if (rc) return rc;
-    if (!(std::isfinite(p->depth_tol_m) && p->depth_tol_m > 0.0f))
-        return fail(TSDF_ERR_INVALID, "%s: depth_tol_m must be finite and > 0 (%g)", who, (double)p->depth_tol_m);
-    if (p->min_pixels < 1) return fail(TSDF_ERR_INVALID, "%s: min_pixels %d is below 1", who, p->min_pixels);
-    if (!(p->min_iou >= 0.0f && p->min_iou <= 1.0f))
-        return fail(TSDF_ERR_INVALID, "%s: min_iou must lie in [0, 1] (%g)", who, (double)p->min_iou);
-    if (p->one_to_one != 0 && p->one_to_one != 1)
-        return fail(TSDF_ERR_INVALID, "%s: one_to_one must be 0 or 1 (%d)", who, p->one_to_one);
-    return TSDF_OK;
-}
-
-static int assoc_sizes_ok(const char *who, int32_t k, int32_t n_members)
-{
-    if (k < 1 || k > tsdfk::kAssocMaxMasks)
-        return fail(TSDF_ERR_INVALID, "%s: k = %d masks is outside 1..%d", who, k, tsdfk::kAssocMaxMasks);
-    if (n_members < 1 || n_members > kAssocMaxMembers)
-        return fail(TSDF_ERR_INVALID, "%s: n_members = %d is outside 1..%d", who, n_members, kAssocMaxMembers);
-    return TSDF_OK;
-}
-
-static int assoc_labels_ok(const char *who, const tsdf_associate_labels *l)
-{
-    if (l && (!l->mask_label || !l->mask_score || !l->member_label || !l->member_score))
-        return fail(TSDF_ERR_INVALID, "%s: a label block needs all four arrays", who);
-    return TSDF_OK;
-}
-
-static size_t assoc_words(int K, int M) { return 3 * (size_t)K * M + 3 * (size_t)K + 4 * (size_t)M; }
-
-// Zero the block and count, queued on s.
-static int launch_associate(hipStream_t s, const tsdf_associate_params *p, const int32_t *member, const float *rdepth, int M,
-                            const float *depth, const uint8_t *masks, int K, uint32_t *counts)
-{
-    HIP_TRY(hipMemsetAsync(counts, 0, assoc_words(K, M) * sizeof(uint32_t), s));
-    tsdfk::AssocParams k;
-    k.member = member; k.rdepth = rdepth; k.depth = depth; k.masks = masks; k.counts = counts;
-    k.n_px = (int64_t)p->ray.im_height * p->ray.im_width;
-    k.n_quads = (k.n_px + 3) / 4;
-    k.K = K; k.M = M; k.MT = tsdfk::assoc_tile_members(K, M);
-    k.near_m = p->ray.near_m; k.far_m = p->ray.far_m; k.tol = p->depth_tol_m;
-    const int tiles = (M + k.MT - 1) / k.MT;
-    const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((k.n_quads + 255) / 256, tsdfk::kAssocMaxBlocks));
-    const size_t lds = (3 * (size_t)K * k.MT + 3 * (size_t)K + 4 * (size_t)k.MT) * sizeof(uint32_t);
-    auto aligned = [](const void *q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; };
-    const bool vec = k.n_px % 4 == 0 && aligned(member, 16) && aligned(rdepth, 16) && aligned(depth, 16) && aligned(masks, 4);
-    if (vec)
-        hipLaunchKernelGGL(tsdfk::associate_count<true>, dim3(nb, tiles), dim3(256), lds, s, k);
-    else
-        hipLaunchKernelGGL(tsdfk::associate_count<false>, dim3(nb, tiles), dim3(256), lds, s, k);
-    HIP_TRY(hipGetLastError());
-    return TSDF_OK;
-}
-
-struct AssocCandidate {
-    int k, m;
-    uint64_t a, u;
-};
-
-// a1 / u1 > a2 / u2, exactly (u > 0; the products need up to 65 bits)
-static bool assoc_iou_greater(const AssocCandidate &x, const AssocCandidate &y)
-{
-    return (unsigned __int128)x.a * y.u > (unsigned __int128)y.a * x.u;
-}
-
-// The assignment of include/tsdf_hip.h on a count block (the arguments checked by the caller).
-static int assoc_assign(const char *who, const tsdf_associate_params *p, const uint32_t *counts, int K, int M,
-                        const tsdf_associate_labels *labels, int32_t *assign_out, float *iou_out)
-{
-    const uint32_t *ov = counts, *mask = counts + 3 * (size_t)K * M, *mem = mask + 3 * (size_t)K;
-    for (int k = 0; k < K; ++k)
-        for (int m = 0; m < M; ++m) {
-            const uint32_t a = ov[((size_t)k * M + m) * 3];
-            if (a > mask[3 * k + 1] || a > mem[4 * m])
-                return fail(TSDF_ERR_INVALID, "%s: inconsistent counts: overlap[%d][%d][agree] = %u exceeds mask[%d][1] = %u "
-                            "or member[%d][0] = %u", who, k, m, a, k, mask[3 * k + 1], m, mem[4 * m]);
-        }
-    std::vector<AssocCandidate> cand;
-    for (int k = 0; k < K; ++k)
-        for (int m = 0; m < M; ++m) {
-            const uint64_t a = ov[((size_t)k * M + m) * 3];
-            const uint64_t u = (uint64_t)mask[3 * k + 1] + mem[4 * m] - a;     // >= a: the check above
-            if (a < (uint64_t)p->min_pixels || !((double)a >= (double)p->min_iou * (double)u)) continue;
-            if (labels && !(labels->mask_label[k] == labels->member_label[m] ||
-                            labels->member_score[m] > 1.1f * labels->mask_score[k]))
-                continue;
-            cand.push_back({k, m, a, u});                                      // in (k, m) order
-        }
-    std::vector<const AssocCandidate *> pick(K, nullptr);
-    if (p->one_to_one) {
-        std::stable_sort(cand.begin(), cand.end(), assoc_iou_greater);        // equal IoUs keep (k, m) order
-        std::vector<char> used_m(M, 0);
-        for (const AssocCandidate &c : cand) {
-            if (pick[c.k] || used_m[c.m]) continue;
-            pick[c.k] = &c;
-            used_m[c.m] = 1;
-        }
-    } else {
-        for (const AssocCandidate &c : cand)
-            if (!pick[c.k] || assoc_iou_greater(c, *pick[c.k])) pick[c.k] = &c;   // ties keep the lower m
-    }
-    for (int k = 0; k < K; ++k) {
-        assign_out[k] = pick[k] ? pick[k]->m : -1;
-        iou_out[k] = pick[k] ? (float)((double)pick[k]->a / (double)pick[k]->u) : 0.0f;
-    }
-    return TSDF_OK;
-}
-
-int tsdf_associate_params_default(const tsdf_config *cfg, tsdf_associate_params *out)
-{
-    if (!cfg || !out) return fail(TSDF_ERR_INVALID, "tsdf_associate_params_default: NULL argument");
-    int rc = tsdf_raycast_params_default(cfg, &out->ray);
-    if (rc) return rc;
-    out->depth_tol_m = cfg->trunc_margin;
-    out->min_pixels = 25;
-    out->min_iou = 0.25f;
-    out->one_to_one = 1;
-    return TSDF_OK;
-}
-
-int tsdf_associate_count(int32_t device, const tsdf_associate_params *p, const int32_t *member_dev, const float *rdepth_dev,
-                         int32_t n_members, const float *depth_dev, const uint8_t *masks_dev, int32_t k,
-                         uint32_t *counts_host)
-{
-    const char *who = "tsdf_associate_count";
-    if (!member_dev || !rdepth_dev || !depth_dev || !masks_dev || !counts_host)
-        return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
-    int rc = assoc_params_ok(who, p);
-    if (rc == TSDF_OK) rc = assoc_sizes_ok(who, k, n_members);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(device));
-    // the images may have been produced on a handle's (non-blocking) stream, which the null stream does not order against
-    HIP_TRY(hipDeviceSynchronize());
-    const size_t words = assoc_words(k, n_members);
-    DevPtr<uint32_t> d_counts;
-    HIP_TRY(dev_alloc(d_counts, words * sizeof(uint32_t)));
-    rc = launch_associate(0, p, member_dev, rdepth_dev, n_members, depth_dev, masks_dev, k, d_counts);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(counts_host, d_counts, words * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return TSDF_OK;
-}
-
-int tsdf_associate_assign(const tsdf_associate_params *p, const uint32_t *counts_host, int32_t k, int32_t n_members,
-                          const tsdf_associate_labels *labels, int32_t *assign_out, float *iou_out)
-{
-    const char *who = "tsdf_associate_assign";
-    if (!counts_host || !assign_out || !iou_out) return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
-    int rc = assoc_params_ok(who, p);
-    if (rc == TSDF_OK) rc = assoc_sizes_ok(who, k, n_members);
-    if (rc == TSDF_OK) rc = assoc_labels_ok(who, labels);
-    if (rc) return rc;
-    return assoc_assign(who, p, counts_host, k, n_members, labels, assign_out, iou_out);
-}
-
-int tsdf_batch_associate(tsdf_batch *b, const tsdf_associate_params *p, const float cam2world[16], const float *depth_dev,
-                         const uint8_t *masks_dev, int32_t k, const tsdf_associate_labels *labels, uint32_t *counts_host,
-                         int32_t *assign_out, float *iou_out)
-{
-    const char *who = "tsdf_batch_associate";
-    if (!b || !cam2world || !depth_dev || !masks_dev || !assign_out || !iou_out)
-        return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
-    const int M = (int)b->vols.size();
-    int rc = assoc_params_ok(who, p);
-    if (rc == TSDF_OK) rc = assoc_sizes_ok(who, k, M);
-    if (rc == TSDF_OK) rc = assoc_labels_ok(who, labels);
-    if (rc) return rc;
-    const tsdf_config &c0 = b->vols[0]->cfg;
-    if (p->ray.im_height != c0.im_height || p->ray.im_width != c0.im_width)
-        return fail(TSDF_ERR_INVALID, "%s: the render is %dx%d, the batch's frames %dx%d", who, p->ray.im_width,
-                    p->ray.im_height, c0.im_width, c0.im_height);
-    rc = batch_render_checks(who, b, &p->ray);   // then the collected frames
-    if (rc) return rc;
-    // scratch: member | render depth | counts (kept on the batch, grown with the image and the block)
-    const size_t px = (size_t)p->ray.im_height * p->ray.im_width, words = assoc_words(k, M);
-    auto up = [](size_t n) { return (n + 255) / 256 * 256; };
-    const size_t o_d = up(px * 4), o_c = o_d + up(px * 4), bytes = o_c + words * sizeof(uint32_t);
-    if (b->assoc_bytes < bytes) {
-        b->assoc_bytes = 0;
-        HIP_TRY(dev_alloc(b->d_assoc, bytes));
-        b->assoc_bytes = bytes;
-    }
-    if (b->h_assoc_words < words) {
-        b->h_assoc_words = 0;
-        HIP_TRY(host_alloc(b->h_assoc, words * sizeof(uint32_t), hipHostMallocDefault));
-        b->h_assoc_words = words;
-    }
-    char *base = b->d_assoc;
-    int32_t *member = reinterpret_cast<int32_t *>(base);
-    float *rdepth = reinterpret_cast<float *>(base + o_d);
-    uint32_t *counts = reinterpret_cast<uint32_t *>(base + o_c);
-    rc = batch_render(b, &p->ray, cam2world, rdepth, nullptr, member);
-    if (rc == TSDF_OK) rc = launch_associate(b->stream, p, member, rdepth, M, depth_dev, masks_dev, k, counts);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(b->h_assoc.get(), counts, words * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    if (counts_host) std::memcpy(counts_host, b->h_assoc.get(), words * sizeof(uint32_t));
-    return assoc_assign(who, p, b->h_assoc.get(), k, M, labels, assign_out, iou_out);
-}
-
-// ---------------------------------------------------------------------------------------------
-// geometric segmentation and mask refinement (csrc/tsdf_segment.hip.h states the rule)
-// ---------------------------------------------------------------------------------------------
-constexpr int64_t kSegMaxCountWords = (int64_t)1 << 24;   // C + C * K words of the refinement's count block
-
-struct tsdf_segmenter {
-    int device = 0, H = 0, W = 0;
-    Stream own_stream;
-    hipStream_t stream = nullptr;
-    DevPtr<int4> d_pts;
-    DevPtr<int32_t> d_parent, d_root, d_num, d_cluster, d_total;
-    DevPtr<uint32_t> d_size, d_blocks;
-    DevPtr<uint32_t> d_counts;                  // grown with C + C * K
-    size_t counts_words = 0;
-    HostPtr<uint32_t> h_counts;
-    size_t h_counts_words = 0;
-    HostPtr<int32_t> h_total;
-};
-
-static int seg_image_ok(const char *who, int32_t h, int32_t w)
-{
-    if (h <= 0 || w <= 0 || (h + 15) / 16 > 65535 || (int64_t)h * w > (int64_t)1 << 30)
-        return fail(TSDF_ERR_INVALID, "%s: bad image size %dx%d", who, h, w);
-    return TSDF_OK;
-}
-
-static int seg_params_ok(const char *who, const tsdf_segment_params *p)
-{
-    if (!p) return fail(TSDF_ERR_INVALID, "%s: NULL parameters", who);
-    for (int i = 0; i < 9; ++i)
-        if (!std::isfinite(p->cam_K[i])) return fail(TSDF_ERR_INVALID, "%s: cam_K[%d] is not finite", who, i);
-    if (p->cam_K[0] == 0.0f || p->cam_K[4] == 0.0f) return fail(TSDF_ERR_INVALID, "%s: fx and fy must be non-zero", who);
-    int rc = seg_image_ok(who, p->im_height, p->im_width);
-    if (rc) return rc;
-    if (!std::isfinite(p->near_m) || !std::isfinite(p->far_m) || !(p->near_m >= 0.0f) || !(p->near_m < p->far_m))
-        return fail(TSDF_ERR_INVALID, "%s: need 0 <= near < far, both finite (near %g, far %g)", who, (double)p->near_m,
-                    (double)p->far_m);
-    if (p->far_m > 32.0f) return fail(TSDF_ERR_INVALID, "%s: far_m %g is above 32 m", who, (double)p->far_m);
-    const struct { const char *name; float v; } radii[] = {{"small_radius_m", p->small_radius_m},
-                                                            {"large_radius_m", p->large_radius_m},
-                                                            {"seg_radius_m", p->seg_radius_m}};
-    for (const auto &r : radii)
-        if (!(std::isfinite(r.v) && r.v > 0.0f && r.v <= 32.0f))
-            return fail(TSDF_ERR_INVALID, "%s: %s must be finite, > 0 and <= 32 m (%g)", who, r.name, (double)r.v);
-    if (!(p->small_radius_m < p->large_radius_m))
-        return fail(TSDF_ERR_INVALID, "%s: small_radius_m %g must be below large_radius_m %g", who, (double)p->small_radius_m,
-                    (double)p->large_radius_m);
-    if (!(std::isfinite(p->don_thresh) && p->don_thresh > 0.0f))
-        return fail(TSDF_ERR_INVALID, "%s: don_thresh must be finite and > 0 (%g)", who, (double)p->don_thresh);
-    if (p->min_cluster < 1) return fail(TSDF_ERR_INVALID, "%s: min_cluster %d is below 1", who, p->min_cluster);
-    if (p->max_cluster < p->min_cluster)
-        return fail(TSDF_ERR_INVALID, "%s: max_cluster %d is below min_cluster %d", who, p->max_cluster, p->min_cluster);
-    if (!(p->overlap > 0.0f && p->overlap <= 1.0f))
-        return fail(TSDF_ERR_INVALID, "%s: overlap must lie in (0, 1] (%g)", who, (double)p->overlap);
-    if (p->inset < 0 || p->inset > tsdfk::kSegMaxInset)
-        return fail(TSDF_ERR_INVALID, "%s: inset %d is outside 0..%d", who, p->inset, tsdfk::kSegMaxInset);
-    return TSDF_OK;
-}
-
-static int seg_handle_ok(const char *who, const tsdf_segmenter *s, const tsdf_segment_params *p)
-{
-    if (p->im_height != s->H || p->im_width != s->W)
-        return fail(TSDF_ERR_INVALID, "%s: the parameters' image is %dx%d, the segmenter's %dx%d", who, p->im_width, p->im_height,
-                    s->W, s->H);
-    return TSDF_OK;
-}
-
-static tsdfk::SegCamera seg_camera(const tsdf_segment_params *p)
-{
-    tsdfk::SegCamera k;
-    k.fx = p->cam_K[0]; k.fy = p->cam_K[4]; k.cx = p->cam_K[2]; k.cy = p->cam_K[5];
-    k.near_m = p->near_m; k.far_m = p->far_m; k.H = p->im_height; k.W = p->im_width;
-    return k;
-}
-
-// DoN, labelling and numbering queued on the segmenter's stream; *n_clusters on the host when it returns.
-static int seg_depth(tsdf_segmenter *s, const tsdf_segment_params *p, const float *depth, float *don, int32_t *cluster,
-                     int32_t *n_clusters)
-{
-    const int64_t n_px = (int64_t)s->H * s->W;
-    const int nb = (int)((n_px + 255) / 256);
-    const tsdfk::SegCamera k = seg_camera(p);
-    hipStream_t st = s->stream;
-    hipLaunchKernelGGL(tsdfk::seg_backproject, dim3(nb), dim3(256), 0, st, k, depth, s->d_pts.get());
-    hipLaunchKernelGGL(tsdfk::seg_don, dim3((s->W + 15) / 16, (s->H + 15) / 16), dim3(256), 0, st, k, s->d_pts.get(),
-                       p->small_radius_m, p->large_radius_m, p->don_thresh, don, s->d_parent.get());
-    const int64_t Rs = (int64_t)std::rint(p->seg_radius_m * 8192.0f);
-    hipLaunchKernelGGL(tsdfk::seg_merge, dim3(nb), dim3(256), 0, st, s->H, s->W, s->d_pts.get(), Rs * Rs, s->d_parent.get());
-    HIP_TRY(hipMemsetAsync(s->d_size, 0, (size_t)n_px * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(tsdfk::seg_root_size, dim3(nb), dim3(256), 0, st, n_px, s->d_parent.get(), s->d_root.get(), s->d_size.get());
-    const uint32_t lo = (uint32_t)p->min_cluster, hi = (uint32_t)p->max_cluster;
-    hipLaunchKernelGGL(tsdfk::seg_block_count, dim3(nb), dim3(256), 0, st, n_px, s->d_root.get(), s->d_size.get(), lo, hi,
-                       s->d_blocks.get());
-    hipLaunchKernelGGL(tsdfk::seg_scan_blocks, dim3(1), dim3(1024), 0, st, s->d_blocks.get(), nb, s->d_total.get());
-    hipLaunchKernelGGL(tsdfk::seg_number, dim3(nb), dim3(256), 0, st, n_px, s->d_root.get(), s->d_size.get(), lo, hi,
-                       s->d_blocks.get(), s->d_num.get());
-    hipLaunchKernelGGL(tsdfk::seg_label, dim3(nb), dim3(256), 0, st, n_px, s->d_root.get(), s->d_size.get(), lo, hi,
-                       s->d_num.get(), cluster);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(s->h_total.get(), s->d_total.get(), sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *n_clusters = *s->h_total.get();
-    return TSDF_OK;
-}
-
-static int seg_refine(const char *who, tsdf_segmenter *s, const tsdf_segment_params *p, const int32_t *cluster, int32_t C,
-                      const uint8_t *masks, int32_t K, uint8_t *out, uint32_t *counts_host)
-{
-    const int64_t n_px = (int64_t)s->H * s->W;
-    const int64_t words = (int64_t)C + (int64_t)C * K;
-    if (words > kSegMaxCountWords)
-        return fail(TSDF_ERR_INVALID, "%s: %d clusters under %d masks need a count block of %lld words, above %lld", who, C, K,
-                    (long long)words, (long long)kSegMaxCountWords);
-    const size_t need = (size_t)std::max<int64_t>(words, 1);
-    if (s->counts_words < need) {
-        s->counts_words = 0;
-        HIP_TRY(dev_alloc(s->d_counts, need * sizeof(uint32_t)));
-        s->counts_words = need;
-    }
-    if (counts_host && s->h_counts_words < need) {
-        s->h_counts_words = 0;
-        HIP_TRY(host_alloc(s->h_counts, need * sizeof(uint32_t), hipHostMallocDefault));
-        s->h_counts_words = need;
-    }
-    hipStream_t st = s->stream;
-    HIP_TRY(hipMemsetAsync(s->d_counts, 0, need * sizeof(uint32_t), st));
-    tsdfk::SegRefine a;
-    a.cluster = cluster; a.masks = masks; a.out = out; a.counts = s->d_counts;
-    a.H = s->H; a.W = s->W; a.K = K; a.C = C; a.inset = p->inset; a.overlap = p->overlap;
-    const dim3 grid((unsigned)((n_px + 255) / 256), (unsigned)K);
-    hipLaunchKernelGGL(tsdfk::seg_refine_count, grid, dim3(256), 0, st, a);
-    hipLaunchKernelGGL(tsdfk::seg_refine_accept, grid, dim3(256), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    if (counts_host && words > 0)
-        HIP_TRY(hipMemcpyAsync(s->h_counts.get(), s->d_counts.get(), (size_t)words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (counts_host && words > 0) std::memcpy(counts_host, s->h_counts.get(), (size_t)words * sizeof(uint32_t));
-    return TSDF_OK;
-}
-
-static int seg_masks_ok(const char *who, int32_t k)
-{
-    if (k < 1 || k > tsdfk::kAssocMaxMasks)
-        return fail(TSDF_ERR_INVALID, "%s: k = %d masks is outside 1..%d", who, k, tsdfk::kAssocMaxMasks);
-    return TSDF_OK;
-}
-
-int tsdf_segment_params_default(const tsdf_config *cfg, tsdf_segment_params *out)
-{
-    if (!cfg || !out) return fail(TSDF_ERR_INVALID, "tsdf_segment_params_default: NULL argument");
-    std::memcpy(out->cam_K, cfg->cam_K, sizeof out->cam_K);
-    out->im_height = cfg->im_height;
-    out->im_width = cfg->im_width;
-    out->near_m = 0.0f;
-    out->far_m = cfg->max_depth;
-    out->small_radius_m = 0.05f;      // ref: config/TUM3.yaml:75
-    out->large_radius_m = 0.5f;       // :76
-    out->don_thresh = 0.1f;           // :77
-    out->seg_radius_m = 0.05f;        // :78
-    out->min_cluster = 15;            // ref: src/DoN.cpp:47
-    out->max_cluster = 1000000;
-    out->overlap = 0.5f;              // ref: config/TUM3.yaml:90
-    out->inset = 2;                   // :85, mnDist = 1.0: more than one pixel inside the contour
-    return TSDF_OK;
-}
-
-int tsdf_segmenter_destroy(tsdf_segmenter *s)
-{
-    if (!s) return TSDF_OK;
-    (void)hipSetDevice(s->device);
-    if (s->own_stream) (void)hipStreamSynchronize(s->own_stream);
-    if (s->stream && s->stream != s->own_stream) (void)hipStreamSynchronize(s->stream);
-    delete s;            // the owners release the memory and the stream (the device is current)
-    return TSDF_OK;
-}
-
-int tsdf_segmenter_create(int32_t device, int32_t im_height, int32_t im_width, tsdf_segmenter **out)
-{
-    const char *who = "tsdf_segmenter_create";
-    if (!out) return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
-    *out = nullptr;
-    int rc = seg_image_ok(who, im_height, im_width);
-    if (rc) return rc;
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
-        return fail(TSDF_ERR_NO_DEVICE, "%s: no HIP device visible (this library has no CPU path)", who);
-    if (device < 0 || device >= n_dev) return fail(TSDF_ERR_INVALID, "%s: device %d not in [0,%d)", who, device, n_dev);
-    tsdf_segmenter *s = new (std::nothrow) tsdf_segmenter();
-    if (!s) return fail(TSDF_ERR_INVALID, "%s: out of host memory", who);
-    s->device = device; s->H = im_height; s->W = im_width;
-    auto cleanup = [&](int code) { tsdf_segmenter_destroy(s); return code; };
-    HIP_TRY_OR(cleanup, hipSetDevice(device));
-    HIP_TRY_OR(cleanup, stream_create(s->own_stream));
-    s->stream = s->own_stream;
-    const size_t n_px = (size_t)im_height * im_width, nb = (n_px + 255) / 256;
-    HIP_TRY_OR(cleanup, dev_alloc(s->d_pts, n_px * sizeof(int4)));
-    HIP_TRY_OR(cleanup, dev_alloc(s->d_parent, n_px * sizeof(int32_t)));
-    HIP_TRY_OR(cleanup, dev_alloc(s->d_root, n_px * sizeof(int32_t)));
-    HIP_TRY_OR(cleanup, dev_alloc(s->d_num, n_px * sizeof(int32_t)));
-    HIP_TRY_OR(cleanup, dev_alloc(s->d_cluster, n_px * sizeof(int32_t)));
-    HIP_TRY_OR(cleanup, dev_alloc(s->d_size, n_px * sizeof(uint32_t)));
-    HIP_TRY_OR(cleanup, dev_alloc(s->d_blocks, nb * sizeof(uint32_t)));
-    HIP_TRY_OR(cleanup, dev_alloc(s->d_total, sizeof(int32_t)));
-    HIP_TRY_OR(cleanup, host_alloc(s->h_total, sizeof(int32_t), hipHostMallocDefault));
-    *out = s;
-    return TSDF_OK;
-}
-
-int tsdf_segmenter_set_stream(tsdf_segmenter *s, void *hip_stream)
-{
-    if (!s) return fail(TSDF_ERR_INVALID, "tsdf_segmenter_set_stream: NULL handle");
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipStreamSynchronize(s->stream));  // do not reorder against work already queued
-    s->stream = hip_stream ? (hipStream_t)hip_stream : s->own_stream.get();
-    return TSDF_OK;
-}
-
-int tsdf_segment_depth_device(tsdf_segmenter *s, const tsdf_segment_params *p, const float *depth_dev, float *don_dev,
-                              int32_t *cluster_dev, int32_t *n_clusters)
-{
-    const char *who = "tsdf_segment_depth_device";
-    int rc = seg_params_ok(who, p);
-    if (rc) return rc;
-    if (!s || !depth_dev || !cluster_dev || !n_clusters) return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
-    rc = seg_handle_ok(who, s, p);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    return seg_depth(s, p, depth_dev, don_dev, cluster_dev, n_clusters);
-}
-
-int tsdf_segment_refine_masks_device(tsdf_segmenter *s, const tsdf_segment_params *p, const int32_t *cluster_dev,
-                                     int32_t n_clusters, const uint8_t *masks_dev, int32_t k, uint8_t *masks_out_dev,
-                                     uint32_t *counts_host)
-{
-    const char *who = "tsdf_segment_refine_masks_device";
-    int rc = seg_params_ok(who, p);
-    if (rc == TSDF_OK) rc = seg_masks_ok(who, k);
-    if (rc) return rc;
-    if (n_clusters < 0) return fail(TSDF_ERR_INVALID, "%s: n_clusters = %d is negative", who, n_clusters);
-    if (!s || !cluster_dev || !masks_dev || !masks_out_dev) return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
-    if (masks_out_dev == masks_dev) return fail(TSDF_ERR_INVALID, "%s: the masks cannot be refined in place", who);
-    rc = seg_handle_ok(who, s, p);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    return seg_refine(who, s, p, cluster_dev, n_clusters, masks_dev, k, masks_out_dev, counts_host);
-}
-
-int tsdf_segment_frame(tsdf_segmenter *s, const tsdf_segment_params *p, const float *depth_dev, const uint8_t *masks_dev,
-                       int32_t k, uint8_t *masks_out_dev, int32_t *cluster_dev, int32_t *n_clusters)
-{
-    const char *who = "tsdf_segment_frame";
-    int rc = seg_params_ok(who, p);
-    if (rc == TSDF_OK) rc = seg_masks_ok(who, k);
-    if (rc) return rc;
-    if (!s || !depth_dev || !masks_dev || !masks_out_dev || !n_clusters) return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
-    if (masks_out_dev == masks_dev) return fail(TSDF_ERR_INVALID, "%s: the masks cannot be refined in place", who);
-    rc = seg_handle_ok(who, s, p);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    int32_t *cluster = cluster_dev ? cluster_dev : s->d_cluster.get();
-    rc = seg_depth(s, p, depth_dev, nullptr, cluster, n_clusters);
-    if (rc) return rc;
-    return seg_refine(who, s, p, cluster, *n_clusters, masks_dev, k, masks_out_dev, nullptr);
-}
-
 }  // extern "C"
 
+#include "tsdf_raycast_host.hip.h"
+#include "tsdf_track_host.hip.h"
+#include "tsdf_fuse_host.hip.h"
+#include "tsdf_associate_host.hip.h"
+#include "tsdf_segment_host.hip.h"
 #include "tsdf_group.hip.h"
 #include "tsdf_diag.hip.h"

@@ -58,11 +58,7 @@ int classify_single(tsdf_volume *v, tsdfk::IntegrateParams &p, int nbx, int nby,
     int rc0 = tables_begin(v, &tiles);   // (released by the caller's tables_end() after the launch that reads the classes)
     if (rc0) return rc0;
     const size_t n_wg = (size_t)nbx * nby * nz;
-    if (v->wg_class_bytes < n_wg) {
-        v->wg_class_bytes = 0;
-        HIP_TRY(dev_alloc(v->d_wg_class, n_wg));
-        v->wg_class_bytes = n_wg;
-    }
+    HIP_TRY(v->d_wg_class.ensure(n_wg));
     const float *d = p.depth;
     const uint8_t *m = p.mask;
     int rc = build_tile_tables(v->stream, v->cfg, p, &d, &m, 1, tiles);
@@ -192,26 +188,16 @@ int launch_multi_experiment(tsdf_volume *v, tsdfk::MultiParamsInline &mi, const 
     mi.nz_super = 1;
     if (!labels && (v->variant == 4 || v->variant == 5 || v->variant == 6)) {
         // frame blocks staged in device memory: pinned host ring -> device ring
-        const int s = v->frames_next;
-        v->frames_next = (s + 1) % kStageSlots;
-        const size_t bytes = tsdfk::kMaxFramesPerLaunch * sizeof(tsdfk::FramePose);
-        if (!v->h_frames[s]) {      // all three or none
-            HostPtr<tsdfk::FramePose> h;
-            DevPtr<tsdfk::FramePose> d;
-            Event done;
-            HIP_TRY(host_alloc(h, bytes, hipHostMallocDefault));
-            HIP_TRY(dev_alloc(d, bytes));
-            HIP_TRY(event_create(done));
-            v->h_frames[s] = std::move(h); v->d_frames[s] = std::move(d); v->frames_done[s] = std::move(done);
-        }
-        if (v->frames_used[s]) HIP_TRY(hipEventSynchronize(v->frames_done[s]));
+        decltype(v->frames)::Slot *s = nullptr;
+        HIP_TRY(v->frames.take(&s));
+        if (!s->dev) HIP_TRY(staged_alloc(*s, s->done, tsdfk::kMaxFramesPerLaunch * sizeof(tsdfk::FramePose)));
         tsdfk::MultiParams mp;
         mp.common = mi.common;
         mp.common.claim_counter = nullptr;
-        mp.frames = v->d_frames[s];
+        mp.frames = s->dev;
         mp.n_frames = n;
-        for (int f = 0; f < n; ++f) { v->h_frames[s][f] = mi.frames[f]; v->h_frames[s][f].tiles = nullptr; }
-        HIP_TRY(hipMemcpyAsync(v->d_frames[s], v->h_frames[s], n * sizeof(tsdfk::FramePose), hipMemcpyHostToDevice, v->stream));
+        for (int f = 0; f < n; ++f) { s->host[f] = mi.frames[f]; s->host[f].tiles = nullptr; }
+        HIP_TRY(hipMemcpyAsync(s->dev, s->host, n * sizeof(tsdfk::FramePose), hipMemcpyHostToDevice, v->stream));
         if (v->flat) {
             dim3 grid((v->chunks_per_slice + 3) / 4, 1, nz);
             hipLaunchKernelGGL((tsdfk::integrate_multi<1, true, true>), grid, block, 0, v->stream, mp);
@@ -226,8 +212,7 @@ int launch_multi_experiment(tsdf_volume *v, tsdfk::MultiParamsInline &mi, const 
             hipLaunchKernelGGL((tsdfk::integrate_multi<1, true, false>), grid, block, 0, v->stream, mp);
         }
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(v->frames_done[s], v->stream));
-        v->frames_used[s] = true;
+        HIP_TRY(v->frames.consumed(s, v->stream));
         *handled = true;
         *claims_total = 0.0;
         return TSDF_OK;
@@ -254,11 +239,7 @@ int launch_multi_experiment(tsdf_volume *v, tsdfk::MultiParamsInline &mi, const 
         if (v->variant == 13) {
             mi.nz_super = (nz_groups + tsdfk::kSuperZ - 1) / tsdfk::kSuperZ;
             const size_t words = (size_t)wgs * mi.nz_super;
-            if (v->super_words < words) {
-                v->super_words = 0;
-                HIP_TRY(dev_alloc(v->d_super, words * sizeof(unsigned int)));
-                v->super_words = words;
-            }
+            HIP_TRY(v->d_super.ensure(words));
             hipLaunchKernelGGL(tsdfk::classify_superbricks, dim3((unsigned)((words + 3) / 4)), block, 0, v->stream, mi, v->d_super, (int)wgs);
             mi.super_mask = v->d_super;
         }

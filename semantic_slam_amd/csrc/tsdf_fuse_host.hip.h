@@ -1,0 +1,107 @@
+// tsdf_fuse_host.hip.h -- host side of merging and re-gridding (include/tsdf_hip.h: tsdf_fuse_*), included at the end of
+// tsdf_capi.hip; tsdf_fuse.hip.h states the rule.
+#pragma once
+
+namespace {
+
+int fuse_handle_ok(const char *who, const char *side, const tsdf_volume *v)
+{
+    const tsdf_config &c = v->cfg;
+    if (v->group_owner) return fail(TSDF_ERR_INVALID, "%s: %s is a slab of a tsdf_group; merging needs whole-grid handles", who, side);
+    if (c.z_begin != 0 || c.z_end != c.dim_z)
+        return fail(TSDF_ERR_INVALID, "%s: %s is the z-slab [%d,%d) of %d slices; merging needs whole-grid handles", who, side,
+                    c.z_begin, c.z_end, c.dim_z);
+    return TSDF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tsdf_fuse_params_default(const tsdf_config *dst_cfg, tsdf_fuse_params *out)
+{
+    if (!dst_cfg || !out) return fail(TSDF_ERR_INVALID, "tsdf_fuse_params_default: NULL argument");
+    out->weight_thresh = 0.9f;
+    out->agree_tol = 0.4f;   // two voxels of the default band of five: a choice
+    out->write = 1;
+    return TSDF_OK;
+}
+
+int tsdf_fuse_volume(tsdf_volume *dst, tsdf_volume *src, const tsdf_fuse_params *p, tsdf_fuse_counts *counts)
+{
+    const char *who = "tsdf_fuse_volume";
+    if (!dst || !src || !p) return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
+    if (dst == src) return fail(TSDF_ERR_INVALID, "%s: dst and src are the same handle", who);
+    int rc = fuse_handle_ok(who, "dst", dst);
+    if (rc == TSDF_OK) rc = fuse_handle_ok(who, "src", src);
+    if (rc) return rc;
+    if (dst->cfg.device != src->cfg.device)
+        return fail(TSDF_ERR_INVALID, "%s: dst is on device %d, src on device %d", who, dst->cfg.device, src->cfg.device);
+    if (!std::isfinite(p->weight_thresh)) return fail(TSDF_ERR_INVALID, "%s: weight_thresh is not finite", who);
+    if (!std::isfinite(p->agree_tol) || !(p->agree_tol > 0.0f))
+        return fail(TSDF_ERR_INVALID, "%s: agree_tol must be finite and > 0 (%g)", who, (double)p->agree_tol);
+    if (p->write != 0 && p->write != 1) return fail(TSDF_ERR_INVALID, "%s: write must be 0 or 1 (%d)", who, p->write);
+    rc = bind_device(dst);               // the collected frames of both, through their batches where they have one
+    if (rc == TSDF_OK) rc = bind_device(src);
+    if (rc) return rc;
+    if (!dst->d_fuse) {                  // all four or none
+        DevPtr<unsigned long long> d;
+        HostPtr<unsigned long long> h;
+        Event ready, done;
+        HIP_TRY(dev_alloc(d, 4 * sizeof(unsigned long long)));
+        HIP_TRY(host_alloc(h, 4 * sizeof(unsigned long long), hipHostMallocDefault));
+        HIP_TRY(event_create(ready));
+        HIP_TRY(event_create(done));
+        dst->d_fuse = std::move(d); dst->h_fuse = std::move(h);
+        dst->fuse_src_ready = std::move(ready); dst->fuse_done = std::move(done);
+    }
+    const tsdf_config &cd = dst->cfg, &cs = src->cfg;
+    float M[16];
+    tsdf_host::multiply_matrix(src->base2world_inv, cd.base2world, M);
+    tsdfk::FuseParams k;
+    k.dt = dst->d_tsdf; k.dw = dst->d_weight;
+    k.st = src->d_tsdf; k.sw = src->d_weight;
+    for (int i = 0; i < 12; ++i) k.m[i] = M[i];
+    const int sd[3] = {cs.dim_x, cs.dim_y, cs.dim_z}, dd[3] = {cd.dim_x, cd.dim_y, cd.dim_z};
+    for (int i = 0; i < 3; ++i) {
+        k.od[i] = cd.origin[i]; k.os[i] = cs.origin[i];
+        k.hi[i] = (float)(sd[i] - 1);
+        k.sdim[i] = sd[i]; k.ddim[i] = dd[i];
+    }
+    k.vsd = cd.voxel_size; k.vss = cs.voxel_size;
+    k.ratio = cs.trunc_margin / cd.trunc_margin;
+    k.wthr = p->weight_thresh; k.tol = p->agree_tol;
+    k.write = p->write;
+    k.counts = dst->d_fuse;
+    HIP_TRY(hipMemsetAsync(dst->d_fuse, 0, 4 * sizeof(unsigned long long), dst->stream));
+    if (src->stream != dst->stream) {    // after everything queued on src's stream so far
+        HIP_TRY(hipEventRecord(dst->fuse_src_ready, src->stream));
+        HIP_TRY(hipStreamWaitEvent(dst->stream, dst->fuse_src_ready, 0));
+    }
+    const int quads = (cd.dim_x + 3) / 4;
+    const dim3 grid((quads + 7) / 8, (cd.dim_y + 7) / 8, (cd.dim_z + 4 * tsdfk::kFuseZRun - 1) / (4 * tsdfk::kFuseZRun));
+    if (cd.dim_x % 4 == 0)
+        hipLaunchKernelGGL(tsdfk::fuse_volume<true>, grid, dim3(256), 0, dst->stream, k);
+    else
+        hipLaunchKernelGGL(tsdfk::fuse_volume<false>, grid, dim3(256), 0, dst->stream, k);
+    HIP_TRY(hipGetLastError());
+    if (src->stream != dst->stream) {    // a later write to src must not overtake the read
+        HIP_TRY(hipEventRecord(dst->fuse_done, dst->stream));
+        HIP_TRY(hipStreamWaitEvent(src->stream, dst->fuse_done, 0));
+    }
+    if (p->write) {                      // later fused / classified Integrate launches must not trust stale summary words
+        rc = rebuild_summary(dst);
+        if (rc) return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(dst->h_fuse.get(), dst->d_fuse, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, dst->stream));
+    HIP_TRY(hipStreamSynchronize(dst->stream));
+    if (counts) {
+        counts->sampled = dst->h_fuse.get()[0];
+        counts->both = dst->h_fuse.get()[1];
+        counts->both_band = dst->h_fuse.get()[2];
+        counts->agree_band = dst->h_fuse.get()[3];
+    }
+    return TSDF_OK;
+}
+
+}  // extern "C"

@@ -24,10 +24,9 @@ struct tsdf_group {
     std::vector<tsdf_volume *> slabs;     // slab i: z in [i*dim_z/n, (i+1)*dim_z/n), on devices[i]
     std::vector<int> devices;
     // pinned frames every device can read (hipHostMallocPortable): a ring for single frames, a pool for sequences
-    HostPtr<float> h_ring[kStageSlots];
-    int ring_next = 0;
-    std::vector<Event> ring_copied;       // [ring slot][slab]: that slab's copy out of the slot
-    std::vector<bool> ring_used;
+    // (a ring slot is free when every slab's copy out of it has run: one event per slab and device, not the slot's own)
+    struct RingFrame { HostPtr<float> host; std::vector<Event> copied; std::vector<bool> copy_queued; };
+    StageRing<RingFrame, kStageSlots> ring;
     HostPtr<float> h_pool;                // kMaxFramesPerLaunch frames, allocated on first tsdf_group_integrate_frames
     std::vector<DevPtr<float>> d_pool;    // per slab: the same frames in its device's memory
     std::vector<Event> pool_done;         // per slab: the copy of its last pass out of h_pool has run
@@ -184,7 +183,7 @@ int tsdf_group_destroy(tsdf_group *g)
         if (i < g->d_pool.size()) g->d_pool[i].reset();
         if (i < g->pool_done.size()) g->pool_done[i].reset();
         if (i < g->d_halo.size()) g->d_halo[i].reset();
-        for (size_t k = i; k < g->ring_copied.size(); k += g->slabs.size()) g->ring_copied[k].reset();
+        for (auto &s : g->ring.slots) if (i < s.copied.size()) s.copied[i].reset();
         tsdf_destroy(v);
     }
     delete g;            // (the pinned ring and pool are portable)
@@ -220,11 +219,11 @@ int tsdf_group_create(const tsdf_config *cfg, const int32_t *devices, int32_t n_
     g->pool_done.resize((size_t)n_slabs);
     g->pool_used.assign((size_t)n_slabs, false);
     g->d_halo.resize((size_t)n_slabs);
-    g->ring_copied.resize((size_t)n_slabs * kStageSlots);
-    g->ring_used.assign((size_t)n_slabs * kStageSlots, false);
     const size_t img = (size_t)cfg->im_height * cfg->im_width * sizeof(float);
-    for (int s = 0; s < kStageSlots; ++s) {
-        hipError_t e = host_alloc(g->h_ring[s], img, hipHostMallocPortable);
+    for (auto &s : g->ring.slots) {
+        s.copied.resize((size_t)n_slabs);
+        s.copy_queued.assign((size_t)n_slabs, false);
+        hipError_t e = host_alloc(s.host, img, hipHostMallocPortable);
         if (e != hipSuccess) return cleanup(fail(TSDF_ERR_HIP, "tsdf_group_create: pinned frame: %s", hipGetErrorString(e)));
     }
     // neighbouring slabs on different devices exchange one slice at extraction: let the copy go directly over xGMI
@@ -272,18 +271,18 @@ int tsdf_group_integrate(tsdf_group *g, const float *depth_host, const float cam
         if (++g->pend_count >= std::min(g->defer_n, (int)tsdfk::kMaxFramesPerLaunch)) return group_flush(g);
         return TSDF_OK;
     }
-    const int s = g->ring_next;
-    g->ring_next = (s + 1) % kStageSlots;
+    decltype(g->ring)::Slot *s = nullptr;
+    HIP_TRY(g->ring.take(&s));
     const size_t img = (size_t)g->cfg.im_height * g->cfg.im_width * sizeof(float);
     const size_t n = g->slabs.size();
     // the pinned slot is free again when every slab's copy out of it has run
     for (size_t i = 0; i < n; ++i) {
-        if (g->ring_used[(size_t)s * n + i]) {
+        if (s->copy_queued[i]) {
             HIP_TRY(hipSetDevice(g->slabs[i]->cfg.device));
-            HIP_TRY(hipEventSynchronize(g->ring_copied[(size_t)s * n + i]));
+            HIP_TRY(hipEventSynchronize(s->copied[i]));
         }
     }
-    tsdf_host::copy_to_pinned(g->h_ring[s], depth_host, img);          // the caller may free depth_host after we return
+    tsdf_host::copy_to_pinned(s->host, depth_host, img);          // the caller may free depth_host after we return
     for (size_t i = 0; i < n; ++i) {
         tsdf_volume *v = g->slabs[i];
         int rc0 = bind_device(v);      // device current; frames given to a borrowed slab handle come first
@@ -293,11 +292,11 @@ int tsdf_group_integrate(tsdf_group *g, const float *depth_host, const float cam
         void *dev = nullptr;
         int rc = store_slot(v, &v->store->frames, v->copy_stream, &slot, &dev);
         if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(dev, g->h_ring[s], img, hipMemcpyHostToDevice, v->copy_stream));
-        if (!g->ring_copied[(size_t)s * n + i]) HIP_TRY(event_create(g->ring_copied[(size_t)s * n + i]));
-        HIP_TRY(hipEventRecord(g->ring_copied[(size_t)s * n + i], v->copy_stream));
-        g->ring_used[(size_t)s * n + i] = true;
-        HIP_TRY(hipStreamWaitEvent(v->stream, g->ring_copied[(size_t)s * n + i], 0));
+        HIP_TRY(hipMemcpyAsync(dev, s->host, img, hipMemcpyHostToDevice, v->copy_stream));
+        if (!s->copied[i]) HIP_TRY(event_create(s->copied[i]));
+        HIP_TRY(hipEventRecord(s->copied[i], v->copy_stream));
+        s->copy_queued[i] = true;
+        HIP_TRY(hipStreamWaitEvent(v->stream, s->copied[i], 0));
         float c2b[16];
         compose_cam2base(v, cam2world, c2b);
         rc = launch_integrate(v, static_cast<const float *>(dev), nullptr, c2b);

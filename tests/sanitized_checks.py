@@ -211,6 +211,33 @@ def main():
     ok(L.asan_batch_classifies(ADAPTIVE, 24, 48000000) == 1 and L.asan_batch_classifies(ADAPTIVE, 25, 48000000) == 0)   # 2 M voxels per member
     ok([L.asan_batch_lanes(m) for m in (1, 7, 8, 64)] == [1, 1, 4, 4])
 
+    # ---- scratch blocks (csrc/host_derive.h, Regions): the three layouts it carves, every region on a 256-byte boundary, the last
+    # one not padded; sizes on both sides of a boundary (63 / 64 / 65 pixels of 4 bytes) -------------------------------------------
+    L.asan_regions.argtypes = [C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_size_t)]
+    L.asan_regions.restype = C.c_size_t
+
+    def up(b):
+        return -(-b // 256) * 256
+
+    track_state = 12 * 8 + 12 * 4 + 8 * 4 + 8 + 29 * 8              # struct TrackState (csrc/tsdf_track.hip.h): 416 bytes
+    for px in (1, 63, 64, 65, 640 * 480):
+        for k_words in (8, 3 * 3 * 2 + 3 * 3 + 4 * 2):              # associate: 3 K M + 3 K + 4 M words of counts
+            layouts = {"raycast": [px * 4, px * 12, px * 2, px * 4],                    # depth | normal | label | colour
+                       "track": [px * 4, px * 12, 8 * 256 * 29, track_state],        # depth | normal | 256 partial rows of 29 | state
+                       "associate": [px * 4, px * 4, k_words * 4]}                     # member | render depth | counts
+            for name, sizes in layouts.items():
+                want, end = [], 0
+                for b in sizes:
+                    want.append(up(end))
+                    end = want[-1] + b
+                got = (C.c_size_t * len(sizes))()
+                total = L.asan_regions((C.c_size_t * len(sizes))(*sizes), len(sizes), got)
+                ok(list(got) == want and total == end and all(o % 256 == 0 for o in got), (name, px, list(got), want, total, end))
+    # ... and as the three call sites wrote them before the carver: running sums of rounded sizes
+    px = 65
+    got = (C.c_size_t * 4)()
+    ok(L.asan_regions((C.c_size_t * 4)(px * 4, px * 12, px * 2, px * 4), 4, got) == 512 + 1024 + 256 + 260 and list(got) == [0, 512, 1536, 1792])
+
     # ---- the caller's frame into the pinned ring (csrc/host_copy.h: 32-byte streaming stores from 64 KiB, memcpy below) ---------------
     L.asan_copy_to_pinned.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     src = rng.integers(0, 256, 1228800 + 300).astype(np.uint8)

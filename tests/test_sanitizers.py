@@ -4,7 +4,7 @@ arithmetic -- csrc/pose_math.h and csrc/host_derive.h behind oracle/asan_host.cp
 UndefinedBehaviorSanitizer, every finding fatal; tests/sanitized_checks.py then runs the seven golden vectors (whole grid and
 slabs), NaN / inf / denormal depth frames, the pose known-answer tests on 206 matrices (restatement == product header, bit for
 bit), the brick choice and the guards for degenerate configurations and poses, the launch policy's thresholds on both sides
-and its known answers, the streaming copy into the pinned ring for sizes and
+and its known answers, the layout of the scratch blocks, the streaming copy into the pinned ring for sizes and
 alignments around its thresholds, the .ply / .bin writers, the extraction rules and
 the label / colour rules in a child interpreter with the sanitizer runtimes preloaded."""
 import json
