@@ -442,6 +442,75 @@ int tsdf_fuse_params_default(const tsdf_config *dst_cfg, tsdf_fuse_params *out);
 int tsdf_fuse_volume(tsdf_volume *dst, tsdf_volume *src, const tsdf_fuse_params *p, tsdf_fuse_counts *counts /* may be NULL */);
 
 /*
+ * Extent: what a fused volume holds -- how many voxels were observed, how many lie near a surface, where those are (sums,
+ * second moments, index bounds) and how many of them sit against each face of the grid.  Three decisions of the per-object
+ * loop read it: whether an object has outgrown the grid placed from its first frame (ref: src/Object.cpp:37-49 places it once;
+ * tsdf_fuse_volume moves the content, tsdf_extent_regrid proposes where to), whether an instance is worth keeping (the dense
+ * counterpart of HasEnoughObjectPoints, ref: src/Object.cpp:305-309, src/Engine.cpp:238-250), and where the object is (ref:
+ * src/Engine.cpp:550 matches instances by 2-D contour centroids and asks "should this be the TSDF center instead ?").  Not a
+ * reference function; the rule is stated in csrc/tsdf_extent.hip.h and restated with exact integers in tests/extent_spec.py.
+ * The library makes none of these decisions.
+ *   For the voxel at GLOBAL grid index (x, y, z) with TSDF t and weight w:
+ *     observed   w > weight_thresh
+ *     surface    observed && fabsf(t) < band      (a NaN t is never surface; a free-space t == 1 is not when band == 1)
+ *   The record holds integers only, so it is specified bit for bit and does not depend on the order of the reduction.  A
+ *   voxel near two faces counts for both; margin == 0 leaves all six border counts 0.
+ *   weight_thresh   finite                 band   finite, in (0, 1]                 margin   >= 0
+ * tsdf_extent_params_default: weight_thresh 0.9 (the extraction, raycast and merge default), band 1.0 (anywhere inside the
+ * truncation band), margin (int32_t)ceilf(trunc_margin / voxel_size) -- 5 for the reference's grid: a surface closer to a face
+ * than this has part of its band clipped by the grid.  Host arithmetic only: needs no device.
+ */
+typedef struct tsdf_extent_params { float weight_thresh; float band; int32_t margin; } tsdf_extent_params;
+typedef struct tsdf_extent {
+    uint64_t n_observed, n_surface;
+    uint64_t sum[3];      /* over surface voxels: x, y, z                       */
+    uint64_t sum2[6];     /* xx, yy, zz, xy, xz, yz                             */
+    uint64_t border[6];   /* surface voxels within `margin` voxels of the faces */
+                          /* x-, x+, y-, y+, z-, z+ of the GLOBAL grid          */
+                          /* (x < margin; x >= dim_x - margin; and so on)       */
+    int32_t lo[3], hi[3]; /* inclusive index bounds of the surface voxels;      */
+                          /* lo = dims, hi = -1 when n_surface == 0             */
+} tsdf_extent;
+int tsdf_extent_params_default(const tsdf_config *cfg, tsdf_extent_params *out);
+/*
+ * The record of one handle, a plain one or a borrowed batch member or group slab.  Applies the handle's collected frames first
+ * (through its batch or group where it has one), queues everything on the handle's stream and returns when *out is on the host.
+ * Reads the volume only: not one bit of TSDF, weights, summary words, labels or colours changes.  Unlike raycast and merging it
+ * takes a z-slab handle: indices, bounds and the z faces are then in GLOBAL z and the record covers the slab's voxels.
+ * Refused with TSDF_ERR_INVALID (this call, tsdf_batch_extents and tsdf_group_extent): a NULL argument; a weight_thresh that
+ * is not finite; a band that is not finite or outside (0, 1]; a negative margin; a slab of so many voxels that voxels *
+ * (largest global dim)^2 reaches 2^64 (the second moments could wrap).
+ */
+int tsdf_volume_extent(tsdf_volume *vol, const tsdf_extent_params *p, tsdf_extent *out);
+/*
+ * The record of two disjoint sets of voxels of one grid from the records of each: sums added, lo by min, hi by max.  The
+ * extent of a whole grid equals the combination of its slabs' extents.  out may be a or b.  Host arithmetic only.
+ */
+int tsdf_extent_combine(const tsdf_extent *a, const tsdf_extent *b, tsdf_extent *out);
+/*
+ * Metric form of a record, in double: voxel index i sits at origin + i * voxel_size in the base frame.  centroid_base = origin +
+ * (sum / n) * voxel_size; centroid_world = base2world applied to it; cov_base = (sum2 / n - mean * mean^T) * voxel_size^2 in the
+ * order xx, yy, zz, xy, xz, yz; lo_base / hi_base = the outer corners of the bounding voxels, origin + (lo - 0.5) * voxel_size
+ * and origin + (hi + 0.5) * voxel_size (a voxel is the cube around its centre).  Refuses n_surface == 0.  Host arithmetic only.
+ * (The struct has a tag and no typedef: C keeps tags apart from function names, so both can be called tsdf_extent_metric.)
+ */
+struct tsdf_extent_metric {
+    double centroid_base[3], centroid_world[3];
+    double cov_base[6];
+    double lo_base[3], hi_base[3];
+};
+int tsdf_extent_metric(const tsdf_config *cfg, const tsdf_extent *e, struct tsdf_extent_metric *out);
+/*
+ * The grid to move an object into (tsdf_create, then tsdf_fuse_volume): *out_cfg starts as a copy of *cfg; per axis
+ * origin[i] = cfg->origin[i] + (float)(e->lo[i] - pad_voxels) * voxel_size -- two rounded float32 operations; the index may be
+ * negative: the grid grows outward -- and dim[i] = hi[i] - lo[i] + 1 + 2 * pad_voxels rounded up to a multiple of dim_multiple
+ * (batches need 4); z_begin = 0, z_end = dim_z.  Refuses n_surface == 0, pad_voxels < 0, dim_multiple < 1 and a result
+ * tsdf_create would refuse.  Host arithmetic only; whether and when to re-grid stays the caller's decision.
+ */
+int tsdf_extent_regrid(const tsdf_config *cfg, const tsdf_extent *e, int32_t pad_voxels, int32_t dim_multiple,
+                       tsdf_config *out_cfg);
+
+/*
  * Grid origin of a new object volume from its first (masked) depth frame, on the device: the per-axis
  * minimum over pixels with depth > 0 of the back-projected point, starting from 1000 -- what
  * Object::Object computes on the host before it constructs its TSDF (ref: src/Object.cpp:37-49, with the
@@ -487,6 +556,12 @@ int tsdf_batch_sync(tsdf_batch *batch);
  */
 int tsdf_batch_raycast_device(tsdf_batch *batch, const tsdf_raycast_params *p, const float cam2world[16], float *depth_dev,
                               float *normal_dev, int32_t *member_dev);
+/*
+ * The extent (tsdf_volume_extent) of every member of a batch in ONE launch (members differ in dims; the batch's slice map indexes {member, slice}): out receives
+ * tsdf_batch_size records.  Applies the batch's collected frames first, queues everything on the batch's stream and returns
+ * when all records are on the host.  Each record equals tsdf_volume_extent on that member's borrowed handle.
+ */
+int tsdf_batch_extents(tsdf_batch *batch, const tsdf_extent_params *p, tsdf_extent *out /* tsdf_batch_size records */);
 
 /*
  * Association: which object of a batch each instance mask of a live frame shows -- step 1 of the reference's per-instance
@@ -688,6 +763,11 @@ int tsdf_group_extract_mesh(tsdf_group *group, float weight_thresh, float *trian
 int tsdf_group_save_ply(tsdf_group *group, const char *path, float weight_thresh);
 int tsdf_group_save_mesh_ply(tsdf_group *group, const char *path, float weight_thresh);
 int tsdf_group_save_bin(tsdf_group *group, const char *path);
+/*
+ * The extent (tsdf_volume_extent) of the whole grid: the per-slab call on every slab's device, one host thread per slab, then
+ * tsdf_extent_combine.  Equal to the record of a whole-grid handle holding the same values.
+ */
+int tsdf_group_extent(tsdf_group *group, const tsdf_extent_params *p, tsdf_extent *out);
 
 /* Message describing the last failure on this thread ("" when none). */
 const char *tsdf_last_error(void);

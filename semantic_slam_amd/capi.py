@@ -32,6 +32,8 @@ ABI_SYMBOLS = [
     "tsdf_raycast_params_default", "tsdf_raycast_device", "tsdf_raycast", "tsdf_batch_raycast_device",
     "tsdf_track_params_default", "tsdf_track", "tsdf_track_system",
     "tsdf_fuse_params_default", "tsdf_fuse_volume",
+    "tsdf_extent_params_default", "tsdf_volume_extent", "tsdf_batch_extents", "tsdf_group_extent", "tsdf_extent_combine",
+    "tsdf_extent_metric", "tsdf_extent_regrid",
     "tsdf_associate_params_default", "tsdf_associate_count", "tsdf_associate_assign", "tsdf_batch_associate",
     "tsdf_segment_params_default", "tsdf_segmenter_create", "tsdf_segmenter_destroy", "tsdf_segmenter_set_stream",
     "tsdf_segment_depth_device", "tsdf_segment_refine_masks_device", "tsdf_segment_frame",
@@ -116,6 +118,39 @@ class FuseParams(C.Structure):
 class FuseCounts(C.Structure):
     """Mirror of `struct tsdf_fuse_counts` (include/tsdf_hip.h)."""
     _fields_ = [("sampled", C.c_uint64), ("both", C.c_uint64), ("both_band", C.c_uint64), ("agree_band", C.c_uint64)]
+
+
+class ExtentParams(C.Structure):
+    """Mirror of `struct tsdf_extent_params` (include/tsdf_hip.h)."""
+    _fields_ = [("weight_thresh", C.c_float), ("band", C.c_float), ("margin", C.c_int32)]
+
+
+class Extent(C.Structure):
+    """Mirror of `struct tsdf_extent` (include/tsdf_hip.h): integers only."""
+    _fields_ = [
+        ("n_observed", C.c_uint64), ("n_surface", C.c_uint64), ("sum", C.c_uint64 * 3), ("sum2", C.c_uint64 * 6),
+        ("border", C.c_uint64 * 6), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3),
+    ]
+
+    def as_dict(self):
+        """The record as plain Python integers (lists for the arrays): what tests/extent_spec.py produces."""
+        return {"n_observed": int(self.n_observed), "n_surface": int(self.n_surface), "sum": [int(x) for x in self.sum],
+                "sum2": [int(x) for x in self.sum2], "border": [int(x) for x in self.border], "lo": [int(x) for x in self.lo],
+                "hi": [int(x) for x in self.hi]}
+
+    @classmethod
+    def from_dict(cls, d):
+        e = cls()
+        e.n_observed, e.n_surface = d["n_observed"], d["n_surface"]
+        for name in ("sum", "sum2", "border", "lo", "hi"):
+            getattr(e, name)[:] = d[name]
+        return e
+
+
+class ExtentMetric(C.Structure):
+    """Mirror of `struct tsdf_extent_metric` (include/tsdf_hip.h): doubles."""
+    _fields_ = [("centroid_base", C.c_double * 3), ("centroid_world", C.c_double * 3), ("cov_base", C.c_double * 6),
+                ("lo_base", C.c_double * 3), ("hi_base", C.c_double * 3)]
 
 
 class AssociateParams(C.Structure):
@@ -239,6 +274,13 @@ def load():
     L.tsdf_track_system.argtypes = [vp, C.POINTER(TrackParams), vp, vp, vp, vp, C.c_int32, vp]
     L.tsdf_fuse_params_default.argtypes = [C.POINTER(TsdfConfig), C.POINTER(FuseParams)]
     L.tsdf_fuse_volume.argtypes = [vp, vp, C.POINTER(FuseParams), C.POINTER(FuseCounts)]
+    L.tsdf_extent_params_default.argtypes = [C.POINTER(TsdfConfig), C.POINTER(ExtentParams)]
+    L.tsdf_volume_extent.argtypes = [vp, C.POINTER(ExtentParams), C.POINTER(Extent)]
+    L.tsdf_batch_extents.argtypes = [vp, C.POINTER(ExtentParams), C.POINTER(Extent)]
+    L.tsdf_group_extent.argtypes = [vp, C.POINTER(ExtentParams), C.POINTER(Extent)]
+    L.tsdf_extent_combine.argtypes = [C.POINTER(Extent), C.POINTER(Extent), C.POINTER(Extent)]
+    L.tsdf_extent_metric.argtypes = [C.POINTER(TsdfConfig), C.POINTER(Extent), C.POINTER(ExtentMetric)]
+    L.tsdf_extent_regrid.argtypes = [C.POINTER(TsdfConfig), C.POINTER(Extent), C.c_int32, C.c_int32, C.POINTER(TsdfConfig)]
     L.tsdf_associate_params_default.argtypes = [C.POINTER(TsdfConfig), C.POINTER(AssociateParams)]
     L.tsdf_associate_count.argtypes = [C.c_int32, C.POINTER(AssociateParams), vp, vp, C.c_int32, vp, vp, C.c_int32, vp]
     L.tsdf_associate_assign.argtypes = [C.POINTER(AssociateParams), vp, C.c_int32, C.c_int32, C.POINTER(AssociateLabels), vp,
@@ -379,6 +421,37 @@ def fuse_params_default(cfg):
     p = FuseParams()
     check(load().tsdf_fuse_params_default(C.byref(cfg), C.byref(p)), "tsdf_fuse_params_default")
     return p
+
+
+def extent_params_default(cfg):
+    """Extent parameters from a config (include/tsdf_hip.h): weight_thresh 0.9, band 1.0, margin = ceil(trunc_margin /
+    voxel_size) voxels (no device)."""
+    p = ExtentParams()
+    check(load().tsdf_extent_params_default(C.byref(cfg), C.byref(p)), "tsdf_extent_params_default")
+    return p
+
+
+def extent_combine(a, b):
+    """The record of two disjoint sets of voxels of one grid (slabs) from the records of each (host only)."""
+    out = Extent()
+    check(load().tsdf_extent_combine(C.byref(a), C.byref(b), C.byref(out)), "tsdf_extent_combine")
+    return out
+
+
+def extent_metric(cfg, extent):
+    """Metric form of a record (host only, double): dict of centroid_base [3], centroid_world [3], cov_base [6] (xx, yy, zz,
+    xy, xz, yz), lo_base [3], hi_base [3] (the outer corners of the bounding voxels)."""
+    m = ExtentMetric()
+    check(load().tsdf_extent_metric(C.byref(cfg), C.byref(extent), C.byref(m)), "tsdf_extent_metric")
+    return {name: np.array(getattr(m, name), np.float64) for name, _ in ExtentMetric._fields_}
+
+
+def extent_regrid(cfg, extent, pad_voxels, dim_multiple=4):
+    """The config of the grid to move an object into (host only): the record's bounds padded by pad_voxels, dims rounded up to
+    a multiple of dim_multiple (batches need 4), whole-grid slab."""
+    out = TsdfConfig()
+    check(load().tsdf_extent_regrid(C.byref(cfg), C.byref(extent), pad_voxels, dim_multiple, C.byref(out)), "tsdf_extent_regrid")
+    return out
 
 
 def associate_params_default(cfg):
@@ -859,6 +932,16 @@ class Volume:
         return {"sampled": int(c.sampled), "both": int(c.both), "both_band": int(c.both_band),
                 "agree_band": int(c.agree_band)}
 
+    # -- extent -----------------------------------------------------------------------------
+    def extent(self, params=None):
+        """What the slab holds (csrc/tsdf_extent.hip.h): an Extent record -- observed and near-surface voxel counts, sums,
+        second moments, index bounds (GLOBAL z) and border counts.  params: an ExtentParams, default
+        extent_params_default(cfg).  Reads the volume only."""
+        p = extent_params_default(self.cfg) if params is None else params
+        e = Extent()
+        check(self.lib.tsdf_volume_extent(self._h, C.byref(p), C.byref(e)), "tsdf_volume_extent")
+        return e
+
     # -- outputs ----------------------------------------------------------------------------
     def count_surface(self, weight_thresh=0.9):
         n = C.c_int64()
@@ -989,6 +1072,14 @@ class Batch:
         overlap, mask, member = associate_split(counts, k, n)
         return {"counts": counts, "overlap": overlap, "mask": mask, "member": member, "assign": assign, "iou": iou}
 
+    def extents(self, params=None):
+        """The Extent record of every member, by one launch (tsdf_batch_extents).  params default: extent_params_default of
+        the first member's config."""
+        p = extent_params_default(self.cfgs[0]) if params is None else params
+        arr = (Extent * len(self.cfgs))()
+        check(self.lib.tsdf_batch_extents(self._h, C.byref(p), arr), "tsdf_batch_extents")
+        return list(arr)
+
     def close(self):
         if self._h:
             for v in self.volumes:
@@ -1080,6 +1171,13 @@ class Group:
 
     def save_bin(self, path):
         check(self.lib.tsdf_group_save_bin(self._h, os.fsencode(path)), "tsdf_group_save_bin")
+
+    def extent(self, params=None):
+        """The Extent record of the whole grid: every slab's, combined (tsdf_group_extent)."""
+        p = extent_params_default(self.cfg) if params is None else params
+        e = Extent()
+        check(self.lib.tsdf_group_extent(self._h, C.byref(p), C.byref(e)), "tsdf_group_extent")
+        return e
 
     def close(self):
         if self._h:

@@ -39,6 +39,7 @@
 #include "tsdf_raycast.hip.h"
 #include "tsdf_track.hip.h"
 #include "tsdf_fuse.hip.h"
+#include "tsdf_extent.hip.h"
 #include "tsdf_associate.hip.h"
 #include "tsdf_segment.hip.h"
 #ifdef TSDF_EXPERIMENTS
@@ -197,6 +198,10 @@ struct tsdf_volume {
     DevPtr<unsigned long long> d_fuse;
     HostPtr<unsigned long long> h_fuse;
     Event fuse_src_ready, fuse_done;
+    // extent (tsdf_volume_extent), allocated on first use, both or neither: the record and behind it one partial record per
+    // workgroup of the launch in HBM (the slab's dims fix their number); the record's pinned host copy
+    DevPtr<unsigned long long> d_extent;
+    HostPtr<unsigned long long> h_extent;
 };
 
 using tsdf_host::kBatchSideStreams;
@@ -241,6 +246,13 @@ struct tsdf_batch {
     // (member | depth) and the counts in HBM; the counts' pinned host copy
     DevBuf<char> d_assoc;
     HostBuf<uint32_t> h_assoc;
+    // extents (tsdf_batch_extents), allocated on first use, all or none: one record per member and behind them one partial
+    // record per workgroup of the launch in HBM; the records' pinned host copy; the members as the kernels read them (filled
+    // and copied once: a batch's members do not change)
+    DevPtr<unsigned long long> d_extent;
+    HostPtr<unsigned long long> h_extent;
+    Staged<tsdfk::ExtentVolume> extent_vols;
+    int extent_blocks = 0;       // workgroups per slice of that launch
 };
 
 namespace {
@@ -1214,10 +1226,9 @@ int tsdf_config_default(tsdf_config *cfg, int32_t im_height, int32_t im_width)
     return TSDF_OK;
 }
 
-// tsdf_create, and tsdf_batch_create for its members (batch_member: one table layout for all of them, tsdf_host::tile_edge)
-static int create_volume(const tsdf_config *cfg, bool batch_member, tsdf_volume **out)
+// What tsdf_create refuses in a configuration before it looks for a device (also behind tsdf_extent_regrid: host arithmetic only).
+static int config_ok(const tsdf_config *cfg)
 {
-    *out = nullptr;
     if (cfg->dim_x <= 0 || cfg->dim_y <= 0 || cfg->dim_z <= 0)
         return fail(TSDF_ERR_INVALID, "tsdf_create: grid dims must be positive (%d,%d,%d)",
                     cfg->dim_x, cfg->dim_y, cfg->dim_z);
@@ -1233,6 +1244,15 @@ static int create_volume(const tsdf_config *cfg, bool batch_member, tsdf_volume 
         return fail(TSDF_ERR_INVALID, "tsdf_create: slab exceeds launch limits (dim_y <= 262140, slices <= 65535)");
     if ((int64_t)cfg->dim_x * cfg->dim_y > ((int64_t)1 << 31) - 1024)
         return fail(TSDF_ERR_INVALID, "tsdf_create: a slice may hold at most 2^31 voxels (dim_x * dim_y)");
+    return TSDF_OK;
+}
+
+// tsdf_create, and tsdf_batch_create for its members (batch_member: one table layout for all of them, tsdf_host::tile_edge)
+static int create_volume(const tsdf_config *cfg, bool batch_member, tsdf_volume **out)
+{
+    *out = nullptr;
+    int ok = config_ok(cfg);
+    if (ok) return ok;
 
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0)
@@ -2443,6 +2463,7 @@ int tsdf_load_state(tsdf_volume *v, const char *path)
 #include "tsdf_raycast_host.hip.h"
 #include "tsdf_track_host.hip.h"
 #include "tsdf_fuse_host.hip.h"
+#include "tsdf_extent_host.hip.h"
 #include "tsdf_associate_host.hip.h"
 #include "tsdf_segment_host.hip.h"
 #include "tsdf_group.hip.h"

@@ -440,4 +440,21 @@ int tsdf_group_save_bin(tsdf_group *g, const char *path)
     return TSDF_OK;
 }
 
+// The extent of the whole grid (tsdf_extent.hip.h): every slab's own record, the slabs concurrently, then combined in z
+// order -- the records are integer sums and bounds in GLOBAL indices, so the combination is the whole grid's record.
+int tsdf_group_extent(tsdf_group *g, const tsdf_extent_params *p, tsdf_extent *out)
+{
+    if (!g || !p || !out) return fail(TSDF_ERR_INVALID, "tsdf_group_extent: NULL argument");
+    int rc = extent_params_ok("tsdf_group_extent", p);
+    if (rc == TSDF_OK) rc = group_flush(g);
+    if (rc) return rc;
+    std::vector<tsdf_extent> part(g->slabs.size());
+    rc = for_each_slab(g, [&](int i) -> int { return tsdf_volume_extent(g->slabs[(size_t)i], p, &part[(size_t)i]); });
+    if (rc) return rc;
+    tsdf_extent all = part[0];
+    for (size_t i = 1; i < part.size(); ++i) tsdf_extent_combine(&all, &part[i], &all);
+    *out = all;
+    return TSDF_OK;
+}
+
 }  // extern "C"
