@@ -226,3 +226,159 @@ def test_track_layouts_match_c(tmp_path, struct, cname):
     assert int(got["size"]) == C.sizeof(struct)
     for f in fields:
         assert int(got[f]) == getattr(struct, f).offset, f
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the cases of test_gpu_track_exact.py: not vacuous, and clear of the restatement's own thresholds (tests/track_cases.py)
+# ------------------------------------------------------------------------------------------------------------------------
+import track_cases as tc
+from test_gpu_raycast import edge_state
+
+
+def world_of(dims, origin, vs, trunc, t, w):
+    """track_cases.World on the CPU: a fused TrackScene volume and the edge-valued volume of test_gpu_raycast.edge_state on
+    its grid, both rendered by raycast_spec."""
+    states = {"scene": (t, w), "edge": edge_state(dims, np.random.default_rng(tc.EDGE_SEED))}
+
+    def render(volume, ray, pose):
+        hw = (ray.im_height, ray.im_width)
+        o = rs.render(*states[volume], dims, origin, vs, trunc, np.asarray(ray.cam_K, f32), hw, ray.near_m, ray.far_m,
+                      ray.weight_thresh, pose)
+        return o["depth"].reshape(hw), o["normal"].reshape(hw + (3,))
+
+    return tc.World(dims, vs, origin, render)
+
+
+@pytest.fixture(scope="module")
+def world(fused):
+    dims, origin, trunc, t, w = fused
+    return world_of(dims, origin, VS, trunc, t, w)
+
+
+def reject_totals(world, cases):
+    """Gate totals over the cases (and, per case: the counts add up to the sample count)."""
+    tot, pairs = dict.fromkeys(ts.GATES, 0), []
+    for c in cases:
+        info = {}
+        terms = tc.spec_terms(world, c, info)
+        assert sum(info["rejected"].values()) + len(terms) == info["samples"] == ts.sample_grid(c.hw, c.level)[0].size, c
+        assert len(info["idx"]) == len(terms) and np.all(np.diff(info["idx"]) > 0), c
+        plain = tc.spec_terms(world, c)
+        assert plain.tobytes() == terms.tobytes(), c                 # info changes nothing
+        for g in ts.GATES:
+            tot[g] += info["rejected"][g]
+        pairs.append(len(terms))
+    return tot, pairs
+
+
+def test_value_edge_cases_reach_every_gate(world):
+    cases = tc.value_edge_cases(world)
+    assert len(cases) == 19
+    tot, pairs = reject_totals(world, cases)
+    print("a:", tot, pairs)
+    assert min(tot.values()) >= 10, tot
+    assert min(pairs) >= 50, pairs
+    for near, far, _ in tc.EDGE_RANGES:
+        mine = [c for c in cases if (c.par["near"], c.par["far"]) == (near, far)]
+        bits = set(mine[0].live.view(np.uint32).ravel().tolist())
+        assert set(tc.edge_depths(near, far).view(np.uint32).tolist()) <= bits, (near, far)   # every edge value is in the frame
+        if (near, far) != (tc.NEAR, tc.FAR):                          # len == 0 from tiny depths; len = inf from huge ones
+            assert reject_totals(world, mine)[0]["len"] >= 10, (near, far)
+
+
+def test_pose_edge_cases_leave_every_side_and_touch_every_border(world):
+    cases = tc.pose_edge_cases(world)
+    tot, pairs = reject_totals(world, cases)
+    print("b:", tot, pairs)
+    by = {c.name: c for c in cases}
+    h, w = tc.HW
+    borders = np.zeros(4, int)
+    for c in cases:
+        info = {}
+        tc.spec_terms(world, c, info)
+        n, rej = info["samples"], info["rejected"]
+        if "turned" in c.name:
+            assert rej["behind"] > n // 2, (c, rej)
+        if "off the" in c.name:
+            assert rej["off_image"] > n // 5 and len(info["idx"]) > n // 5, (c, rej)
+        if "sweep" in c.name:
+            assert len(info["idx"]) >= 50 and len(tc.border_pairs(c.hw, info)) > 0, c
+        ui, vi = info["model_px"]
+        borders += [(ui == 0).sum(), (ui == w - 1).sum(), (vi == 0).sum(), (vi == h - 1).sum()]
+    assert borders.min() >= 10, borders
+    assert tot["normal"] > 1000 and tot["distance"] > 1000, tot      # "b cos 1" and "b dist 1e-4"
+    assert sum("sweep" in n for n in by) == 20
+
+
+def test_a_single_pair_mask_leaves_exactly_that_pair(world):
+    cases = [tc.pose_edge_cases(world)[2], tc.value_edge_cases(world)[3], tc.reduction_case(world, (17, 18), close=True)]
+    for c in cases:
+        info = {}
+        terms = tc.spec_terms(world, c, info)
+        picks = tc.border_pairs(c.hw, info, cap=5) + tc.nearest_pairs(info["idx"], tc.reduction_targets(c.hw))
+        assert picks
+        for idx in picks:
+            one = {}
+            t1 = tc.spec_terms(world, c.with_mask(tc.single_mask(c.hw, c.level, idx), f"pair {idx}"), one)
+            assert len(t1) == 1 and one["idx"].tolist() == [idx], (c, idx)
+            assert t1[0].tobytes() == terms[np.searchsorted(info["idx"], idx)].tobytes(), (c, idx)
+            want, bound = tc.system_bound(t1)
+            assert want.tolist() == t1[0].astype(np.float64).tolist() and want[28] == 1.0
+
+
+def test_tiny_images_and_the_reduction_sizes_make_the_pairs_the_cases_need(world):
+    systems, tracks = tc.tiny_cases(world)
+    empty = 0
+    for c in systems:
+        n = ts.sample_grid(c.hw, c.level)[0].size
+        terms = tc.spec_terms(world, c)
+        empty += n == 0
+        assert len(terms) <= n and (n > 0 or terms.shape == (0, 29))
+    assert empty >= 10 and len(systems) == 21                        # levels without a sample
+    for hw, n_wg in zip(tc.REDUCTION[:4], (1, 2, 8, 9)):              # (the larger sizes cost a second each here)
+        n = (hw[0] - 1) * (hw[1] - 1)
+        assert (n + 255) // 256 == n_wg
+        c = tc.reduction_case(world, hw, close=True)
+        info, last = {}, {}
+        tc.spec_terms(world, c, info)
+        mask, first = tc.last_workgroup_mask(hw)
+        t = tc.spec_terms(world, c.with_mask(mask, "last workgroup"), last)
+        assert len(t) > 0 and last["idx"].min() >= first, (hw, first)
+        assert len(tc.nearest_pairs(info["idx"], tc.reduction_targets(hw))) >= 4
+    for hw, n in zip(tc.REDUCTION[4:7], (65280, 65536, 65792)):
+        assert (hw[0] - 1) * (hw[1] - 1) == n
+
+
+def test_tracked_cases_cover_the_state_machine_and_keep_clear_of_its_thresholds(world):
+    cases = tc.tracked_cases(world)
+    seen, early, full, w_only, tau_only = set(), False, False, False, False
+    res = {}
+    for c in cases:
+        hist = []
+        r = tc.spec_track(world, c, hist)
+        plain = ts.track((c.live, c.mask), world.model(c), c.P())
+        assert all(np.array_equal(plain[k], r[k]) for k in plain), c          # history changes nothing
+        P = c.P()
+        assert tc.preconditions(hist, P) == [], c
+        assert len(hist) == sum(r["iters_run"]) and [h["lost"] for h in hist[:-1]].count(True) == 0
+        seen.add(r["status"])
+        res[c.name] = r
+        for lvl in range(P["n_levels"]):
+            ended = any(h["done"] for h in hist if h["level"] == lvl)
+            early |= ended and r["iters_run"][lvl] < P["iters"][lvl]
+            full |= P["iters"][lvl] > 0 and r["iters_run"][lvl] == P["iters"][lvl] and not ended
+        for h in hist:
+            if h["w"] is not None:
+                w_only |= h["w"] < P["eps_rot"] and h["tau"] >= P["eps_trans"]
+                tau_only |= h["w"] >= P["eps_rot"] and h["tau"] < P["eps_trans"]
+        if r["lost"]:
+            assert r["pose"].tobytes() == c.ref.tobytes()
+    assert seen == {0, 1, 2} and early and full and w_only and tau_only, (seen, early, full, w_only, tau_only)
+    lost0 = res["f lost at level 0"]
+    assert lost0["status"] == 2 and min(lost0["iters_run"]) >= 1, lost0
+    at = [r for n, r in res.items() if n.startswith("f min_inliers c =")][0]
+    over = [r for n, r in res.items() if n.startswith("f min_inliers c + 1")][0]
+    assert not at["lost"] and sum(at["iters_run"]) > 1 and over["status"] == 2 and over["iters_run"] == [0, 0, 1]
+    for n, r in res.items():
+        if n.startswith("d "):
+            assert r["status"] == 2 and r["iters_run"] == [0, 0, 1], (n, r)

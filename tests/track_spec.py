@@ -1,13 +1,16 @@
 """Float32 NumPy restatement of the tracking rule of csrc/tsdf_track.hip.h (the header comment states it; this follows it line
 by line).  Per-sample values are np.float32 evaluated in the header's order, so every pair decision and every per-pair term is
-the device's bit for bit; the sums are float64 (np.sum: a different order from the device's, hence the tolerance
-1e-5 * sum |term| per entry), and the solve is float64.
+the device's bit for bit; the sums and the solve are float64.  The parity contract, as tests/test_gpu_track_exact.py and
+tests/test_gpu_track.py hold it: the system of a single pair equals the double value of these float32 terms exactly (a sum of
+one term has no order); a system of n pairs is within n * 2^-52 * sum |term| per entry (np.sum's order is not the device's:
+two double sums of the same n terms differ by at most 2 (n - 1) 2^-53 sum |term| to first order) with the pair count exact; a
+track's status, iters_run and inliers are equal, its rmse and every entry of its float32 pose within one float32 ulp.
 
     relative(c_ref, c_cur)                       M [3, 4] float64 = C_ref^-1 * C_cur (rigid inverse), the rule's order
     result_pose(base2world, c_ref, M)            cam2world float32 [16]
-    pair_terms(live, model, level, Rm, tm, P)    per-pair terms [n, 29] float32
+    pair_terms(live, model, level, Rm, tm, P)    per-pair terms [n, 29] float32 (info: rejects per gate, the pairs' samples)
     system(live, model, level, M, P)             (sums [29] float64, sum |term| [29] float64)
-    track(live, model, P, M0=None)               dict M, status, iters_run, inliers, rmse, lost
+    track(live, model, P, M0=None)               dict M, status, iters_run, inliers, rmse, lost (history: per iteration)
 
 live = (depth [H, W] float32, mask [H, W] uint8 or None); model = (depth [H, W], normal [H, W, 3]) of the render at C_ref; P: a
 dict of the tsdf_track_params fields (params() or from_ctypes()), with K, hw, near, far from its ray member.
@@ -73,8 +76,13 @@ def sample_grid(hw, level):
     return s * i.ravel(), s * j.ravel(), s
 
 
-def pair_terms(live, model, level, Rm, tm, P):
-    """(terms [n_pairs, 29] float32, the (u, v) of the pairs)."""
+GATES = ("depth_or_mask", "len", "behind", "off_image", "no_model", "distance", "normal")      # the rule's order
+
+
+def pair_terms(live, model, level, Rm, tm, P, info=None):
+    """(terms [n_pairs, 29] float32, the (u, v) of the pairs).  info, a dict, receives "samples" (ni * nj), "rejected" (a dict
+    of GATES: the samples each gate turned away, every sample counted at the first gate that rejects it) and "idx" (the flat
+    sample index j * ni + i of every pair, in the order of the terms) and "model_px" (the model pixel (ui, vi) of every pair)."""
     depth, mask = live
     mdepth, mnormal = model
     depth = np.asarray(depth, f32)
@@ -85,6 +93,7 @@ def pair_terms(live, model, level, Rm, tm, P):
     Rm = np.asarray(Rm, f32).reshape(3, 3)
     tm = np.asarray(tm, f32).ravel()
     u, v, s = sample_grid((H, W), level)
+    left = [u.size]                                    # samples still alive after each gate
 
     def ok(d, uu, vv):
         with np.errstate(invalid="ignore"):
@@ -96,6 +105,7 @@ def pair_terms(live, model, level, Rm, tm, P):
     d00, d10, d01 = depth[v, u], depth[v, u + s], depth[v + s, u]
     keep = ok(d00, u, v) & ok(d10, u + s, v) & ok(d01, u, v + s)
     u, v, d00, d10, d01 = u[keep], v[keep], d00[keep], d10[keep], d01[keep]
+    left.append(u.size)
     with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
         dcx0 = (u.astype(f32) - cx) / fx
         dcx1 = ((u + s).astype(f32) - cx) / fx
@@ -107,10 +117,12 @@ def pair_terms(live, model, level, Rm, tm, P):
         n = [b[1] * a[2] - b[2] * a[1], b[2] * a[0] - b[0] * a[2], b[0] * a[1] - b[1] * a[0]]
         ln = np.sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2])
         keep = np.isfinite(ln) & (ln > f32(0))
+        left.append(int(keep.sum()))
         n = [x / ln for x in n]
         Pp = [((Rm[k, 0] * V[0] + Rm[k, 1] * V[1]) + Rm[k, 2] * V[2]) + tm[k] for k in range(3)]
         nl = [(Rm[k, 0] * n[0] + Rm[k, 1] * n[1]) + Rm[k, 2] * n[2] for k in range(3)]
         keep &= Pp[2] > f32(0)
+        left.append(int(keep.sum()))
         pu = fx * (Pp[0] / Pp[2]) + cx
         pv = fy * (Pp[1] / Pp[2]) + cy
         keep &= np.isfinite(pu) & np.isfinite(pv) & (pu >= f32(-0.5)) & (pu < f32(W) - f32(0.5)) & \
@@ -119,22 +131,32 @@ def pair_terms(live, model, level, Rm, tm, P):
         fv = np.floor(np.where(keep, pv, f32(0)) + f32(0.5))
     ui, vi = fu.astype(np.int64), fv.astype(np.int64)
     keep &= (ui >= 0) & (ui < W) & (vi >= 0) & (vi < H)
+    left.append(int(keep.sum()))
     ui, vi = np.where(keep, ui, 0), np.where(keep, vi, 0)
     t = np.asarray(mdepth, f32)[vi, ui]
     nm = np.asarray(mnormal, f32)[vi, ui]
     nm = [nm[:, 0], nm[:, 1], nm[:, 2]]
     keep &= (t > f32(0)) & ~((nm[0] == 0) & (nm[1] == 0) & (nm[2] == 0))
+    left.append(int(keep.sum()))
     dist2 = P["dist"][level] * P["dist"][level]
     with np.errstate(invalid="ignore", over="ignore"):
         q = [t * ((ui.astype(f32) - cx) / fx), t * ((vi.astype(f32) - cy) / fy), t]
         e = [Pp[k] - q[k] for k in range(3)]
         keep &= ((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]) <= dist2
+        left.append(int(keep.sum()))
         keep &= ((nl[0] * nm[0] + nl[1] * nm[1]) + nl[2] * nm[2]) >= P["cos"]
         sel = lambda x: x[keep]
         e, nm, Pp = [sel(x) for x in e], [sel(x) for x in nm], [sel(x) for x in Pp]
         r = (nm[0] * e[0] + nm[1] * e[1]) + nm[2] * e[2]
         J = [Pp[1] * nm[2] - Pp[2] * nm[1], Pp[2] * nm[0] - Pp[0] * nm[2], Pp[0] * nm[1] - Pp[1] * nm[0], nm[0], nm[1], nm[2]]
         cols = [J[a] * J[b] for a, b in UPPER] + [J[a] * r for a in range(6)] + [r * r, np.ones_like(r)]
+    if info is not None:
+        left.append(int(keep.sum()))
+        ni = (W - 1 - s) // s + 1 if W > s else 0
+        info["samples"] = left[0]
+        info["rejected"] = {g: left[k] - left[k + 1] for k, g in enumerate(GATES)}
+        info["idx"] = (v[keep] // s) * ni + u[keep] // s
+        info["model_px"] = (ui[keep], vi[keep])
     return np.stack(cols, axis=1).astype(f32), (u[keep], v[keep])
 
 
@@ -152,15 +174,20 @@ def unpack(sys):
     return A, np.asarray(sys[21:27]), float(sys[27]), float(sys[28])
 
 
-def cholesky_solve(sys):
-    """xi of A xi = -b, or None when a pivot is <= 1e-12 * max diagonal (the rule's loop, in double)."""
+def cholesky_solve(sys, info=None):
+    """xi of A xi = -b, or None when a pivot is <= 1e-12 * max diagonal (the rule's loop, in double).  info, a dict, receives
+    "pivot_ratio": the smallest pivot met over 1e-12 * max diagonal (<= 1 exactly when lost; 0 for an all-zero diagonal)."""
     A, b, _, _ = unpack(sys)
     dmax = max(A[a, a] for a in range(6))
     L = np.zeros((6, 6))
+    ratio = math.inf
     for c in range(6):
         piv = A[c, c]
         for j in range(c):
             piv -= L[c, j] * L[c, j]
+        ratio = min(ratio, piv / (1e-12 * dmax) if dmax > 0.0 else 0.0)
+        if info is not None:
+            info["pivot_ratio"] = ratio
         if not piv > 1e-12 * dmax:
             return None
         L[c, c] = math.sqrt(piv)
@@ -194,14 +221,29 @@ def rodrigues(w):
 
 
 def step(M, xi):
-    R = rodrigues(xi[:3])
+    """[Rodrigues(w) | tau] * M in the device's order of operations (sums over k left to right, no contraction)."""
+    w = [float(x) for x in xi[:3]]
+    th = math.sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2])
+    R = [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]]
+    if th > 0.0:
+        kx, ky, kz = w[0] / th, w[1] / th, w[2] / th
+        sn, cs = math.sin(th), 1.0 - math.cos(th)
+        Kx = [[0.0, -kz, ky], [kz, 0.0, -kx], [-ky, kx, 0.0]]
+        for a in range(3):
+            for b in range(3):
+                k2 = (Kx[a][0] * Kx[0][b] + Kx[a][1] * Kx[1][b]) + Kx[a][2] * Kx[2][b]
+                R[a][b] = (R[a][b] + sn * Kx[a][b]) + cs * k2
     out = np.zeros((3, 4))
-    out[:, :3] = R @ M[:, :3]
-    out[:, 3] = R @ M[:, 3] + xi[3:]
+    for a in range(3):
+        for b in range(3):
+            out[a, b] = (R[a][0] * M[0, b] + R[a][1] * M[1, b]) + R[a][2] * M[2, b]
+        out[a, 3] = ((R[a][0] * M[0, 3] + R[a][1] * M[1, 3]) + R[a][2] * M[2, 3]) + float(xi[3 + a])
     return out
 
 
-def track(live, model, P, M0=None):
+def track(live, model, P, M0=None, history=None):
+    """history, a list, receives one dict per iteration that ran: level, pairs, w and tau (|w|, |tau| of the step; None when
+    there was none), pivot_ratio (cholesky_solve's; None when min_inliers decided), lost, done."""
     M = np.hstack([np.eye(3), np.zeros((3, 1))]) if M0 is None else np.asarray(M0, np.float64).copy()
     lost, done, iters_run, inliers, r2 = False, [0, 0, 0], [0, 0, 0], 0, 0.0
     for lvl in range(P["n_levels"] - 1, -1, -1):
@@ -211,15 +253,20 @@ def track(live, model, P, M0=None):
             sys, _ = system(live, model, lvl, M, P)
             inliers, r2 = int(sys[28]), float(sys[27])
             iters_run[lvl] += 1
-            xi = cholesky_solve(sys) if sys[28] >= P["min_inliers"] else None
+            note = {"level": lvl, "pairs": inliers, "w": None, "tau": None, "pivot_ratio": None, "lost": False, "done": False}
+            if history is not None:
+                history.append(note)
+            xi = cholesky_solve(sys, note) if sys[28] >= P["min_inliers"] else None
             if xi is None:
-                lost = True
+                lost = note["lost"] = True
                 break
             M = step(M, xi)
             th = math.sqrt((xi[0] * xi[0] + xi[1] * xi[1]) + xi[2] * xi[2])
             tn = math.sqrt((xi[3] * xi[3] + xi[4] * xi[4]) + xi[5] * xi[5])
+            note["w"], note["tau"] = th, tn
             if th < P["eps_rot"] and tn < P["eps_trans"]:
                 done[lvl] = 1
+                note["done"] = True
     ran = [lvl for lvl in range(P["n_levels"]) if P["iters"][lvl] > 0]
     status = 2 if lost else (0 if ran and done[ran[0]] else 1)
     return {"M": M, "status": status, "iters_run": iters_run, "inliers": inliers, "lost": lost,
