@@ -1,6 +1,8 @@
-// tsdf_capi.hip -- implementation of include/tsdf_hip.h (libtsdf_hip.so).  Handles, integration, batches, extraction and files
-// are here; raycasting, tracking, merging, association and segmentation each in a tsdf_<feature>_host.hip.h beside its kernels,
-// the group in tsdf_group.hip.h and include/tsdf_hip_diag.h in tsdf_diag.hip.h, all included at the end (one translation unit).
+// tsdf_capi.hip -- implementation of include/tsdf_hip.h (libtsdf_hip.so).  Handles, integration, labels, colour and batches
+// are here; raycasting, tracking, merging, extents, association and segmentation each in a tsdf_<feature>_host.hip.h beside its
+// kernels, extraction, the file writers and the checkpoint calls in tsdf_extract_host.hip.h (the file formats themselves in
+// mesh_files.h, host-only), the group in tsdf_group.hip.h and include/tsdf_hip_diag.h in tsdf_diag.hip.h, all included at the
+// end (one translation unit).
 //
 // One handle = one z-slab of the voxel grid resident in HBM on one device + one HIP stream.
 // Host work per frame is the 4x4 pose composition (pose_math.h) and one kernel launch; the
@@ -23,7 +25,6 @@
 #include <cstring>
 #include <new>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "pose_math.h"
@@ -1078,111 +1079,6 @@ int fill(tsdf_volume *v)
     return TSDF_OK;
 }
 
-// ---- file writers shared by the single-handle and the group entry points ---------------------------------------
-// .ply of surface points: header text of ref: src/tsdf.cu:185-192 (the vertex count is printed with %d there)
-int write_points_ply(const char *path, const float *xyz, int64_t n, const char *who)
-{
-    FILE *fp = std::fopen(path, "w");
-    if (!fp) return fail(TSDF_ERR_IO, "%s: cannot open %s", who, path);
-    std::fprintf(fp, "ply\nformat binary_little_endian 1.0\nelement vertex %d\n", (int)n);
-    std::fprintf(fp, "property float x\nproperty float y\nproperty float z\nend_header\n");
-    size_t wrote = std::fwrite(xyz, sizeof(float), (size_t)n * 3, fp);
-    int bad = std::fclose(fp);
-    if (wrote != (size_t)n * 3 || bad) return fail(TSDF_ERR_IO, "%s: short write to %s", who, path);
-    return TSDF_OK;
-}
-
-// binary .ply with vertex + face elements, three vertices per triangle; rgb (may be null): 3 bytes per vertex
-int write_mesh_ply(const char *path, const float *tri, int64_t n, const char *who, const unsigned char *rgb = nullptr)
-{
-    FILE *fp = std::fopen(path, "wb");
-    if (!fp) return fail(TSDF_ERR_IO, "%s: cannot open %s", who, path);
-    std::fprintf(fp, "ply\nformat binary_little_endian 1.0\nelement vertex %lld\n", (long long)(3 * n));
-    std::fprintf(fp, "property float x\nproperty float y\nproperty float z\n");
-    if (rgb) std::fprintf(fp, "property uchar red\nproperty uchar green\nproperty uchar blue\n");
-    std::fprintf(fp, "element face %lld\nproperty list uchar int vertex_indices\nend_header\n", (long long)n);
-    size_t ok = 0, want = 0;
-    if (rgb) {
-        std::vector<unsigned char> rec((size_t)(n > 0 ? n : 1) * 3 * 15);
-        for (int64_t k = 0; k < 3 * n; ++k) {
-            std::memcpy(rec.data() + 15 * k, tri + 3 * k, 12);
-            std::memcpy(rec.data() + 15 * k + 12, rgb + 3 * k, 3);
-        }
-        ok = std::fwrite(rec.data(), 15, (size_t)n * 3, fp);
-        want = (size_t)n * 3;
-    } else {
-        ok = std::fwrite(tri, sizeof(float), (size_t)n * 9, fp);
-        want = (size_t)n * 9;
-    }
-    std::vector<unsigned char> faces((size_t)(n > 0 ? n : 1) * 13);
-    for (int64_t f = 0; f < n; ++f) {
-        unsigned char *rec = faces.data() + 13 * f;
-        rec[0] = 3;
-        for (int k = 0; k < 3; ++k) { const int32_t idx = (int32_t)(3 * f + k); std::memcpy(rec + 1 + 4 * k, &idx, 4); }
-    }
-    ok += std::fwrite(faces.data(), 13, (size_t)n, fp);
-    int bad = std::fclose(fp);
-    if (ok != want + (size_t)n || bad) return fail(TSDF_ERR_IO, "%s: short write to %s", who, path);
-    return TSDF_OK;
-}
-
-// ref: src/tsdf.cu:119-129 -- dims as floats, origin, voxel size, truncation margin, then the TSDF values
-int write_bin(const char *path, int dx, int dy, int dz, const float origin[3], float vs, float trunc, const float *data,
-              int64_t n, const char *who)
-{
-    FILE *fp = std::fopen(path, "wb");
-    if (!fp) return fail(TSDF_ERR_IO, "%s: cannot open %s", who, path);
-    float hdr[8] = {(float)dx, (float)dy, (float)dz, origin[0], origin[1], origin[2], vs, trunc};
-    size_t ok = std::fwrite(hdr, sizeof(float), 8, fp);
-    ok += std::fwrite(data, sizeof(float), (size_t)n, fp);  // one write, not one per float
-    int bad = std::fclose(fp);
-    if (ok != 8 + (size_t)n || bad) return fail(TSDF_ERR_IO, "%s: short write to %s", who, path);
-    return TSDF_OK;
-}
-
-// Device memory to an open file at the rate of the slower of PCIe and the file system: pieces of 32 MiB go device -> pinned host
-// buffer on the handle's stream while the previous piece is being written (the reference's writers scan and write float by
-// float, ref: src/tsdf.cu:130-131,210-212; a whole-array download into a fresh std::vector first costs a zero fill, a pageable
-// copy and the write, one after the other: 300 ms for a 512^3 .bin against 150 ms this way).  The two buffers are process-wide
-// (files are written rarely and the disk serialises writers anyway); the lock is held for the length of one array.
-struct FileStager {
-    std::mutex mu;
-    HostPtr<char> pin[2];                    // portable: any device may copy into them
-    static constexpr size_t kPiece = (size_t)32 << 20;
-};
-FileStager &file_stager() { static FileStager s; return s; }
-
-// bytes of device memory `src` (on v's device) appended to fp; the stream must already hold everything `src` depends on
-int stream_device_to_file(tsdf_volume *v, FILE *fp, const void *src, size_t bytes, const char *who, const char *path)
-{
-    if (bytes == 0) return TSDF_OK;
-    FileStager &fs = file_stager();
-    std::lock_guard<std::mutex> lk(fs.mu);
-    for (int i = 0; i < 2; ++i)
-        if (!fs.pin[i]) HIP_TRY(host_alloc(fs.pin[i], FileStager::kPiece, hipHostMallocPortable));
-    // the events belong to the device of v's stream (the current one: every caller has bound it), so they live for the call
-    Event ev[2];
-    hipError_t e = event_create(ev[0]);
-    if (e == hipSuccess) e = event_create(ev[1]);
-    const size_t pieces = (bytes + FileStager::kPiece - 1) / FileStager::kPiece;
-    auto len = [&](size_t k) { return k + 1 < pieces ? FileStager::kPiece : bytes - k * FileStager::kPiece; };
-    bool short_write = false;
-    for (size_t k = 0; e == hipSuccess && k <= pieces; ++k) {
-        if (k < pieces) {     // piece k on its way ...
-            e = hipMemcpyAsync(fs.pin[k & 1], (const char *)src + k * FileStager::kPiece, len(k), hipMemcpyDeviceToHost, v->stream);
-            if (e == hipSuccess) e = hipEventRecord(ev[k & 1], v->stream);
-        }
-        if (e == hipSuccess && k > 0) {          // ... while piece k - 1 is written
-            e = hipEventSynchronize(ev[(k - 1) & 1]);
-            if (e == hipSuccess && !short_write && std::fwrite(fs.pin[(k - 1) & 1], 1, len(k - 1), fp) != len(k - 1)) short_write = true;
-        }
-    }
-    if (e != hipSuccess) (void)hipStreamSynchronize(v->stream);     // nothing may still be writing into the buffers
-    if (e != hipSuccess) return fail(TSDF_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    if (short_write) return fail(TSDF_ERR_IO, "%s: short write to %s", who, path);
-    return TSDF_OK;
-}
-
 #ifdef TSDF_EXPERIMENTS
 #include "tsdf_experiments_host.hip.h"
 #endif
@@ -2111,353 +2007,6 @@ int tsdf_batch_integrate_device(tsdf_batch *b, const float *depth_dev, const uin
     return TSDF_OK;
 }
 
-// ---------------------------------------------------------------------------------------------
-// surface extraction (ref: src/tsdf.cu:170-218), on the device
-// ---------------------------------------------------------------------------------------------
-// xyz_host == nullptr with keep_on_device: the list is left in v->d_list (the file writers stream it from there)
-static int surface_pass(tsdf_volume *v, float weight_thresh, float *xyz_host, int64_t capacity,
-                        int64_t *count, bool keep_on_device = false)
-{
-    int rc = bind_device(v);
-    if (rc) return rc;
-    *count = 0;
-    if (v->n_vox == 0) return TSDF_OK;
-    const int64_t n = v->n_vox;
-    const int64_t n_chunks = (n + tsdfx::kChunk - 1) / tsdfx::kChunk;
-    if (n_chunks > 0x7fffffff) return fail(TSDF_ERR_INVALID, "surface extraction: slab too large");
-    // scratch: per-chunk counts (u32) then per-chunk offsets (i64) then total (i64)
-    size_t off_counts = 0;
-    size_t off_offsets = ((size_t)n_chunks * sizeof(uint32_t) + 255) & ~(size_t)255;
-    size_t off_total = off_offsets + (size_t)n_chunks * sizeof(int64_t);
-    size_t need = off_total + 256;
-    HIP_TRY(v->d_scratch.ensure(need));
-    char *s = (char *)v->d_scratch;
-    uint32_t *d_counts = (uint32_t *)(s + off_counts);
-    int64_t *d_offsets = (int64_t *)(s + off_offsets);
-    int64_t *d_total = (int64_t *)(s + off_total);
-
-    hipLaunchKernelGGL(tsdfx::surface_count, dim3((unsigned)n_chunks), dim3(256), 0, v->stream,
-                       v->d_tsdf, v->d_weight, n, weight_thresh, d_counts);
-    hipLaunchKernelGGL(tsdfx::scan_counts, dim3(1), dim3(1024), 0, v->stream, d_counts, n_chunks,
-                       d_offsets, d_total);
-    HIP_TRY(hipGetLastError());
-    int64_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, v->stream));
-    HIP_TRY(hipStreamSynchronize(v->stream));
-    *count = total;
-    if ((!xyz_host && !keep_on_device) || capacity <= 0 || total == 0) return TSDF_OK;
-
-    int64_t n_out = total < capacity ? total : capacity;
-    HIP_TRY(v->d_list.ensure((size_t)total * 3 * sizeof(float)));
-    float *d_xyz = reinterpret_cast<float *>(v->d_list.get());
-    const tsdf_config &c = v->cfg;
-    hipLaunchKernelGGL(tsdfx::surface_emit, dim3((unsigned)n_chunks), dim3(256), 0, v->stream,
-                       v->d_tsdf, v->d_weight, n, weight_thresh, d_offsets, c.dim_x, c.dim_y,
-                       c.z_begin, c.origin[0], c.origin[1], c.origin[2], c.voxel_size, d_xyz);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && xyz_host)
-        e = hipMemcpyAsync(xyz_host, d_xyz, (size_t)n_out * 3 * sizeof(float), hipMemcpyDeviceToHost, v->stream);
-    if (e == hipSuccess && xyz_host) e = hipStreamSynchronize(v->stream);
-    if (e != hipSuccess) return fail(TSDF_ERR_HIP, "surface extraction: %s", hipGetErrorString(e));
-    return TSDF_OK;
-}
-
-int tsdf_count_surface(tsdf_volume *v, float weight_thresh, int64_t *count)
-{
-    if (!v || !count) return fail(TSDF_ERR_INVALID, "tsdf_count_surface: NULL argument");
-    return surface_pass(v, weight_thresh, nullptr, 0, count);
-}
-
-int tsdf_extract_surface(tsdf_volume *v, float weight_thresh, float *xyz_host, int64_t capacity,
-                         int64_t *count)
-{
-    if (!v || !count) return fail(TSDF_ERR_INVALID, "tsdf_extract_surface: NULL argument");
-    return surface_pass(v, weight_thresh, xyz_host, capacity, count);
-}
-
-// Zero-crossing vertices.  halo_*: slice z_end from the upper neighbour (host or device memory) or NULL.
-static int crossing_pass(tsdf_volume *v, const float *halo_tsdf, const float *halo_weight, float weight_thresh,
-                         float *xyz_host, int64_t capacity, int64_t *count, bool mesh = false)
-{
-    const size_t item_floats = mesh ? 9 : 3;   // triangle = 3 vertices, crossing = 1 vertex
-    int rc = bind_device(v);
-    if (rc) return rc;
-    *count = 0;
-    if (v->n_vox == 0) return TSDF_OK;
-    if ((halo_tsdf == nullptr) != (halo_weight == nullptr))
-        return fail(TSDF_ERR_INVALID, "zero crossings: give both halo arrays or neither");
-    const tsdf_config &c = v->cfg;
-    const int64_t n = v->n_vox;
-    const int64_t n_chunks = (n + tsdfx::kChunk - 1) / tsdfx::kChunk;
-    if (n_chunks > 0x7fffffff) return fail(TSDF_ERR_INVALID, "zero crossings: slab too large");
-    const size_t slice = (size_t)c.dim_x * c.dim_y;
-    // scratch: counts (u32) | offsets (i64) | total (i64) | halo copy (2 slices of floats)
-    size_t off_offsets = ((size_t)n_chunks * sizeof(uint32_t) + 255) & ~(size_t)255;
-    size_t off_total = off_offsets + (size_t)n_chunks * sizeof(int64_t);
-    size_t off_halo = (off_total + 256 + 255) & ~(size_t)255;
-    HIP_TRY(v->d_scratch.ensure(off_halo + 2 * slice * sizeof(float)));
-    char *s = (char *)v->d_scratch;
-    uint32_t *d_counts = (uint32_t *)s;
-    int64_t *d_offsets = (int64_t *)(s + off_offsets);
-    int64_t *d_total = (int64_t *)(s + off_total);
-    float *d_halo = (float *)(s + off_halo);
-    tsdfx::CrossingGrid g;
-    g.tsdf = v->d_tsdf; g.weight = v->d_weight; g.halo_tsdf = nullptr; g.halo_weight = nullptr;
-    if (halo_tsdf) {   // host or device source: stage both slices in our scratch
-        HIP_TRY(hipMemcpyAsync(d_halo, halo_tsdf, slice * sizeof(float), hipMemcpyDefault, v->stream));
-        HIP_TRY(hipMemcpyAsync(d_halo + slice, halo_weight, slice * sizeof(float), hipMemcpyDefault, v->stream));
-        g.halo_tsdf = d_halo; g.halo_weight = d_halo + slice;
-    }
-    g.n = n; g.dim_x = c.dim_x; g.dim_y = c.dim_y; g.nz = c.z_end - c.z_begin; g.z_begin = c.z_begin;
-    g.thr = weight_thresh; g.ox = c.origin[0]; g.oy = c.origin[1]; g.oz = c.origin[2]; g.vs = c.voxel_size;
-    g.flags = v->nseg > 0 ? v->d_flags : nullptr; g.nseg = v->nseg;     // segments that are all free / unseen space are skipped
-    if (mesh) hipLaunchKernelGGL(tsdfx::mesh_count, dim3((unsigned)n_chunks), dim3(256), 0, v->stream, g, d_counts);
-    else hipLaunchKernelGGL(tsdfx::crossing_count, dim3((unsigned)n_chunks), dim3(256), 0, v->stream, g, d_counts);
-    hipLaunchKernelGGL(tsdfx::scan_counts, dim3(1), dim3(1024), 0, v->stream, d_counts, n_chunks, d_offsets, d_total);
-    HIP_TRY(hipGetLastError());
-    int64_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, v->stream));
-    HIP_TRY(hipStreamSynchronize(v->stream));
-    *count = total;
-    if (!xyz_host || capacity <= 0 || total == 0) return TSDF_OK;
-    const int64_t n_out = total < capacity ? total : capacity;
-    HIP_TRY(v->d_list.ensure((size_t)total * item_floats * sizeof(float)));
-    float *d_xyz = reinterpret_cast<float *>(v->d_list.get());
-    if (mesh) hipLaunchKernelGGL(tsdfx::mesh_emit_kernel, dim3((unsigned)n_chunks), dim3(256), 0, v->stream, g, d_offsets, d_xyz);
-    else hipLaunchKernelGGL(tsdfx::crossing_emit, dim3((unsigned)n_chunks), dim3(256), 0, v->stream, g, d_offsets, d_xyz);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(xyz_host, d_xyz, (size_t)n_out * item_floats * sizeof(float), hipMemcpyDeviceToHost, v->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(v->stream);
-    if (e != hipSuccess) return fail(TSDF_ERR_HIP, "zero crossings: %s", hipGetErrorString(e));
-    return TSDF_OK;
-}
-
-int tsdf_extract_crossings(tsdf_volume *v, const float *halo_tsdf, const float *halo_weight, float weight_thresh,
-                           float *xyz_host, int64_t capacity, int64_t *count)
-{
-    if (!v || !count) return fail(TSDF_ERR_INVALID, "tsdf_extract_crossings: NULL argument");
-    return crossing_pass(v, halo_tsdf, halo_weight, weight_thresh, xyz_host, capacity, count);
-}
-
-int tsdf_extract_mesh(tsdf_volume *v, const float *halo_tsdf, const float *halo_weight, float weight_thresh,
-                      float *triangles_host, int64_t capacity, int64_t *count)
-{
-    if (!v || !count) return fail(TSDF_ERR_INVALID, "tsdf_extract_mesh: NULL argument");
-    return crossing_pass(v, halo_tsdf, halo_weight, weight_thresh, triangles_host, capacity, count, true);
-}
-
-int tsdf_save_mesh_ply(tsdf_volume *v, const char *path, float weight_thresh)
-{
-    if (!v || !path) return fail(TSDF_ERR_INVALID, "tsdf_save_mesh_ply: NULL argument");
-    int64_t n = 0;
-    int rc = crossing_pass(v, nullptr, nullptr, weight_thresh, nullptr, 0, &n, true);
-    if (rc) return rc;
-    std::vector<float> tri((size_t)(n > 0 ? n : 1) * 9);
-    if (n > 0) {
-        rc = crossing_pass(v, nullptr, nullptr, weight_thresh, tri.data(), n, &n, true);
-        if (rc) return rc;
-    }
-    if (v->d_colour) {
-        // vertex colour = colour of the nearest voxel (what the Python glue's get_mesh does with the rounded vertex indices)
-        std::vector<uint32_t> col((size_t)(v->n_vox > 0 ? v->n_vox : 1));
-        rc = tsdf_download_colour(v, col.data());
-        if (rc) return rc;
-        const tsdf_config &c = v->cfg;
-        const int nz = c.z_end - c.z_begin;
-        std::vector<unsigned char> rgb((size_t)(n > 0 ? n : 1) * 9);
-        for (int64_t k = 0; k < 3 * n; ++k) {
-            const float *p = tri.data() + 3 * k;
-            long ix = std::lround((p[0] - c.origin[0]) / c.voxel_size), iy = std::lround((p[1] - c.origin[1]) / c.voxel_size);
-            long iz = std::lround((p[2] - c.origin[2]) / c.voxel_size) - c.z_begin;
-            ix = std::min<long>(std::max<long>(ix, 0), c.dim_x - 1);
-            iy = std::min<long>(std::max<long>(iy, 0), c.dim_y - 1);
-            iz = std::min<long>(std::max<long>(iz, 0), nz - 1);
-            const uint32_t q = col[((size_t)iz * c.dim_y + (size_t)iy) * c.dim_x + (size_t)ix];
-            rgb[3 * k] = (unsigned char)(q & 255u); rgb[3 * k + 1] = (unsigned char)((q >> 8) & 255u);
-            rgb[3 * k + 2] = (unsigned char)((q >> 16) & 255u);
-        }
-        return write_mesh_ply(path, tri.data(), n, "tsdf_save_mesh_ply", rgb.data());
-    }
-    return write_mesh_ply(path, tri.data(), n, "tsdf_save_mesh_ply");
-}
-
-// The mesh as the reference's Python glue saves it (ref: src/TSDFfusion.py.in:48-53: get_mesh -> verts, faces, norms,
-// colors -> meshwrite): shared vertices, a normal per vertex, a colour per vertex when colour is enabled.  The triangle soup's
-// edge vertices are bit-identical between neighbouring cubes (tsdf_extract.hip.h), so welding is an exact match on the three
-// coordinates' bits; normals are the area-weighted sums of the face normals; faces keep the soup's order and winding.
-int tsdf_save_mesh_welded_ply(tsdf_volume *v, const char *path, float weight_thresh)
-{
-    if (!v || !path) return fail(TSDF_ERR_INVALID, "tsdf_save_mesh_welded_ply: NULL argument");
-    int64_t n = 0;
-    int rc = crossing_pass(v, nullptr, nullptr, weight_thresh, nullptr, 0, &n, true);
-    if (rc) return rc;
-    if (3 * n > 0x7fffffffll) return fail(TSDF_ERR_INVALID, "tsdf_save_mesh_welded_ply: %lld triangles exceed 32-bit vertex indices", (long long)n);
-    std::vector<float> tri((size_t)(n > 0 ? n : 1) * 9);
-    if (n > 0 && (rc = crossing_pass(v, nullptr, nullptr, weight_thresh, tri.data(), n, &n, true)) != TSDF_OK) return rc;
-    struct Key { uint32_t x, y, z; bool operator==(const Key &o) const { return x == o.x && y == o.y && z == o.z; } };
-    struct Hash { size_t operator()(const Key &k) const { uint64_t h = k.x * 0x9E3779B97F4A7C15ull; h ^= (h >> 29) + k.y * 0xBF58476D1CE4E5B9ull; h ^= (h >> 31) + k.z * 0x94D049BB133111EBull; return (size_t)(h ^ (h >> 32)); } };
-    std::unordered_map<Key, int32_t, Hash> ids;
-    ids.reserve((size_t)n);
-    std::vector<float> verts;
-    std::vector<int32_t> faces((size_t)(n > 0 ? n : 1) * 3);
-    for (int64_t k = 0; k < 3 * n; ++k) {
-        Key key;
-        std::memcpy(&key, tri.data() + 3 * k, 12);
-        auto it = ids.find(key);
-        if (it == ids.end()) {
-            it = ids.emplace(key, (int32_t)(verts.size() / 3)).first;
-            verts.insert(verts.end(), tri.data() + 3 * k, tri.data() + 3 * k + 3);
-        }
-        faces[(size_t)k] = it->second;
-    }
-    const size_t nv = verts.size() / 3;
-    std::vector<double> acc(nv * 3 + 3, 0.0);
-    for (int64_t f = 0; f < n; ++f) {
-        const float *a = tri.data() + 9 * f, *b = a + 3, *c = a + 6;
-        const double ux = (double)b[0] - a[0], uy = (double)b[1] - a[1], uz = (double)b[2] - a[2];
-        const double wx = (double)c[0] - a[0], wy = (double)c[1] - a[1], wz = (double)c[2] - a[2];
-        const double nx = uy * wz - uz * wy, ny = uz * wx - ux * wz, nz = ux * wy - uy * wx;   // 2 x area x unit normal
-        for (int k = 0; k < 3; ++k) { double *q = acc.data() + 3 * (size_t)faces[(size_t)(3 * f + k)]; q[0] += nx; q[1] += ny; q[2] += nz; }
-    }
-    std::vector<uint32_t> col;
-    if (v->d_colour) {
-        col.resize((size_t)(v->n_vox > 0 ? v->n_vox : 1));
-        rc = tsdf_download_colour(v, col.data());
-        if (rc) return rc;
-    }
-    const tsdf_config &c = v->cfg;
-    const int nz_ = c.z_end - c.z_begin;
-    const size_t rec_bytes = 24 + (v->d_colour ? 3 : 0);
-    std::vector<unsigned char> rec((nv > 0 ? nv : 1) * rec_bytes);
-    for (size_t i = 0; i < nv; ++i) {
-        const float *p = verts.data() + 3 * i;
-        const double *q = acc.data() + 3 * i;
-        const double len = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]);
-        const float nrm[3] = {len > 0 ? (float)(q[0] / len) : 0.0f, len > 0 ? (float)(q[1] / len) : 0.0f, len > 0 ? (float)(q[2] / len) : 0.0f};
-        unsigned char *r = rec.data() + i * rec_bytes;
-        std::memcpy(r, p, 12);
-        std::memcpy(r + 12, nrm, 12);
-        if (v->d_colour) {   // the nearest voxel's colour (the Python glue indexes its colour volume with the rounded vertex)
-            long ix = std::lround((p[0] - c.origin[0]) / c.voxel_size), iy = std::lround((p[1] - c.origin[1]) / c.voxel_size);
-            long iz = std::lround((p[2] - c.origin[2]) / c.voxel_size) - c.z_begin;
-            ix = std::min<long>(std::max<long>(ix, 0), c.dim_x - 1);
-            iy = std::min<long>(std::max<long>(iy, 0), c.dim_y - 1);
-            iz = std::min<long>(std::max<long>(iz, 0), nz_ - 1);
-            const uint32_t u = col[((size_t)iz * c.dim_y + (size_t)iy) * c.dim_x + (size_t)ix];
-            r[24] = (unsigned char)(u & 255u); r[25] = (unsigned char)((u >> 8) & 255u); r[26] = (unsigned char)((u >> 16) & 255u);
-        }
-    }
-    FILE *fp = std::fopen(path, "wb");
-    if (!fp) return fail(TSDF_ERR_IO, "tsdf_save_mesh_welded_ply: cannot open %s", path);
-    std::fprintf(fp, "ply\nformat binary_little_endian 1.0\nelement vertex %zu\n", nv);
-    std::fprintf(fp, "property float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\n");
-    if (v->d_colour) std::fprintf(fp, "property uchar red\nproperty uchar green\nproperty uchar blue\n");
-    std::fprintf(fp, "element face %lld\nproperty list uchar int vertex_index\nend_header\n", (long long)n);
-    size_t ok = std::fwrite(rec.data(), rec_bytes, nv, fp);
-    std::vector<unsigned char> fr((size_t)(n > 0 ? n : 1) * 13);
-    for (int64_t f = 0; f < n; ++f) { fr[13 * f] = 3; std::memcpy(fr.data() + 13 * f + 1, faces.data() + 3 * f, 12); }
-    ok += std::fwrite(fr.data(), 13, (size_t)n, fp);
-    const int bad = std::fclose(fp);
-    if (ok != nv + (size_t)n || bad) return fail(TSDF_ERR_IO, "tsdf_save_mesh_welded_ply: short write to %s", path);
-    return TSDF_OK;
-}
-
-int tsdf_save_ply(tsdf_volume *v, const char *path, float weight_thresh)
-{
-    if (!v || !path) return fail(TSDF_ERR_INVALID, "tsdf_save_ply: NULL argument");
-    // one counting + emitting pass that leaves the points in device memory, then header + list streamed to the file
-    int64_t n = 0;
-    int rc = surface_pass(v, weight_thresh, nullptr, INT64_MAX, &n, true);
-    if (rc) return rc;
-    if (n > 0x7fffffffll)   // the header's "element vertex %d" (ref: src/tsdf.cu:188) cannot hold it
-        return fail(TSDF_ERR_INVALID, "tsdf_save_ply: %lld surface points exceed the format's 2^31 - 1 (write slabs separately)", (long long)n);
-    FILE *fp = std::fopen(path, "w");
-    if (!fp) return fail(TSDF_ERR_IO, "tsdf_save_ply: cannot open %s", path);
-    bool ok = std::fprintf(fp, "ply\nformat binary_little_endian 1.0\nelement vertex %d\n", (int)n) > 0 &&
-              std::fprintf(fp, "property float x\nproperty float y\nproperty float z\nend_header\n") > 0;
-    rc = ok ? stream_device_to_file(v, fp, v->d_list, (size_t)n * 3 * sizeof(float), "tsdf_save_ply", path) : TSDF_OK;
-    const int bad = std::fclose(fp);
-    if (rc) return rc;
-    if (!ok || bad) return fail(TSDF_ERR_IO, "tsdf_save_ply: short write to %s", path);
-    return TSDF_OK;
-}
-
-int tsdf_save_bin(tsdf_volume *v, const char *path)
-{
-    if (!v || !path) return fail(TSDF_ERR_INVALID, "tsdf_save_bin: NULL argument");
-    int rc = bind_device(v);
-    if (rc) return rc;
-    const tsdf_config &c = v->cfg;
-    FILE *fp = std::fopen(path, "wb");
-    if (!fp) return fail(TSDF_ERR_IO, "tsdf_save_bin: cannot open %s", path);
-    const float hdr[8] = {(float)c.dim_x, (float)c.dim_y, (float)(c.z_end - c.z_begin), c.origin[0], c.origin[1], c.origin[2],
-                          c.voxel_size, c.trunc_margin};       // ref: src/tsdf.cu:118-129
-    const bool ok = std::fwrite(hdr, sizeof(float), 8, fp) == 8;
-    rc = ok ? stream_device_to_file(v, fp, v->d_tsdf, (size_t)v->n_vox * sizeof(float), "tsdf_save_bin", path) : TSDF_OK;
-    const int bad = std::fclose(fp);
-    if (rc) return rc;
-    if (!ok || bad) return fail(TSDF_ERR_IO, "tsdf_save_bin: short write to %s", path);
-    return TSDF_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// checkpoint / resume (the reference only ever writes: ref src/tsdf.cu:114-132; nothing reads a .bin back)
-// ---------------------------------------------------------------------------------------------
-int tsdf_load_bin(tsdf_volume *v, const char *path)
-{
-    if (!v || !path) return fail(TSDF_ERR_INVALID, "tsdf_load_bin: NULL argument");
-    FILE *fp = std::fopen(path, "rb");
-    if (!fp) return fail(TSDF_ERR_IO, "tsdf_load_bin: cannot open %s", path);
-    float hdr[8];
-    const tsdf_config &c = v->cfg;
-    const int nz = c.z_end - c.z_begin;
-    bool ok = std::fread(hdr, sizeof(float), 8, fp) == 8 && hdr[0] == (float)c.dim_x && hdr[1] == (float)c.dim_y &&
-              hdr[2] == (float)nz;
-    std::vector<float> host((size_t)(v->n_vox > 0 ? v->n_vox : 1));
-    ok = ok && std::fread(host.data(), sizeof(float), (size_t)v->n_vox, fp) == (size_t)v->n_vox;
-    std::fclose(fp);
-    if (!ok) return fail(TSDF_ERR_IO, "tsdf_load_bin: %s is not a %dx%dx%d TSDF dump", path, c.dim_x, c.dim_y, nz);
-    return tsdf_upload(v, host.data(), nullptr);   // weights are not in the reference's format
-}
-
-static const char kStateMagic[8] = {'T', 'S', 'D', 'F', 'H', 'I', 'P', '1'};
-
-int tsdf_save_state(tsdf_volume *v, const char *path)
-{
-    if (!v || !path) return fail(TSDF_ERR_INVALID, "tsdf_save_state: NULL argument");
-    int rc = bind_device(v);
-    if (rc) return rc;
-    FILE *fp = std::fopen(path, "wb");
-    if (!fp) return fail(TSDF_ERR_IO, "tsdf_save_state: cannot open %s", path);
-    const bool ok = std::fwrite(kStateMagic, 1, 8, fp) == 8 && std::fwrite(&v->cfg, sizeof(tsdf_config), 1, fp) == 1;
-    rc = ok ? stream_device_to_file(v, fp, v->d_tsdf, (size_t)v->n_vox * sizeof(float), "tsdf_save_state", path) : TSDF_OK;
-    if (ok && rc == TSDF_OK) rc = stream_device_to_file(v, fp, v->d_weight, (size_t)v->n_vox * sizeof(float), "tsdf_save_state", path);
-    const int bad = std::fclose(fp);
-    if (rc) return rc;
-    if (!ok || bad) return fail(TSDF_ERR_IO, "tsdf_save_state: short write to %s", path);
-    return TSDF_OK;
-}
-
-int tsdf_load_state(tsdf_volume *v, const char *path)
-{
-    if (!v || !path) return fail(TSDF_ERR_INVALID, "tsdf_load_state: NULL argument");
-    FILE *fp = std::fopen(path, "rb");
-    if (!fp) return fail(TSDF_ERR_IO, "tsdf_load_state: cannot open %s", path);
-    char magic[8];
-    tsdf_config c;
-    bool ok = std::fread(magic, 1, 8, fp) == 8 && std::memcmp(magic, kStateMagic, 8) == 0 &&
-              std::fread(&c, sizeof c, 1, fp) == 1;
-    ok = ok && c.dim_x == v->cfg.dim_x && c.dim_y == v->cfg.dim_y && c.dim_z == v->cfg.dim_z &&
-         c.z_begin == v->cfg.z_begin && c.z_end == v->cfg.z_end;
-    std::vector<float> t((size_t)(v->n_vox > 0 ? v->n_vox : 1)), w(t.size());
-    ok = ok && std::fread(t.data(), sizeof(float), (size_t)v->n_vox, fp) == (size_t)v->n_vox &&
-         std::fread(w.data(), sizeof(float), (size_t)v->n_vox, fp) == (size_t)v->n_vox;
-    std::fclose(fp);
-    if (!ok) return fail(TSDF_ERR_IO, "tsdf_load_state: %s does not hold the state of this slab", path);
-    return tsdf_upload(v, t.data(), w.data());
-}
-
 }  // extern "C"
 
 #include "tsdf_raycast_host.hip.h"
@@ -2466,5 +2015,6 @@ int tsdf_load_state(tsdf_volume *v, const char *path)
 #include "tsdf_extent_host.hip.h"
 #include "tsdf_associate_host.hip.h"
 #include "tsdf_segment_host.hip.h"
+#include "tsdf_extract_host.hip.h"
 #include "tsdf_group.hip.h"
 #include "tsdf_diag.hip.h"

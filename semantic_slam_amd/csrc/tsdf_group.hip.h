@@ -81,21 +81,17 @@ int fetch_halo(tsdf_group *g, int i, const float **ht, const float **hw)
     return TSDF_OK;
 }
 
-enum class ListKind { Surface, Crossings, Mesh };
-
 // count pass on every slab (concurrently), then -- when a destination is given -- the emit passes into the right offsets
 int group_list(tsdf_group *g, ListKind kind, float weight_thresh, float *out_host, int64_t capacity, int64_t *count)
 {
     int rc_flush = group_flush(g);
     if (rc_flush) return rc_flush;
     const int n = (int)g->slabs.size();
-    const size_t item = kind == ListKind::Mesh ? 9 : 3;
+    const size_t item = list_item_floats(kind);
     std::vector<int64_t> cnt((size_t)n, 0);
     std::vector<const float *> ht((size_t)n, nullptr), hw((size_t)n, nullptr);
     auto pass = [&](int i, float *dst, int64_t cap, int64_t *c) -> int {
-        tsdf_volume *v = g->slabs[(size_t)i];
-        if (kind == ListKind::Surface) return surface_pass(v, weight_thresh, dst, cap, c);
-        return crossing_pass(v, ht[(size_t)i], hw[(size_t)i], weight_thresh, dst, cap, c, kind == ListKind::Mesh);
+        return extract_pass(g->slabs[(size_t)i], kind, ht[(size_t)i], hw[(size_t)i], weight_thresh, ListDest::to_host(dst, cap), c);
     };
     int rc = for_each_slab(g, [&](int i) -> int {
         if (kind != ListKind::Surface) {
@@ -116,6 +112,12 @@ int group_list(tsdf_group *g, ListKind kind, float weight_thresh, float *out_hos
         int64_t c = 0;
         return pass(i, out_host + (size_t)off[(size_t)i] * item, room, &c);
     });
+}
+
+// the gathered lists of a group as count_then_fill asks for them
+ListFn group_lists(tsdf_group *g, float weight_thresh)
+{
+    return [=](ListKind kind, float *dst, int64_t capacity, int64_t *count) { return group_list(g, kind, weight_thresh, dst, capacity, count); };
 }
 
 // The first n frames of h_pool (already there) into every slab: one copy and one fused launch per slab.
@@ -396,48 +398,43 @@ int tsdf_group_extract_mesh(tsdf_group *g, float weight_thresh, float *triangles
 
 int tsdf_group_save_ply(tsdf_group *g, const char *path, float weight_thresh)
 {
-    if (!g || !path) return fail(TSDF_ERR_INVALID, "tsdf_group_save_ply: NULL argument");
+    const char *who = "tsdf_group_save_ply";
+    if (!g || !path) return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
+    std::vector<float> xyz;
     int64_t n = 0;
-    int rc = group_list(g, ListKind::Surface, weight_thresh, nullptr, 0, &n);
+    int rc = count_then_fill(group_lists(g, weight_thresh), ListKind::Surface, xyz, &n, [&](int64_t k) {
+        return k > 0x7fffffffll ? fail(TSDF_ERR_INVALID, "%s: %lld surface points exceed the format's 2^31 - 1", who, (long long)k) : TSDF_OK;
+    });
     if (rc) return rc;
-    if (n > 0x7fffffffll)
-        return fail(TSDF_ERR_INVALID, "tsdf_group_save_ply: %lld surface points exceed the format's 2^31 - 1", (long long)n);
-    std::vector<float> xyz((size_t)(n > 0 ? n : 1) * 3);
-    if (n > 0 && (rc = group_list(g, ListKind::Surface, weight_thresh, xyz.data(), n, &n)) != TSDF_OK) return rc;
-    return write_points_ply(path, xyz.data(), n, "tsdf_group_save_ply");
+    return io_result(mesh_files::write_points_ply(path, xyz.data(), n), who, path);
 }
 
 int tsdf_group_save_mesh_ply(tsdf_group *g, const char *path, float weight_thresh)
 {
-    if (!g || !path) return fail(TSDF_ERR_INVALID, "tsdf_group_save_mesh_ply: NULL argument");
+    const char *who = "tsdf_group_save_mesh_ply";
+    if (!g || !path) return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
+    std::vector<float> tri;
     int64_t n = 0;
-    int rc = group_list(g, ListKind::Mesh, weight_thresh, nullptr, 0, &n);
+    int rc = count_then_fill(group_lists(g, weight_thresh), ListKind::Mesh, tri, &n);
     if (rc) return rc;
-    std::vector<float> tri((size_t)(n > 0 ? n : 1) * 9);
-    if (n > 0 && (rc = group_list(g, ListKind::Mesh, weight_thresh, tri.data(), n, &n)) != TSDF_OK) return rc;
-    return write_mesh_ply(path, tri.data(), n, "tsdf_group_save_mesh_ply");
+    return io_result(mesh_files::write_mesh_ply(path, tri.data(), n, g->cfg), who, path);
 }
 
 int tsdf_group_save_bin(tsdf_group *g, const char *path)
 {
-    if (!g || !path) return fail(TSDF_ERR_INVALID, "tsdf_group_save_bin: NULL argument");
+    const char *who = "tsdf_group_save_bin";
+    if (!g || !path) return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
     int rc = group_flush(g);
     if (rc) return rc;
-    const tsdf_config &c = g->cfg;
-    FILE *fp = std::fopen(path, "wb");
-    if (!fp) return fail(TSDF_ERR_IO, "tsdf_group_save_bin: cannot open %s", path);
-    const float hdr[8] = {(float)c.dim_x, (float)c.dim_y, (float)c.dim_z, c.origin[0], c.origin[1], c.origin[2], c.voxel_size, c.trunc_margin};
-    const bool ok = std::fwrite(hdr, sizeof(float), 8, fp) == 8;
+    mesh_files::OutFile f(path, "wb");
+    mesh_files::write_bin_header(f, g->cfg);      // the group's cfg is the whole grid: z in [0, dim_z)
     // the slabs in z order, each streamed from its own device (the file is the whole grid's: ref src/tsdf.cu:118-131)
-    for (size_t i = 0; ok && rc == TSDF_OK && i < g->slabs.size(); ++i) {
+    for (size_t i = 0; f.good() && rc == TSDF_OK && i < g->slabs.size(); ++i) {
         tsdf_volume *v = g->slabs[i];
         if ((rc = bind_device(v)) != TSDF_OK) break;
-        rc = stream_device_to_file(v, fp, v->d_tsdf, (size_t)v->n_vox * sizeof(float), "tsdf_group_save_bin", path);
+        rc = stream_device_to_file(v, f.get(), v->d_tsdf, (size_t)v->n_vox * sizeof(float), who, path);
     }
-    const int bad = std::fclose(fp);
-    if (rc) return rc;
-    if (!ok || bad) return fail(TSDF_ERR_IO, "tsdf_group_save_bin: short write to %s", path);
-    return TSDF_OK;
+    return close_streamed(f, rc, who, path);
 }
 
 // The extent of the whole grid (tsdf_extent.hip.h): every slab's own record, the slabs concurrently, then combined in z
