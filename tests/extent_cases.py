@@ -13,8 +13,11 @@ K_SMALL = synth.TUM_K.copy()
 K_SMALL[[0, 2, 4, 5]] *= 0.25          # the TUM camera at a quarter of its resolution
 # a row of 5 quads (no multiple of the 8 quads a wavefront holds per row); one aligned wavefront row; partial workgroups in
 # every axis; a row longer than a workgroup's x tile; and rows that are no multiple of 4 voxels (the per-voxel path), odd in
-# every axis
-SHAPES = [(20, 12, 9), (64, 8, 5), (72, 33, 17), (260, 4, 3), (37, 22, 13)]
+# every axis.  Then the shapes with more than the 32 wavefront tiles (32 x 8 voxels) a workgroup takes per slice, uploaded
+# states only: 3 x 11 = 33 tiles of aligned rows (the second workgroup holds one tile and three wavefronts without any), 3 x 12 =
+# 36 tiles of rows of 67 voxels (the per-voxel path), and rows of 66 000 voxels (65 workgroups per slice; x and x * x beyond
+# 16 and 32 bits)
+SHAPES = [(20, 12, 9), (64, 8, 5), (72, 33, 17), (260, 4, 3), (37, 22, 13), (96, 88, 3), (67, 93, 3), (66000, 4, 2)]
 STATES = ["random", "edges", "fused"]
 BANDS = [1.0, 0.25]
 WEIGHT_THRESH = 0.9
@@ -25,6 +28,19 @@ N_FRAMES = 4
 # five voxels covers every slice (no observed free space) and a wall on the far face leaves a band of 0.25 nearly empty.
 FUSED = {(20, 12, 9): (5, 0.0), (64, 8, 5): (5, 0.0), (72, 33, 17): (8, 3.0), (260, 4, 3): (2, 0.7),
          (37, 22, 13): (5, 2.0)}
+
+
+
+def states_of(dims):
+    """The states a shape is tested in: the fused one only where FUSED has its scene."""
+    return [s for s in STATES if s != "fused" or tuple(dims) in FUSED]
+
+
+def workgroups_per_slice(dims):
+    """csrc/tsdf_extent_host.hip.h, extent_blocks: wavefront tiles of 32 x 8 voxels, 32 of them per workgroup."""
+    tiles = ((dims[0] + 3) // 4 + 7) // 8 * ((dims[1] + 7) // 8)
+    return max(1, (tiles + 31) // 32)
+
 
 ONE_BELOW = np.nextafter(f32(1), f32(0))
 EDGE_T = np.array([0.0, -0.0, 1.0, -1.0, ONE_BELOW, -ONE_BELOW, np.nan, np.inf, -np.inf], f32)

@@ -31,18 +31,38 @@ def extent(t, w, dims, z_begin=0, z_end=None, weight_thresh=0.9, band=1.0, margi
     observed, surface = classify(t, w, weight_thresh, band)
     assert observed.size == dx * dy * nz
     zi, yi, xi = np.nonzero(surface.reshape(nz, dy, dx))
-    idx = [[int(v) for v in xi], [int(v) for v in yi], [int(v) + z_begin for v in zi]]     # Python ints from here on
-    n = len(idx[0])
+    n = len(xi)
+    if n * max(dx, dy, dz) ** 2 < 2 ** 62:
+        # no sum can leave int64: NumPy's integer sums are exact and the record is made of Python ints all the same
+        idx = [xi.astype(np.int64), yi.astype(np.int64), zi.astype(np.int64) + z_begin]
+        total = lambda a: int(a.sum(dtype=np.int64))
+        count = lambda hit: int(np.count_nonzero(hit))
+        product = lambda p, q: p * q
+    else:
+        idx = [[int(v) for v in xi], [int(v) for v in yi], [int(v) + z_begin for v in zi]]     # Python ints from here on
+        total, count = sum, sum
+        product = lambda p, q: [a * b for a, b in zip(p, q)]
+        idx = [_Ints(a) for a in idx]
     rec = {"n_observed": int(observed.sum()), "n_surface": n,
-           "sum": [sum(a) for a in idx],
-           "sum2": [sum(p * q for p, q in zip(idx[i], idx[j])) for i, j in PAIRS],
+           "sum": [total(a) for a in idx],
+           "sum2": [total(product(idx[i], idx[j])) for i, j in PAIRS],
            "border": [], "lo": [dx, dy, dz], "hi": [-1, -1, -1]}
     for axis, d in enumerate((dx, dy, dz)):
-        rec["border"].append(sum(1 for v in idx[axis] if v < margin))
-        rec["border"].append(sum(1 for v in idx[axis] if v >= d - margin))
+        rec["border"].append(count(idx[axis] < margin))
+        rec["border"].append(count(idx[axis] >= d - margin))
         if n:
-            rec["lo"][axis], rec["hi"][axis] = min(idx[axis]), max(idx[axis])
+            rec["lo"][axis], rec["hi"][axis] = int(min(idx[axis])), int(max(idx[axis]))
     return rec
+
+
+class _Ints(list):
+    """A list of Python ints that compares element by element, as the arrays of the int64 path do."""
+
+    def __lt__(self, bound):
+        return [v < bound for v in self]
+
+    def __ge__(self, bound):
+        return [v >= bound for v in self]
 
 
 def empty(dims):

@@ -13,7 +13,8 @@ f32 = np.float32
 IM_HW = (120, 160)
 K_SMALL = synth.TUM_K.copy()
 K_SMALL[[0, 2, 4, 5]] *= 0.25          # the TUM camera at a quarter of its resolution
-DST_SHAPES = [(37, 22, 13), (64, 48, 40)]   # odd rows (the per-voxel path); 16-byte rows, more than one workgroup per axis
+# odd rows (the per-voxel path); 16-byte rows, more than one workgroup per axis; 16-byte rows whose last x tile (8 quads) is partial
+DST_SHAPES = [(37, 22, 13), (64, 48, 40), (44, 12, 9)]
 SRC_SHAPE = (24, 33, 17)
 DST_VS, SRC_VS = 0.004, 0.005
 N_POSES = 3

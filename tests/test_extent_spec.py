@@ -227,7 +227,7 @@ def test_the_gpu_parity_cases_are_not_vacuous():
     lo_above_zero = 0
     for dims in ec.SHAPES:
         n = int(np.prod(dims))
-        for name in ec.STATES:
+        for name in ec.states_of(dims):
             t, w = ec.state(dims, name)
             for band in ec.BANDS:
                 recs = {m: es.extent(t, w, dims, band=band, margin=m) for m in ec.margins(dims)}
@@ -242,6 +242,12 @@ def test_the_gpu_parity_cases_are_not_vacuous():
                 big = recs[ec.margins(dims)[2]]
                 assert big["border"][2 * axis] == big["border"][2 * axis + 1] == rec["n_surface"]
     assert lo_above_zero >= 1
+    # the shapes whose slices take more than one workgroup have uploaded states only; one of them has 33 tiles, one rows that
+    # are no multiple of 4 voxels, one an x whose square does not fit 32 bits
+    wide = [d for d in ec.SHAPES if ec.workgroups_per_slice(d) > 1]
+    assert all(ec.states_of(d) == ["random", "edges"] for d in wide) and len(wide) == 3
+    assert (96, 88, 3) in wide and any(d[0] % 4 for d in wide)
+    assert any(es.extent(*ec.state(d, "random"), d)["hi"][0] ** 2 >= 2 ** 32 for d in wide)
     t, w = ec.state((20, 12, 9), "edges")                               # the edge state holds every pair of the two lists
     for tv in ec.EDGE_T:
         for wv in ec.EDGE_W:

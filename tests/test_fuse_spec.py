@@ -168,6 +168,8 @@ def test_the_gpu_parity_cases_are_not_vacuous():
             for state in fc.STATES:
                 sampled, rejected, fresh, observed = fc.vacuity(dims, pose, state)
                 assert sampled >= 0.10 and rejected >= 0.01 and fresh > 0 and observed > 0, (dims, pose, state, sampled, rejected)
+    # one destination has 16-byte rows whose last x tile (8 quads, 32 voxels) is partial; 64 voxels are two full tiles
+    assert any(d[0] % 4 == 0 and d[0] > 32 and d[0] % 32 for d in fc.DST_SHAPES)
     ratios = {f32(fc.configs(fc.DST_SHAPES[0], p)[1].trunc_margin) / f32(fc.configs(fc.DST_SHAPES[0], p)[0].trunc_margin)
               for p in range(fc.N_POSES)}
     assert min(ratios) < 1 < max(ratios)
