@@ -556,6 +556,41 @@ int tsdf_batch_sync(tsdf_batch *batch);
  */
 int tsdf_batch_raycast_device(tsdf_batch *batch, const tsdf_raycast_params *p, const float cam2world[16], float *depth_dev,
                               float *normal_dev, int32_t *member_dev);
+
+/*
+ * Joint tracking against a batch: the camera pose from all the objects a caller trusts, by one call, and each object's own
+ * system at that pose (an object whose system no longer agrees with the camera's motion was moved or associated wrongly: its
+ * sqrt(S[27] / S[28]) stands out, and the caller can leave it out of the next call or solve its system for the object's own
+ * motion).  tsdf_track's rule with three changes, stated in csrc/tsdf_batch_track.hip.h and restated in
+ * tests/batch_track_spec.py: the poses are taken in the reference camera's frame (the members have base frames of their own:
+ * no base2world enters), the model is tsdf_batch_raycast_device's render at the guess (depth, normal, member), and a pair
+ * belongs to the member of its model pixel.  The joint system of an iteration sums the pairs of the members with
+ * member_use[m] != 0 (host, tsdf_batch_size bytes; NULL = all); the solve, the lost test, the levels and every field of
+ * `out` are tsdf_track's on that system.  member_systems (host, tsdf_batch_size x 29 doubles in tsdf_track_system's layout, or
+ * NULL: the pass is not run): one more association pass after the last iteration, at the final estimate and at the finest
+ * level that has iters > 0 (level 0 when none has), for EVERY member, used or not.  Its counts (entry 28) and sums are those
+ * of a later pass than the one out->inliers and out->rmse report.  On a lost track the pose is the guess's own bits and every
+ * system is all +0.0.  Two spheres alone leave the rotation about the line through their centres free: keep a box in play.
+ * Applies the batch's collected frames, renders once into scratch the batch owns, queues every iteration and the member pass
+ * on the batch's stream without a round trip per iteration, makes one copy and one wait; reads the volumes only.  Lost is
+ * TSDF_OK with status 2.  ray.im_height / ray.im_width must be the batch's image size; a z-slab member is refused.
+ */
+int tsdf_batch_track(tsdf_batch *batch, const tsdf_track_params *p, const float *depth_dev, const uint8_t *mask_dev,
+                     const uint8_t *member_use, const float guess_cam2world[16], tsdf_track_result *out,
+                     double *member_systems);
+/* One member pass: the model rendered at ref_cam2world, the pairs of level `level` taken at cam2world, for every member. */
+int tsdf_batch_track_system(tsdf_batch *batch, const tsdf_track_params *p, const float *depth_dev, const uint8_t *mask_dev,
+                            const float ref_cam2world[16], const float cam2world[16], int32_t level,
+                            double *member_systems);
+/*
+ * The same pass over images the caller supplies (what tsdf_associate_count is to association): model depth, normal (x 3) and
+ * member index per pixel, ray.im_height x ray.im_width; member ids outside [0, n_members) belong to no member; n_members in
+ * 1..65536.  Waits for all work queued on the device before it reads; returns when the systems are on the host.
+ */
+int tsdf_track_member_systems(int32_t device, const tsdf_track_params *p, const float *model_depth_dev,
+                              const float *model_normal_dev, const int32_t *member_dev, int32_t n_members,
+                              const float *depth_dev, const uint8_t *mask_dev, const float ref_cam2world[16],
+                              const float cam2world[16], int32_t level, double *member_systems);
 /*
  * The extent (tsdf_volume_extent) of every member of a batch in ONE launch (members differ in dims; the batch's slice map indexes {member, slice}): out receives
  * tsdf_batch_size records.  Applies the batch's collected frames first, queues everything on the batch's stream and returns

@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "tsdf_colour_enable", "tsdf_integrate_colour_device", "tsdf_integrate_rgbd", "tsdf_download_colour",
     "tsdf_raycast_params_default", "tsdf_raycast_device", "tsdf_raycast", "tsdf_batch_raycast_device",
     "tsdf_track_params_default", "tsdf_track", "tsdf_track_system",
+    "tsdf_batch_track", "tsdf_batch_track_system", "tsdf_track_member_systems",
     "tsdf_fuse_params_default", "tsdf_fuse_volume",
     "tsdf_extent_params_default", "tsdf_volume_extent", "tsdf_batch_extents", "tsdf_group_extent", "tsdf_extent_combine",
     "tsdf_extent_metric", "tsdf_extent_regrid",
@@ -272,6 +273,10 @@ def load():
     L.tsdf_track_params_default.argtypes = [C.POINTER(TsdfConfig), C.POINTER(TrackParams)]
     L.tsdf_track.argtypes = [vp, C.POINTER(TrackParams), vp, vp, vp, C.POINTER(TrackResult)]
     L.tsdf_track_system.argtypes = [vp, C.POINTER(TrackParams), vp, vp, vp, vp, C.c_int32, vp]
+    L.tsdf_batch_track.argtypes = [vp, C.POINTER(TrackParams), vp, vp, vp, vp, C.POINTER(TrackResult), vp]
+    L.tsdf_batch_track_system.argtypes = [vp, C.POINTER(TrackParams), vp, vp, vp, vp, C.c_int32, vp]
+    L.tsdf_track_member_systems.argtypes = [C.c_int32, C.POINTER(TrackParams), vp, vp, vp, C.c_int32, vp, vp, vp, vp,
+                                            C.c_int32, vp]
     L.tsdf_fuse_params_default.argtypes = [C.POINTER(TsdfConfig), C.POINTER(FuseParams)]
     L.tsdf_fuse_volume.argtypes = [vp, vp, C.POINTER(FuseParams), C.POINTER(FuseCounts)]
     L.tsdf_extent_params_default.argtypes = [C.POINTER(TsdfConfig), C.POINTER(ExtentParams)]
@@ -451,6 +456,19 @@ def extent_regrid(cfg, extent, pad_voxels, dim_multiple=4):
     a multiple of dim_multiple (batches need 4), whole-grid slab."""
     out = TsdfConfig()
     check(load().tsdf_extent_regrid(C.byref(cfg), C.byref(extent), pad_voxels, dim_multiple, C.byref(out)), "tsdf_extent_regrid")
+    return out
+
+
+def track_member_systems(params, model_depth_ptr, model_normal_ptr, member_ptr, n_members, depth_ptr, ref_cam2world,
+                         cam2world, level=0, mask_ptr=None, device=0):
+    """The member pass of joint tracking over caller images (device pointers): float64 [n_members, 29], row m the system of
+    the pairs whose model pixel shows member m (tsdf_track_system's layout), at `level`, the model at ref_cam2world, the pairs
+    at cam2world (tsdf_track_member_systems)."""
+    ref, cur = _f32(ref_cam2world, 16), _f32(cam2world, 16)
+    out = np.zeros((n_members, 29), np.float64)
+    check(load().tsdf_track_member_systems(device, C.byref(params), model_depth_ptr, model_normal_ptr, member_ptr, n_members,
+                                           depth_ptr, mask_ptr, ref.ctypes.data, cur.ctypes.data, level, out.ctypes.data),
+          "tsdf_track_member_systems")
     return out
 
 
@@ -1071,6 +1089,40 @@ class Batch:
         del keep
         overlap, mask, member = associate_split(counts, k, n)
         return {"counts": counts, "overlap": overlap, "mask": mask, "member": member, "assign": assign, "iou": iou}
+
+    def track(self, depth_ptr, guess_cam2world, params=None, mask_ptr=None, use=None, want_systems=True):
+        """Track a live depth frame (device pointer) against all members together from guess_cam2world
+        (csrc/tsdf_batch_track.hip.h).  use: None (all) or one flag per member, nonzero = the member's pairs enter the joint
+        system.  Returns (cam2world [4, 4] float32, stats as Volume.track's, systems): systems is float64 [M, 29], every
+        member's own system at the final estimate (used or not; all zero on a lost track), or None without want_systems.
+        params default: track_params_default of the first member's config."""
+        p = track_params_default(self.cfgs[0]) if params is None else params
+        guess = _f32(guess_cam2world, 16)
+        n = len(self.cfgs)
+        flags = None
+        if use is not None:
+            flags = np.ascontiguousarray(np.asarray(use) != 0, np.uint8)
+            if flags.shape != (n,):
+                raise ValueError(f"use has {flags.size} flags, the batch {n} members")
+        systems = np.zeros((n, 29), np.float64) if want_systems else None
+        res = TrackResult()
+        check(self.lib.tsdf_batch_track(self._h, C.byref(p), depth_ptr, mask_ptr, None if flags is None else flags.ctypes.data,
+                                        guess.ctypes.data, C.byref(res), None if systems is None else systems.ctypes.data),
+              "tsdf_batch_track")
+        pose = np.array(res.cam2world, np.float32).reshape(4, 4)
+        stats = {"status": res.status, "status_name": TRACK_STATUS[res.status], "iters_run": list(res.iters_run),
+                 "inliers": res.inliers, "rmse": res.rmse}
+        return pose, stats, systems
+
+    def track_system(self, depth_ptr, ref_cam2world, cam2world, level=0, params=None, mask_ptr=None):
+        """Every member's system of one pass at `level`, the model rendered at ref_cam2world, the pairs at cam2world:
+        float64 [M, 29] in tsdf_track_system's layout (tsdf_batch_track_system)."""
+        p = track_params_default(self.cfgs[0]) if params is None else params
+        ref, cur = _f32(ref_cam2world, 16), _f32(cam2world, 16)
+        out = np.zeros((len(self.cfgs), 29), np.float64)
+        check(self.lib.tsdf_batch_track_system(self._h, C.byref(p), depth_ptr, mask_ptr, ref.ctypes.data, cur.ctypes.data,
+                                               level, out.ctypes.data), "tsdf_batch_track_system")
+        return out
 
     def extents(self, params=None):
         """The Extent record of every member, by one launch (tsdf_batch_extents).  params default: extent_params_default of

@@ -39,6 +39,7 @@
 #include "tsdf_extract.hip.h"
 #include "tsdf_raycast.hip.h"
 #include "tsdf_track.hip.h"
+#include "tsdf_batch_track.hip.h"
 #include "tsdf_fuse.hip.h"
 #include "tsdf_extent.hip.h"
 #include "tsdf_associate.hip.h"
@@ -247,6 +248,11 @@ struct tsdf_batch {
     // (member | depth) and the counts in HBM; the counts' pinned host copy
     DevBuf<char> d_assoc;
     HostBuf<uint32_t> h_assoc;
+    // joint tracking (tsdf_batch_track*), allocated on first use and grown with the image and the members: the render (depth,
+    // normal, member), its depth with the members that are out zeroed, the partial rows of both reductions, the state, the
+    // member systems and member_use in HBM; the pinned mirror of state, systems and member_use
+    DevBuf<char> d_track;
+    HostBuf<char> h_track;
     // extents (tsdf_batch_extents), allocated on first use, all or none: one record per member and behind them one partial
     // record per workgroup of the launch in HBM; the records' pinned host copy; the members as the kernels read them (filled
     // and copied once: a batch's members do not change)
@@ -2014,6 +2020,7 @@ int tsdf_batch_integrate_device(tsdf_batch *b, const float *depth_dev, const uin
 #include "tsdf_fuse_host.hip.h"
 #include "tsdf_extent_host.hip.h"
 #include "tsdf_associate_host.hip.h"
+#include "tsdf_batch_track_host.hip.h"
 #include "tsdf_segment_host.hip.h"
 #include "tsdf_extract_host.hip.h"
 #include "tsdf_group.hip.h"

@@ -91,9 +91,9 @@ __device__ __forceinline__ bool track_depth_ok(float d, const uint8_t *mask, int
     return __builtin_isfinite(d) && near_m < d && d <= far_m && (mask == nullptr || mask[px] >= 128);
 }
 
-// The 29 terms of live sample (i, j), or false when it makes no pair.
-__device__ __forceinline__ bool track_pair(const TrackPairsParams &p, const float Rm[9], const float tm[3], int i, int j,
-                                           float J[6], float &r)
+// The 29 terms of live sample (i, j) and its model pixel mp = vi * W + ui, or false when it makes no pair.
+__device__ __forceinline__ bool track_pair_at(const TrackPairsParams &p, const float Rm[9], const float tm[3], int i, int j,
+                                              float J[6], float &r, int64_t &mp)
 {
     const int s = p.s, u = s * i, v = s * j;
     const int64_t px = (int64_t)v * p.W + u, px10 = px + s, px01 = px + (int64_t)s * p.W;
@@ -123,7 +123,7 @@ __device__ __forceinline__ bool track_pair(const TrackPairsParams &p, const floa
         return false;
     const int ui = (int)floorf(pu + 0.5f), vi = (int)floorf(pv + 0.5f);
     if (ui < 0 || ui >= p.W || vi < 0 || vi >= p.H) return false;
-    const int64_t mp = (int64_t)vi * p.W + ui;
+    mp = (int64_t)vi * p.W + ui;
     const float t = p.model_depth[mp];
     const float nm[3] = {p.model_normal[3 * mp], p.model_normal[3 * mp + 1], p.model_normal[3 * mp + 2]};
     if (!(t > 0.0f) || (nm[0] == 0.0f && nm[1] == 0.0f && nm[2] == 0.0f)) return false;
@@ -137,6 +137,13 @@ __device__ __forceinline__ bool track_pair(const TrackPairsParams &p, const floa
     J[2] = P[0] * nm[1] - P[1] * nm[0];
     J[3] = nm[0]; J[4] = nm[1]; J[5] = nm[2];
     return true;
+}
+
+__device__ __forceinline__ bool track_pair(const TrackPairsParams &p, const float Rm[9], const float tm[3], int i, int j,
+                                           float J[6], float &r)
+{
+    int64_t mp;
+    return track_pair_at(p, Rm, tm, i, j, J, r, mp);
 }
 
 __device__ __forceinline__ double track_wave_sum(double x)

@@ -94,14 +94,15 @@ int track_begin(tsdf_volume *v, const tsdf_track_params *p, const TrackScratch &
     return TSDF_OK;
 }
 
-// One iteration of level l: the association pass and the solve (system_only: the summed system, no step).
-int track_iteration(tsdf_volume *v, const tsdf_track_params *p, const TrackScratch &sc, const float *depth_dev,
-                           const uint8_t *mask_dev, int level, bool system_only)
+// One association pass of level l as track_pairs (and the member pass of tsdf_batch_track.hip.h) reads it.
+tsdfk::TrackPairsParams track_pairs_params(const tsdf_track_params *p, const float *model_depth, const float *model_normal,
+                                           const float *depth_dev, const uint8_t *mask_dev, const tsdfk::TrackState *state,
+                                           double *partials, int level)
 {
     const int s = 1 << level, W = p->ray.im_width, H = p->ray.im_height;
     tsdfk::TrackPairsParams k;
-    k.depth = depth_dev; k.mask = mask_dev; k.model_depth = sc.depth; k.model_normal = sc.normal;
-    k.state = sc.state; k.partials = sc.partials;
+    k.depth = depth_dev; k.mask = mask_dev; k.model_depth = model_depth; k.model_normal = model_normal;
+    k.state = state; k.partials = partials;
     k.fx = p->ray.cam_K[0]; k.fy = p->ray.cam_K[4]; k.cx = p->ray.cam_K[2]; k.cy = p->ray.cam_K[5];
     k.near_m = p->ray.near_m; k.far_m = p->ray.far_m;
     k.dist2 = p->dist_thresh[level] * p->dist_thresh[level];
@@ -109,17 +110,54 @@ int track_iteration(tsdf_volume *v, const tsdf_track_params *p, const TrackScrat
     k.H = H; k.W = W; k.s = s; k.level = level;
     k.ni = W > s ? (W - 1 - s) / s + 1 : 0;
     k.nj = H > s ? (H - 1 - s) / s + 1 : 0;
+    return k;
+}
+
+// One iteration of level l, queued on `stream`: the association pass and the solve (system_only: the summed system, no step).
+int track_iteration(hipStream_t stream, const tsdf_track_params *p, const TrackScratch &sc, const float *depth_dev,
+                           const uint8_t *mask_dev, int level, bool system_only)
+{
+    const tsdfk::TrackPairsParams k = track_pairs_params(p, sc.depth, sc.normal, depth_dev, mask_dev, sc.state, sc.partials, level);
     const int64_t n = (int64_t)k.ni * k.nj;
     const int nb = (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, tsdfk::kTrackMaxBlocks));
-    hipLaunchKernelGGL(tsdfk::track_pairs, dim3(nb), dim3(256), 0, v->stream, k);
+    hipLaunchKernelGGL(tsdfk::track_pairs, dim3(nb), dim3(256), 0, stream, k);
     HIP_TRY(hipGetLastError());
     tsdfk::TrackSolveParams q;
     q.state = sc.state; q.partials = sc.partials; q.n_rows = nb; q.level = level; q.min_inliers = p->min_inliers;
     q.system_only = system_only ? 1 : 0;
     q.eps_rot = p->eps_rot; q.eps_trans = p->eps_trans;
-    hipLaunchKernelGGL(tsdfk::track_solve, dim3(1), dim3(256), 0, v->stream, q);
+    hipLaunchKernelGGL(tsdfk::track_solve, dim3(1), dim3(256), 0, stream, q);
     HIP_TRY(hipGetLastError());
     return TSDF_OK;
+}
+
+// The result of a track from its final state: a lost track returns the guess's own bits, any other cam2world = X * M (4 x 4,
+// double, sums over k left to right) rounded to float32, with X = base2world * C_ref.
+void track_result(const tsdf_track_params *p, const tsdfk::TrackState &st, const float guess_cam2world[16], const double X[16],
+                  tsdf_track_result *out)
+{
+    std::memset(out, 0, sizeof *out);
+    for (int l = 0; l < 3; ++l) out->iters_run[l] = st.iters_run[l];
+    out->inliers = st.inliers;
+    out->rmse = st.inliers > 0 ? (float)std::sqrt(st.r2 / (double)st.inliers) : 0.0f;
+    if (st.lost) {
+        out->status = 2;
+        std::memcpy(out->cam2world, guess_cam2world, sizeof out->cam2world);
+        return;
+    }
+    int last = -1;                         // the finest level that ran
+    for (int l = p->n_levels - 1; l >= 0; --l)
+        if (p->iters[l] > 0) last = l;
+    out->status = last >= 0 && st.done[last] ? 0 : 1;
+    double M4[16] = {};
+    for (int k = 0; k < 12; ++k) M4[k] = st.M[k];
+    M4[15] = 1.0;
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            double acc = X[4 * i] * M4[j];
+            for (int k = 1; k < 4; ++k) acc = acc + X[4 * i + k] * M4[4 * k + j];
+            out->cam2world[4 * i + j] = (float)acc;
+        }
 }
 
 int track_fetch(tsdf_volume *v, const TrackScratch &sc)
@@ -160,24 +198,11 @@ int tsdf_track(tsdf_volume *v, const tsdf_track_params *p, const float *depth_de
     const double eye[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     rc = track_begin(v, p, sc, guess_cam2world, eye);
     for (int l = p->n_levels - 1; l >= 0 && rc == TSDF_OK; --l)
-        for (int it = 0; it < p->iters[l] && rc == TSDF_OK; ++it) rc = track_iteration(v, p, sc, depth_dev, mask_dev, l, false);
+        for (int it = 0; it < p->iters[l] && rc == TSDF_OK; ++it) rc = track_iteration(v->stream, p, sc, depth_dev, mask_dev, l, false);
     if (rc == TSDF_OK) rc = track_fetch(v, sc);
     if (rc) return rc;
     const tsdfk::TrackState &st = *v->h_track.get();
-    std::memset(out, 0, sizeof *out);
-    for (int l = 0; l < 3; ++l) out->iters_run[l] = st.iters_run[l];
-    out->inliers = st.inliers;
-    out->rmse = st.inliers > 0 ? (float)std::sqrt(st.r2 / (double)st.inliers) : 0.0f;
-    if (st.lost) {
-        out->status = 2;
-        std::memcpy(out->cam2world, guess_cam2world, sizeof out->cam2world);
-        return TSDF_OK;
-    }
-    int last = -1;                         // the finest level that ran
-    for (int l = p->n_levels - 1; l >= 0; --l)
-        if (p->iters[l] > 0) last = l;
-    out->status = last >= 0 && st.done[last] ? 0 : 1;
-    // cam2world = (base2world * C_ref) * M, double, sums over k left to right
+    // X = base2world * C_ref, double, sums over k left to right
     float cr[16];
     compose_cam2base(v, guess_cam2world, cr);
     const float *bw = v->cfg.base2world;
@@ -188,15 +213,7 @@ int tsdf_track(tsdf_volume *v, const tsdf_track_params *p, const float *depth_de
             for (int k = 1; k < 4; ++k) acc = acc + (double)bw[4 * i + k] * (double)cr[4 * k + j];
             X[4 * i + j] = acc;
         }
-    double M4[16] = {};
-    for (int k = 0; k < 12; ++k) M4[k] = st.M[k];
-    M4[15] = 1.0;
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) {
-            double acc = X[4 * i] * M4[j];
-            for (int k = 1; k < 4; ++k) acc = acc + X[4 * i + k] * M4[4 * k + j];
-            out->cam2world[4 * i + j] = (float)acc;
-        }
+    track_result(p, st, guess_cam2world, X, out);
     return TSDF_OK;
 }
 
@@ -218,7 +235,7 @@ int tsdf_track_system(tsdf_volume *v, const tsdf_track_params *p, const float *d
     double M[12];
     track_relative(cr, cc, M);
     rc = track_begin(v, p, sc, ref_cam2world, M);
-    if (rc == TSDF_OK) rc = track_iteration(v, p, sc, depth_dev, mask_dev, level, true);
+    if (rc == TSDF_OK) rc = track_iteration(v->stream, p, sc, depth_dev, mask_dev, level, true);
     if (rc == TSDF_OK) rc = track_fetch(v, sc);
     if (rc) return rc;
     std::memcpy(system_out, v->h_track.get()->sys, sizeof(double) * tsdfk::kTrackTerms);
