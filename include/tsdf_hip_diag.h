@@ -110,6 +110,14 @@ int tsdf_brick_list_stats(tsdf_volume *vol, uint64_t counts_out[4]);
  */
 int tsdf_classification_info(tsdf_volume *vol, double info_out[2]);
 
+/*
+ * The handle's share of the staging store that the handles of its device and image size have in common (frame, mask and
+ * tile-table slots): for the frames, the masks and the tables in turn, out = {slots the handle holds, slots it has
+ * released that no one has reused yet, slots the class has in the store}.  Reads the store's bookkeeping only: it applies no
+ * collected frame and does not synchronise, so the frames a deferring handle has collected show as held.
+ */
+int tsdf_store_stats(tsdf_volume *vol, int64_t out[9]);
+
 /* The relative pose used by the most recent integrate call (16 floats), for parity tests. */
 int tsdf_last_cam2base(const tsdf_volume *vol, float out[16]);
 

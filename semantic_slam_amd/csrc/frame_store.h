@@ -17,6 +17,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
 #include <mutex>
 #include <thread>
 #include <utility>
@@ -202,6 +203,21 @@ inline void slots_drop_owner(FrameStore *s, const void *owner)
     for (SlotClass *c : {&s->frames, &s->masks, &s->tables})
         for (Slot &x : c->slots)
             if (x.state != 0 && x.owner == owner) { x.state = 0; x.release = nullptr; x.owner = nullptr; }
+}
+
+// {slots `owner` holds, slots it has released that have not been reused, slots of the class} for frames, masks and tables in turn
+// (diagnostics / tests)
+inline void store_counts(FrameStore *s, const void *owner, int64_t out[9])
+{
+    std::lock_guard<std::mutex> lk(s->mu);
+    int k = 0;
+    for (SlotClass *c : {&s->frames, &s->masks, &s->tables}) {
+        out[k] = out[k + 1] = 0;
+        for (const Slot &x : c->slots)
+            if (x.state != 0 && x.owner == owner) ++out[k + (x.state == 2)];
+        out[k + 2] = (int64_t)c->slots.size();
+        k += 3;
+    }
 }
 
 // bytes of device memory the store holds (diagnostics / tests)

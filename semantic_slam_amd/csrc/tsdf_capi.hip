@@ -120,7 +120,6 @@ struct tsdf_volume {
     hipStream_t copy_stream = nullptr;   // the store's
     Event flush_done[2];              // recorded on `stream` after every launch that read store slots: what they are released after;
     int flush_parity = 0;             // two, used in turn, so that a slot of pass k is not held until pass k + 1 has run as well
-    int table_slot = -1;              // the store's table slot of the launch being queued, or -1
     // Deferred integration of host frames (tsdf_integrate): the reference reads results back only in its destructor
     // (ref: src/tsdf.cu:101-104) and this library only at download / extraction / save, so the frames of successive
     // calls are collected -- copied into a pool in HBM, poses composed at call time -- and applied defer_n at a time as
@@ -287,53 +286,73 @@ int bind_device(tsdf_volume *v, bool flush = true)
 }
 
 // ---- the shared store (frame_store.h) -----------------------------------------------------------------------------
-// A frame (c = frames) or mask (c = masks) slot whose first access is queued on `first_user`.  When the store is at its soft
-// cap and every slot is held by collecting handles, this handle applies what IT has collected (never another handle's: that
-// one may be in use on another thread) and asks again.
-int store_slot(tsdf_volume *v, tsdf_store::SlotClass *c, hipStream_t first_user, int *index, void **dev)
-{
-    hipError_t e = tsdf_store::slot_acquire(v->store, c, v, first_user, false, index, dev);
-    if (e == hipSuccess && *index < 0) {
-        if (v->pend_count > 0 && !v->in_flush) {
-            int rc = flush_pending(v);
-            if (rc) return rc;
-        }
-        e = tsdf_store::slot_acquire(v->store, c, v, first_user, true, index, dev);
+// One slot of the store while a call of this handle holds it, move-only like the owners of hip_owned.h.  The call that has
+// queued the slot's last reader gives it back (release, release_after) or hands it to the collected frames (hand_over); a
+// call that returns early does neither, and the destructor gives the slot back behind everything the call has queued.
+class StoreSlot {
+public:
+    StoreSlot() = default;
+    StoreSlot(StoreSlot &&o) noexcept : v_(o.v_), c_(o.c_), dev_(o.dev_), idx_(std::exchange(o.idx_, -1)) {}
+    StoreSlot &operator=(StoreSlot &&) = delete;
+    // Still held, i.e. a failure path: the handle's stream waits for what is queued on the copy stream, and the slot goes back
+    // after flush_done recorded behind that.  Should one of these calls fail as well, the slot stays held until tsdf_destroy.
+    ~StoreSlot()
+    {
+        if (idx_ < 0) return;
+        if (hipEventRecord(v_->pend_copied, v_->copy_stream) == hipSuccess && hipStreamWaitEvent(v_->stream, v_->pend_copied, 0) == hipSuccess)
+            (void)release_all(v_, c_, &idx_, 1);
     }
-    if (e != hipSuccess) return fail(TSDF_ERR_HIP, "frame store: %s", hipGetErrorString(e));
-    return TSDF_OK;
-}
-
-// Everything queued on the handle's stream so far has read its store slots: they go back after flush_done.
-int store_release(tsdf_volume *v, tsdf_store::SlotClass *c, const int *idx, int n)
-{
-    const Event *evt = &v->flush_done[v->flush_parity];
-    HIP_TRY(hipEventRecord(*evt, v->stream));
-    tsdf_store::slots_release_after(v->store, c, idx, n, evt, v);
-    return TSDF_OK;
-}
+    // A slot of class c whose first access is queued on `first_user`.  When the store is at its soft cap and every slot is
+    // held by collecting handles, this handle applies what IT has collected (never another handle's: that one may be in use
+    // on another thread) and asks again.
+    int take(tsdf_volume *v, tsdf_store::SlotClass *c, hipStream_t first_user)
+    {
+        v_ = v; c_ = c;
+        hipError_t e = tsdf_store::slot_acquire(v->store, c, v, first_user, false, &idx_, &dev_);
+        if (e == hipSuccess && idx_ < 0) {
+            if (v->pend_count > 0 && !v->in_flush) {
+                int rc = flush_pending(v);
+                if (rc) return rc;
+            }
+            e = tsdf_store::slot_acquire(v->store, c, v, first_user, true, &idx_, &dev_);
+        }
+        if (e != hipSuccess) return fail(TSDF_ERR_HIP, "frame store%s: %s", c == &v->store->tables ? " (tile tables)" : "", hipGetErrorString(e));
+        return TSDF_OK;
+    }
+    template <typename T> T *as() const { return idx_ < 0 ? nullptr : static_cast<T *>(dev_); }
+    // everything queued on the handle's stream so far has read the slot (nothing to do for a holder that is empty)
+    int release()
+    {
+        const hipError_t e = idx_ < 0 ? hipSuccess : release_all(v_, c_, &idx_, 1);
+        return e == hipSuccess ? TSDF_OK : fail(TSDF_ERR_HIP, "frame store: hipEventRecord failed: %s", hipGetErrorString(e));
+    }
+    // the slot's last reader sits on another stream, in front of *evt (an event of this handle)
+    void release_after(const Event *evt)
+    {
+        tsdf_store::slots_release_after(v_->store, c_, &idx_, 1, evt, v_);
+        idx_ = -1;
+    }
+    // the collected frames own the slot from here on (pend_slot[] / pend_mask_slot[], until flush_pending); -1: there is none
+    int hand_over() { return std::exchange(idx_, -1); }
+    // Slots that were handed over, or a holder's own: they go back after flush_done, recorded now on the handle's stream.
+    static hipError_t release_all(tsdf_volume *v, tsdf_store::SlotClass *c, int *idx, int n)
+    {
+        const Event *evt = &v->flush_done[v->flush_parity];
+        const hipError_t e = hipEventRecord(*evt, v->stream);
+        if (e != hipSuccess) return e;
+        tsdf_store::slots_release_after(v->store, c, idx, n, evt, v);
+        std::fill(idx, idx + n, -1);
+        return hipSuccess;
+    }
+private:
+    tsdf_volume *v_ = nullptr;
+    tsdf_store::SlotClass *c_ = nullptr;
+    void *dev_ = nullptr;
+    int idx_ = -1;
+};
 
 // the pass (a flush of collected frames, or one one-kernel-per-call frame) is queued: the next one records the other event
 void store_next_pass(tsdf_volume *v) { v->flush_parity ^= 1; }
-
-// The depth tile tables of the launch being queued (kMaxFramesPerLaunch tables): a table slot of the store, first written on the
-// handle's stream; tables_end() after the launch that reads them has been queued.
-int tables_begin(tsdf_volume *v, float2 **tiles, hipStream_t first_user = nullptr)
-{
-    void *dev = nullptr;
-    hipError_t e = tsdf_store::slot_acquire(v->store, &v->store->tables, v, first_user ? first_user : v->stream, true, &v->table_slot, &dev);
-    if (e != hipSuccess) return fail(TSDF_ERR_HIP, "frame store (tile tables): %s", hipGetErrorString(e));
-    *tiles = static_cast<float2 *>(dev);
-    return TSDF_OK;
-}
-
-int tables_end(tsdf_volume *v)
-{
-    if (v->table_slot < 0) return TSDF_OK;
-    const int slot = v->table_slot;
-    v->table_slot = -1;
-    return store_release(v, &v->store->tables, &slot, 1);
-}
 
 // The wavefront brick of classified launches and the library's choice of it: host arithmetic only (host_derive.h; also behind
 // tsdf_default_brick_shape, which needs no device).
@@ -484,24 +503,24 @@ int build_tile_tables(hipStream_t stream, const tsdf_config &c, const tsdfk::Int
 int launch_masked_bricks(tsdf_volume *v, tsdfk::IntegrateParams &p)
 {
     const int blocks = (p.brick_groups * p.bricks_per_group + 3) / 4, nz = (p.nz + p.brick_s - 1) / p.brick_s;   // slice groups
-    float2 *tiles = nullptr;
-    int rc0 = tables_begin(v, &tiles);
+    StoreSlot table;      // the frame's depth tile tables, first written on the handle's stream
+    int rc0 = table.take(v, &v->store->tables, v->stream);
     if (rc0) return rc0;
     const size_t n_bricks = (size_t)blocks * nz * 4;
     HIP_TRY(v->d_wg_class.ensure(n_bricks));
     const float *d = p.depth;
     const uint8_t *m = p.mask;
-    int rc = build_tile_tables(v->stream, v->cfg, p, &d, &m, 1, tiles);
+    int rc = build_tile_tables(v->stream, v->cfg, p, &d, &m, 1, table.as<float2>());
     if (rc) return rc;
     tsdfk::FramePose pose;
     pose_from_params(pose, p);
-    pose.tiles = tiles;
+    pose.tiles = table.as<float2>();
     hipLaunchKernelGGL(tsdfk::classify_bricks, dim3((unsigned)((n_bricks + 255) / 256)), dim3(256), 0, v->stream, p, pose,
                        v->d_wg_class, blocks, nz);
     p.wg_class = v->d_wg_class;
     hipLaunchKernelGGL((tsdfk::integrate_single_bricks<kBrickNT>), dim3(blocks, 1, nz), dim3(64, 4, 1), 0, v->stream, p, pose);
     HIP_TRY(hipGetLastError());
-    return tables_end(v);
+    return table.release();
 }
 
 // Kernels that do not maintain the free-space summary must not leave stale "all ones" flags behind.
@@ -806,10 +825,10 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
         HIP_TRY(v->d_work.ensure(lists * (size_t)total));
     }
     const hipStream_t ps = pipelined ? v->pre_stream : v->stream;
-    // a failure from here on joins the side stream back into the handle's stream and gives the table slot back
+    // a failure from here on joins the side stream back into the handle's stream (the table slot then goes back behind the join)
+    StoreSlot table;
     auto unwind = [&](int code) {
         if (pipelined && hipEventRecord(v->pre_done[P], ps) == hipSuccess) (void)hipStreamWaitEvent(v->stream, v->pre_done[P], 0);
-        (void)tables_end(v);
         return code;
     };
     if (pipelined) {
@@ -823,9 +842,9 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
     if (classify) {
         // depth tile tables of the n frames (two small launches), then the kernels that consult them
         const size_t per_frame = tsdf_host::tile_table_elems(mi.common.tiles_w, mi.common.tiles_h);
-        float2 *tiles = nullptr;
-        int rc = tables_begin(v, &tiles, ps);
+        int rc = table.take(v, &v->store->tables, ps);
         if (rc) return unwind(rc);
+        float2 *const tiles = table.as<float2>();
         // (fine_tables) the fine tables of the launch's frames sit behind its kMaxFramesPerLaunch coarse ones in the same slot
         float2 *fine = v->fine_tables ? tiles + (size_t)tsdfk::kMaxFramesPerLaunch * per_frame : nullptr;
         rc = build_tile_tables(ps, c, mi.common, depth_dev, masks_dev, n, tiles, claims_p, fine, pipelined);
@@ -911,7 +930,7 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
         v->rb_parity = (rs != v->stream) ? P : -1;
     }
     HIP_TRY_OR(unwind, hipGetLastError());
-    const int rc_end = tables_end(v);
+    const int rc_end = table.release();
     // (pipelined) the next launch's table slot is released after the OTHER of the handle's two events: a slot taken two launches
     // later then waits for this launch's Integrate kernel, not for the one in between
     if (pipelined) store_next_pass(v);
@@ -929,10 +948,12 @@ int frames_per_launch(const tsdf_volume *)
 bool can_fuse(const tsdf_volume *v) { return variant_of(v->variant).fuses && v->cfg.dim_x % 4 == 0; }
 
 // A sequence of frames: fused frames_per_launch() at a time when the default kernel is selected.
+// label_ims / score_ims (both or neither): as launch_multi takes them; such a sequence is always fused.
 int integrate_frames(tsdf_volume *v, const float *const *depth_dev, const uint8_t *const *masks_dev,
-                     const float *cam2world, int n_frames)
+                     const float *cam2world, int n_frames, const uint16_t *const *label_ims = nullptr,
+                     const float *const *score_ims = nullptr)
 {
-    const bool fuse = can_fuse(v);
+    const bool fuse = label_ims != nullptr || can_fuse(v);
     int rc = TSDF_OK;
     // every frame of the sequence is readable once what precedes this call on the handle's stream has run: one event for all its
     // launches, so that their pre-passes may run beside the launches ahead of them (launch_multi, inputs_ready)
@@ -945,7 +966,8 @@ int integrate_frames(tsdf_volume *v, const float *const *depth_dev, const uint8_
             HIP_TRY(hipEventRecord(v->seq_ready, v->stream));
             seq_event = true;
         }
-        if (fuse) rc = launch_multi(v, depth_dev + k, masks_dev ? masks_dev + k : nullptr, c2b, n, nullptr, nullptr, seq_event ? v->seq_ready : nullptr);
+        if (fuse) rc = launch_multi(v, depth_dev + k, masks_dev ? masks_dev + k : nullptr, c2b, n, label_ims ? label_ims + k : nullptr,
+                                    label_ims ? score_ims + k : nullptr, seq_event ? v->seq_ready : nullptr);
         else rc = launch_integrate(v, depth_dev[k], masks_dev ? masks_dev[k] : nullptr, c2b);
         k += n;
     }
@@ -972,41 +994,29 @@ int flush_pending(tsdf_volume *v)
         } else {   // a single collected frame (or a variant that does not fuse): the one-frame kernels
             for (int f = 0; f < n && rc == TSDF_OK; ++f) rc = launch_integrate(v, v->pend_depth[f], v->pend_mask[f], v->pend_c2b + 16 * f);
         }
-        if (rc == TSDF_OK) rc = store_release(v, &v->store->frames, v->pend_slot, n);
-        if (rc == TSDF_OK && any_mask) rc = store_release(v, &v->store->masks, v->pend_mask_slot, n);
+        // whatever the launch returned: kernels it queued on the handle's stream may read the slots, so they go back behind them
+        // (and without a word when the launch has failed: its message is the one to report)
+        hipError_t re = StoreSlot::release_all(v, &v->store->frames, v->pend_slot, n);
+        const hipError_t rm = any_mask ? StoreSlot::release_all(v, &v->store->masks, v->pend_mask_slot, n) : hipSuccess;
+        if (re == hipSuccess) re = rm;
         store_next_pass(v);
+        if (rc == TSDF_OK && re != hipSuccess) rc = fail(TSDF_ERR_HIP, "deferred integration: hipEventRecord failed: %s", hipGetErrorString(re));
     }
     v->in_flush = false;
     if (e != hipSuccess) return fail(TSDF_ERR_HIP, "deferred integration: %s", hipGetErrorString(e));
     return rc;
 }
 
-// Deferred integration, collecting side: a frame slot of the store for the next collected frame; `first_user` is the stream
-// the copy into it will be queued on (the copy stream for host frames, the handle's stream for device-resident ones) ...
-struct Collected {
-    int slot, mask_slot;
-    float *dev;
-    const uint8_t *mask;
-};
-
-int pool_slot_begin(tsdf_volume *v, hipStream_t first_user, Collected *c)
-{
-    c->slot = c->mask_slot = -1;
-    c->mask = nullptr;
-    void *dev = nullptr;
-    int rc = store_slot(v, &v->store->frames, first_user, &c->slot, &dev);   // (may apply the frames collected so far to make room)
-    c->dev = static_cast<float *>(dev);
-    return rc;
-}
-
-// ... and the frame's pose, composed now (or given as the relative pose itself); the batch is launched when it is full.
-int pool_slot_commit(tsdf_volume *v, const Collected &c, const float cam2world[16], const float *cam2base = nullptr)
+// Deferred integration, collecting side: the frame in `frame` (and its instance mask in `mask`, which may be empty) joins the
+// collected ones, which own both slots from here on, with its pose composed now (or given as the relative pose itself); the
+// batch is launched when it is full.
+int pool_slot_commit(tsdf_volume *v, StoreSlot &frame, StoreSlot &mask, const float cam2world[16], const float *cam2base = nullptr)
 {
     const int slot = v->pend_count;
-    v->pend_slot[slot] = c.slot;
-    v->pend_mask_slot[slot] = c.mask_slot;
-    v->pend_depth[slot] = c.dev;
-    v->pend_mask[slot] = c.mask;
+    v->pend_depth[slot] = frame.as<float>();
+    v->pend_mask[slot] = mask.as<uint8_t>();
+    v->pend_slot[slot] = frame.hand_over();
+    v->pend_mask_slot[slot] = mask.hand_over();
     if (cam2base) std::memcpy(v->pend_c2b + 16 * slot, cam2base, 16 * sizeof(float));
     else compose_cam2base(v, cam2world, v->pend_c2b + 16 * slot);
     std::memcpy(v->last_cam2base, v->pend_c2b + 16 * slot, sizeof v->last_cam2base);
@@ -1022,52 +1032,109 @@ int collect_device_frame(tsdf_volume *v, const float *depth_dev, const uint8_t *
                          const float *cam2base)
 {
     const size_t px = (size_t)v->cfg.im_height * v->cfg.im_width;
-    Collected c;
-    int rc = pool_slot_begin(v, v->stream, &c);
+    StoreSlot frame, mask;
+    int rc = frame.take(v, &v->store->frames, v->stream);   // (may apply the frames collected so far to make room)
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(c.dev, depth_dev, px * sizeof(float), hipMemcpyDeviceToDevice, v->stream));
+    HIP_TRY(hipMemcpyAsync(frame.as<float>(), depth_dev, px * sizeof(float), hipMemcpyDeviceToDevice, v->stream));
     if (mask_dev) {
-        void *m = nullptr;
-        rc = store_slot(v, &v->store->masks, v->stream, &c.mask_slot, &m);
+        rc = mask.take(v, &v->store->masks, v->stream);
         if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(m, mask_dev, px, hipMemcpyDeviceToDevice, v->stream));
-        c.mask = static_cast<const uint8_t *>(m);
+        HIP_TRY(hipMemcpyAsync(mask.as<uint8_t>(), mask_dev, px, hipMemcpyDeviceToDevice, v->stream));
     }
-    return pool_slot_commit(v, c, cam2world, cam2base);
+    return pool_slot_commit(v, frame, mask, cam2world, cam2base);
 }
 
-// One-kernel-per-call staging of a host frame: pinned ring slot -> frame slot of the store (H2D on the copy stream, which the
-// handle's stream then waits for).  `fill_host(pinned)` writes the pinned frame; *dev = the frame in HBM; *slot goes to
-// stage_end() once the kernels that read it have been queued.
+// A device-resident frame from the caller: collected, or launched at once.  Exactly one of cam2world and cam2base is given.
+int integrate_device_frame(const char *who, tsdf_volume *v, const float *depth_dev, const uint8_t *mask_dev, bool masked,
+                           const float *cam2world, const float *cam2base)
+{
+    if (!v || !depth_dev || (masked && !mask_dev) || (!cam2world && !cam2base)) return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
+    const bool defer = v->defer_n > 1 && can_fuse(v);
+    int rc = bind_device(v, !defer);
+    if (rc) return rc;
+    if (defer) return collect_device_frame(v, depth_dev, mask_dev, cam2world, cam2base);
+    float c2b[16];
+    if (cam2world) compose_cam2base(v, cam2world, c2b);
+    return launch_integrate(v, depth_dev, mask_dev, cam2world ? c2b : cam2base);
+}
+
+// ---- a host frame: staged on the copy stream, then collected or launched -----------------------------------------
+// Staging: pinned ring slot -> `frame`, a frame slot of the store, H2D on the copy stream (it overlaps the previous frame's
+// kernel).  `fill_host(pinned)` writes the pinned frame; the caller may free its buffer when we return.
 template <typename F>
-int stage_begin(tsdf_volume *v, size_t bytes, F fill_host, int *slot, void **dev)
+int stage_frame(tsdf_volume *v, size_t bytes, F fill_host, StoreSlot &frame)
 {
     int r = -1;
     hipError_t e = tsdf_store::ring_acquire(v->store, &r);
     if (e != hipSuccess) return fail(TSDF_ERR_HIP, "frame store (pinned ring): %s", hipGetErrorString(e));
-    fill_host(v->store->ring[r].host);                     // the caller may free its buffer after we return
-    int rc = store_slot(v, &v->store->frames, v->copy_stream, slot, dev);
+    fill_host(v->store->ring[r].host);
+    int rc = frame.take(v, &v->store->frames, v->copy_stream);
     if (rc) { (void)tsdf_store::ring_release(v->store, r, v->copy_stream); return rc; }
-    e = hipMemcpyAsync(*dev, v->store->ring[r].host, bytes, hipMemcpyHostToDevice, v->copy_stream);
+    e = hipMemcpyAsync(frame.as<void>(), v->store->ring[r].host, bytes, hipMemcpyHostToDevice, v->copy_stream);
     const hipError_t e2 = tsdf_store::ring_release(v->store, r, v->copy_stream);
     if (e == hipSuccess) e = e2;
     if (e != hipSuccess) return fail(TSDF_ERR_HIP, "staging copy: %s", hipGetErrorString(e));
     return TSDF_OK;
 }
 
-// the handle's stream waits for everything queued on the copy stream so far
-int stream_waits_for_copies(tsdf_volume *v)
+// The same for a raw 16-bit frame (half the bytes of the float frame): staged into a slot of its own and converted on the copy
+// stream into `frame`, the one Integrate reads.  pend_copied is recorded behind the conversion, and the raw slot goes back after it.
+int stage_frame_u16(tsdf_volume *v, const uint16_t *raw_host, float depth_factor, int row_step, int col_step, StoreSlot &frame)
 {
+    const size_t px = (size_t)v->cfg.im_height * v->cfg.im_width;
+    StoreSlot raw;
+    int rc = stage_frame(v, px * sizeof(uint16_t), [&](float *pinned) { tsdf_host::copy_to_pinned(pinned, raw_host, px * sizeof(uint16_t)); }, raw);
+    if (rc == TSDF_OK) rc = frame.take(v, &v->store->frames, v->copy_stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(tsdfk::depth_u16_to_f32, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, v->copy_stream, raw.as<uint16_t>(),
+                       frame.as<float>(), v->cfg.im_height, v->cfg.im_width, 1.0f / depth_factor, row_step,
+                       col_step);   // ref: examples/label_instance_rgbd.cpp:99-100 (fp32 reciprocal)
+    HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(v->pend_copied, v->copy_stream));
-    HIP_TRY(hipStreamWaitEvent(v->stream, v->pend_copied, 0));
+    raw.release_after(&v->pend_copied);
     return TSDF_OK;
 }
 
-int stage_end(tsdf_volume *v, const int *slots, int n)
+// The colour pass of a frame (tsdf_colour.hip.h), queued behind its Integrate launch.
+int launch_colour(tsdf_volume *v, const float *depth_dev, const uint8_t *rgb_dev, const float *c2b)
 {
-    const int rc = store_release(v, &v->store->frames, slots, n);
+    const int nz = v->cfg.z_end - v->cfg.z_begin;
+    if (nz == 0) return TSDF_OK;
+    tsdfk::ColourParams cp;
+    cp.g = make_params(v, depth_dev, nullptr, c2b, 4);
+    cp.rgb = rgb_dev;
+    cp.colour = v->d_colour;
+    dim3 block(64, 4, 1), grid((cp.g.xgroups + 63) / 64, (v->cfg.dim_y + 3) / 4, nz);
+    hipLaunchKernelGGL(tsdfk::integrate_colour, grid, block, 0, v->stream, cp);
+    HIP_TRY(hipGetLastError());
+    return TSDF_OK;
+}
+
+// The tail of a one-kernel-per-call frame whose copy the handle's stream already waits for: the launch, the colour launch when
+// there is an image (rgb_dev), and the slot's release behind them.  A failed launch returns at once: kernels it queued on the
+// handle's stream may read the slot, and the holder gives it back behind them.
+int launch_staged_frame(tsdf_volume *v, StoreSlot &frame, const float cam2world[16], const uint8_t *rgb_dev = nullptr)
+{
+    float c2b[16];
+    compose_cam2base(v, cam2world, c2b);
+    int rc = launch_integrate(v, frame.as<float>(), nullptr, c2b);
+    if (rc == TSDF_OK && rgb_dev) rc = launch_colour(v, frame.as<float>(), rgb_dev, c2b);
+    if (rc) return rc;
+    rc = frame.release();
     store_next_pass(v);
     return rc;
+}
+
+// Applying a staged frame.  Deferred: collected, its pose composed now, and launched defer_n at a time (or at the next call that
+// observes the volume) as one fused sequence.  Else one kernel per call, which waits for the copy: pend_copied, recorded now on
+// the copy stream unless the staging has (copies_marked).
+int apply_host_frame(tsdf_volume *v, StoreSlot &frame, const float cam2world[16], bool defer, bool copies_marked, const uint8_t *rgb_dev = nullptr)
+{
+    StoreSlot no_mask;
+    if (defer) return pool_slot_commit(v, frame, no_mask, cam2world);
+    if (!copies_marked) HIP_TRY(hipEventRecord(v->pend_copied, v->copy_stream));
+    HIP_TRY(hipStreamWaitEvent(v->stream, v->pend_copied, 0));
+    return launch_staged_frame(v, frame, cam2world, rgb_dev);
 }
 
 int fill(tsdf_volume *v)
@@ -1250,26 +1317,10 @@ int tsdf_integrate(tsdf_volume *v, const float *depth_host, const float cam2worl
     int rc = bind_device(v, !defer);
     if (rc) return rc;
     const size_t img = (size_t)v->cfg.im_height * v->cfg.im_width * sizeof(float);
-    // caller's frame -> pinned ring -> a frame slot in HBM (copy stream); the caller may free depth_host when we return
-    int slot = -1;
-    void *dev = nullptr;
-    rc = stage_begin(v, img, [&](float *pinned) { tsdf_host::copy_to_pinned(pinned, depth_host, img); }, &slot, &dev);
+    StoreSlot frame;
+    rc = stage_frame(v, img, [&](float *pinned) { tsdf_host::copy_to_pinned(pinned, depth_host, img); }, frame);
     if (rc) return rc;
-    if (defer) {
-        // collect: pose composed now; launched defer_n at a time (or at the next call that observes the volume) as one fused
-        // sequence
-        Collected c;
-        c.slot = slot; c.mask_slot = -1; c.dev = static_cast<float *>(dev); c.mask = nullptr;
-        return pool_slot_commit(v, c, cam2world);
-    }
-    // one kernel per call: it waits for the copy (which overlapped the previous frame's kernel)
-    rc = stream_waits_for_copies(v);
-    if (rc) return rc;
-    float c2b[16];
-    compose_cam2base(v, cam2world, c2b);
-    rc = launch_integrate(v, static_cast<const float *>(dev), nullptr, c2b);
-    if (rc) return rc;
-    return stage_end(v, &slot, 1);
+    return apply_host_frame(v, frame, cam2world, defer, false);
 }
 
 int tsdf_set_deferral(tsdf_volume *v, int32_t n_frames)
@@ -1308,78 +1359,26 @@ int tsdf_integrate_u16(tsdf_volume *v, const uint16_t *raw_host, float depth_fac
     const bool defer = v->defer_n > 1;
     int rc = bind_device(v, !defer);
     if (rc) return rc;
-    const size_t px = (size_t)v->cfg.im_height * v->cfg.im_width;
-    // the raw frame (half the bytes of the float frame) -> pinned ring -> a frame slot; converted on the copy stream into a
-    // second slot, which is the frame Integrate reads
-    int raw_slot = -1, slot = -1;
-    void *raw_dev = nullptr, *dev = nullptr;
-    rc = stage_begin(v, px * sizeof(uint16_t), [&](float *pinned) { tsdf_host::copy_to_pinned(pinned, raw_host, px * sizeof(uint16_t)); }, &raw_slot, &raw_dev);
+    StoreSlot frame;
+    rc = stage_frame_u16(v, raw_host, depth_factor, row_step, col_step, frame);
     if (rc) return rc;
-    // a failure from here on hands the slots it holds back to the (shared, per-device) store: they would otherwise stay held until
-    // the handle is destroyed and count against every other handle's share
-    auto give_back = [&](int failed) {
-        int held[2], n = 0;
-        if (raw_slot >= 0) held[n++] = raw_slot;
-        if (slot >= 0) held[n++] = slot;
-        if (n > 0) {
-            (void)hipEventRecord(v->pend_copied, v->copy_stream);      // whatever was queued on the copy stream has read them by then
-            tsdf_store::slots_release_after(v->store, &v->store->frames, held, n, &v->pend_copied, v);
-        }
-        return failed;
-    };
-    rc = store_slot(v, &v->store->frames, v->copy_stream, &slot, &dev);
-    if (rc) { slot = -1; return give_back(rc); }
-    hipLaunchKernelGGL(tsdfk::depth_u16_to_f32, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, v->copy_stream,
-                       static_cast<const uint16_t *>(raw_dev), static_cast<float *>(dev), v->cfg.im_height, v->cfg.im_width,
-                       1.0f / depth_factor, row_step, col_step);   // ref: examples/label_instance_rgbd.cpp:99-100 (fp32 reciprocal)
-    {
-        const hipError_t le = hipGetLastError();
-        if (le != hipSuccess) return give_back(fail(TSDF_ERR_HIP, "depth_u16_to_f32: %s", hipGetErrorString(le)));
-    }
-    // the raw slot is free once the conversion has run: released after an event of the copy stream
-    {
-        const hipError_t ee = hipEventRecord(v->pend_copied, v->copy_stream);
-        if (ee != hipSuccess) return give_back(fail(TSDF_ERR_HIP, "hipEventRecord: %s", hipGetErrorString(ee)));
-    }
-    tsdf_store::slots_release_after(v->store, &v->store->frames, &raw_slot, 1, &v->pend_copied, v);
-    raw_slot = -1;
-    if (defer) {
-        Collected c;
-        c.slot = slot; c.mask_slot = -1; c.dev = static_cast<float *>(dev); c.mask = nullptr;
-        return pool_slot_commit(v, c, cam2world);
-    }
-    {
-        const hipError_t we = hipStreamWaitEvent(v->stream, v->pend_copied, 0);
-        if (we != hipSuccess) return give_back(fail(TSDF_ERR_HIP, "hipStreamWaitEvent: %s", hipGetErrorString(we)));
-    }
-    float c2b[16];
-    compose_cam2base(v, cam2world, c2b);
-    rc = launch_integrate(v, static_cast<const float *>(dev), nullptr, c2b);
-    // (after a failed launch too: kernels it queued on the handle's stream may read the slot, so it goes back behind them)
-    const int rc_end = stage_end(v, &slot, 1);
-    return rc ? rc : rc_end;
+    return apply_host_frame(v, frame, cam2world, defer, true);
 }
 
 int tsdf_integrate_device(tsdf_volume *v, const float *depth_dev, const float cam2world[16])
 {
-    if (!v || !depth_dev || !cam2world) return fail(TSDF_ERR_INVALID, "tsdf_integrate_device: NULL argument");
-    const bool defer = v->defer_n > 1 && can_fuse(v);
-    int rc = bind_device(v, !defer);
-    if (rc) return rc;
-    if (defer) return collect_device_frame(v, depth_dev, nullptr, cam2world, nullptr);
-    float c2b[16];
-    compose_cam2base(v, cam2world, c2b);
-    return launch_integrate(v, depth_dev, nullptr, c2b);
+    return integrate_device_frame("tsdf_integrate_device", v, depth_dev, nullptr, false, cam2world, nullptr);
 }
 
 int tsdf_integrate_cam2base(tsdf_volume *v, const float *depth_dev, const float cam2base[16])
 {
-    if (!v || !depth_dev || !cam2base) return fail(TSDF_ERR_INVALID, "tsdf_integrate_cam2base: NULL argument");
-    const bool defer = v->defer_n > 1 && can_fuse(v);
-    int rc = bind_device(v, !defer);
-    if (rc) return rc;
-    if (defer) return collect_device_frame(v, depth_dev, nullptr, nullptr, cam2base);
-    return launch_integrate(v, depth_dev, nullptr, cam2base);
+    return integrate_device_frame("tsdf_integrate_cam2base", v, depth_dev, nullptr, false, nullptr, cam2base);
+}
+
+int tsdf_integrate_masked_device(tsdf_volume *v, const float *depth_dev, const uint8_t *mask_dev,
+                                 const float cam2world[16])
+{
+    return integrate_device_frame("tsdf_integrate_masked_device", v, depth_dev, mask_dev, true, cam2world, nullptr);
 }
 
 int tsdf_integrate_frames_device(tsdf_volume *v, const float *const *depth_dev, const uint8_t *const *masks_dev,
@@ -1405,33 +1404,7 @@ int tsdf_integrate_frames_labels_device(tsdf_volume *v, const float *const *dept
             return fail(TSDF_ERR_INVALID, "tsdf_integrate_frames_labels_device: frame %d has a NULL image", k);
     int rc = bind_device(v);
     if (rc) return rc;
-    bool seq_event = false;      // as integrate_frames: one "inputs readable" event for all launches of the sequence
-    for (int k = 0; k < n_frames && rc == TSDF_OK;) {
-        const int n = std::min(frames_per_launch(v), n_frames - k);
-        float c2b[16 * tsdfk::kMaxFramesPerLaunch];
-        for (int i = 0; i < n; ++i) compose_cam2base(v, cam2world + 16 * (k + i), c2b + 16 * i);
-        if (!seq_event && v->seq_ready && v->pipeline_ok && n_frames > n) {
-            HIP_TRY(hipEventRecord(v->seq_ready, v->stream));
-            seq_event = true;
-        }
-        rc = launch_multi(v, depth_dev + k, nullptr, c2b, n, label_im_dev + k, score_im_dev + k, seq_event ? v->seq_ready : nullptr);
-        k += n;
-    }
-    return rc;
-}
-
-int tsdf_integrate_masked_device(tsdf_volume *v, const float *depth_dev, const uint8_t *mask_dev,
-                                 const float cam2world[16])
-{
-    if (!v || !depth_dev || !mask_dev || !cam2world)
-        return fail(TSDF_ERR_INVALID, "tsdf_integrate_masked_device: NULL argument");
-    const bool defer = v->defer_n > 1 && can_fuse(v);
-    int rc = bind_device(v, !defer);
-    if (rc) return rc;
-    if (defer) return collect_device_frame(v, depth_dev, mask_dev, cam2world, nullptr);
-    float c2b[16];
-    compose_cam2base(v, cam2world, c2b);
-    return launch_integrate(v, depth_dev, mask_dev, c2b);
+    return integrate_frames(v, depth_dev, nullptr, cam2world, n_frames, label_im_dev, score_im_dev);   // (always through launch_multi)
 }
 
 int tsdf_sync(tsdf_volume *v)
@@ -1647,20 +1620,6 @@ int tsdf_colour_enable(tsdf_volume *v)
     return TSDF_OK;
 }
 
-static int launch_colour(tsdf_volume *v, const float *depth_dev, const uint8_t *rgb_dev, const float *c2b)
-{
-    const int nz = v->cfg.z_end - v->cfg.z_begin;
-    if (nz == 0) return TSDF_OK;
-    tsdfk::ColourParams cp;
-    cp.g = make_params(v, depth_dev, nullptr, c2b, 4);
-    cp.rgb = rgb_dev;
-    cp.colour = v->d_colour;
-    dim3 block(64, 4, 1), grid((cp.g.xgroups + 63) / 64, (v->cfg.dim_y + 3) / 4, nz);
-    hipLaunchKernelGGL(tsdfk::integrate_colour, grid, block, 0, v->stream, cp);
-    HIP_TRY(hipGetLastError());
-    return TSDF_OK;
-}
-
 int tsdf_integrate_colour_device(tsdf_volume *v, const float *depth_dev, const uint8_t *rgb_dev, const float cam2world[16])
 {
     if (!v || !depth_dev || !rgb_dev || !cam2world) return fail(TSDF_ERR_INVALID, "tsdf_integrate_colour_device: NULL argument");
@@ -1685,20 +1644,18 @@ int tsdf_integrate_rgbd(tsdf_volume *v, const float *depth_host, const uint8_t *
     HIP_TRY(v->rgb.take(&s));
     if (!s->dev) HIP_TRY(staged_alloc(*s, s->done, px * 3));
     std::memcpy(s->host, rgb_host, px * 3);           // the caller may free both images after we return
-    int slot = -1;
-    void *dev = nullptr;
-    rc = stage_begin(v, img, [&](float *pinned) { tsdf_host::copy_to_pinned(pinned, depth_host, img); }, &slot, &dev);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(s->dev, s->host, px * 3, hipMemcpyHostToDevice, v->copy_stream));
-    rc = stream_waits_for_copies(v);
-    if (rc) return rc;
-    float c2b[16];
-    compose_cam2base(v, cam2world, c2b);
-    rc = launch_integrate(v, static_cast<const float *>(dev), nullptr, c2b);
-    if (rc == TSDF_OK) rc = launch_colour(v, static_cast<const float *>(dev), s->dev, c2b);
-    if (rc) return rc;
-    HIP_TRY(v->rgb.consumed(s, v->stream));
-    return stage_end(v, &slot, 1);
+    {
+        StoreSlot frame;
+        rc = stage_frame(v, img, [&](float *pinned) { tsdf_host::copy_to_pinned(pinned, depth_host, img); }, frame);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(s->dev, s->host, px * 3, hipMemcpyHostToDevice, v->copy_stream));
+        rc = apply_host_frame(v, frame, cam2world, false, false, s->dev);
+    }
+    // a copy out of the colour image's slot has been queued: after a failure too (the frame's holder has then made the handle's
+    // stream wait for the copy stream) its last reader is in front of this point of the handle's stream
+    const hipError_t ce = v->rgb.consumed(s, v->stream);
+    if (rc == TSDF_OK && ce != hipSuccess) rc = fail(TSDF_ERR_HIP, "tsdf_integrate_rgbd: hipEventRecord failed: %s", hipGetErrorString(ce));
+    return rc;
 }
 
 int tsdf_download_colour(tsdf_volume *v, uint32_t *colour_host)

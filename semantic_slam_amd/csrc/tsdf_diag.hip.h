@@ -345,6 +345,14 @@ int tsdf_classification_info(tsdf_volume *v, double info_out[2])
     return TSDF_OK;
 }
 
+// (under the store's mutex alone: binding would apply the collected frames, whose slots are what the caller wants to see)
+int tsdf_store_stats(tsdf_volume *v, int64_t out[9])
+{
+    if (!v || !out) return fail(TSDF_ERR_INVALID, "tsdf_store_stats: NULL argument");
+    tsdf_store::store_counts(v->store, v, out);
+    return TSDF_OK;
+}
+
 int tsdf_last_cam2base(const tsdf_volume *v, float out[16])
 {
     if (!v || !out) return fail(TSDF_ERR_INVALID, "tsdf_last_cam2base: NULL argument");

@@ -51,12 +51,13 @@ void launch_ladder(const tsdf_volume *v, const tsdfk::IntegrateParams &p)
 }
 
 // One masked frame into one volume: tile table of depth x mask, then the class of every workgroup of the coming launch
-// (grid nbx x nby x nz; rows_per_wg as classify_workgroups takes it).  Sets p.wg_class.
-int classify_single(tsdf_volume *v, tsdfk::IntegrateParams &p, int nbx, int nby, int nz, int rows_per_wg)
+// (grid nbx x nby x nz; rows_per_wg as classify_workgroups takes it).  Sets p.wg_class.  `table`: the caller's, which releases it
+// after the launch that reads the classes.
+int classify_single(tsdf_volume *v, StoreSlot &table, tsdfk::IntegrateParams &p, int nbx, int nby, int nz, int rows_per_wg)
 {
-    float2 *tiles = nullptr;
-    int rc0 = tables_begin(v, &tiles);   // (released by the caller's tables_end() after the launch that reads the classes)
+    int rc0 = table.take(v, &v->store->tables, v->stream);
     if (rc0) return rc0;
+    float2 *const tiles = table.as<float2>();
     const size_t n_wg = (size_t)nbx * nby * nz;
     HIP_TRY(v->d_wg_class.ensure(n_wg));
     const float *d = p.depth;
@@ -85,11 +86,12 @@ int launch_integrate_experiment(tsdf_volume *v, const float *depth_dev, const ui
     if (variant == 11) {   // masked, row-mapped, classified per workgroup (256 x 8 voxels)
         v->flags_known_zero = false;
         const dim3 grid((p.xgroups + 63) / 64, (p.dim_y + 7) / 8, p.nz);
-        int rc = classify_single(v, p, (int)grid.x, (int)grid.y, (int)grid.z, 8);
+        StoreSlot table;
+        int rc = classify_single(v, table, p, (int)grid.x, (int)grid.y, (int)grid.z, 8);
         if (rc) return rc;
         hipLaunchKernelGGL((tsdfk::ladder_tile<2, true, true, true, true, false, true, false, true>), grid, dim3(64, 4, 1), 0, v->stream, p);
         HIP_TRY(hipGetLastError());
-        return tables_end(v);
+        return table.release();
     }
     // which launches keep the free-space summary up to date: the SUM kernels; the rows kernel and the plain tile variants do not
     const bool summary = variant != 2 && ((variant >= 32 && variant < 64) || (variant >= 80 && variant < 96) || variant >= 112);
@@ -158,13 +160,14 @@ int launch_single_experiment(tsdf_volume *v, tsdfk::IntegrateParams &common, tsd
     const int nz = v->cfg.z_end - v->cfg.z_begin;
     dim3 block(64, 4, 1), grid((v->chunks_per_slice + 3) / 4, 1, nz);
     tsdfk::IntegrateParams cp = make_params(v, depth_dev, pose.mask, c2b, 4);
-    int rc = classify_single(v, cp, (int)grid.x, 1, nz, 0);
+    StoreSlot table;
+    int rc = classify_single(v, table, cp, (int)grid.x, 1, nz, 0);
     if (rc) return rc;
     common.wg_class = cp.wg_class;
     hipLaunchKernelGGL((tsdfk::integrate_multi_single_cls<true, true, true>), grid, block, 0, v->stream, common, pose);
     HIP_TRY(hipGetLastError());
     *handled = true;
-    return tables_end(v);
+    return table.release();
 }
 
 // The fused launches launch_multi_experiment queues itself (launch_multi sizes the product's work list only for the others).

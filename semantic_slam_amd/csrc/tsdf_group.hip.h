@@ -290,20 +290,15 @@ int tsdf_group_integrate(tsdf_group *g, const float *depth_host, const float cam
         int rc0 = bind_device(v);      // device current; frames given to a borrowed slab handle come first
         if (rc0) return rc0;
         // a frame slot of the slab's store, filled on its copy stream (overlapping the slab's previous kernel)
-        int slot = -1;
-        void *dev = nullptr;
-        int rc = store_slot(v, &v->store->frames, v->copy_stream, &slot, &dev);
+        StoreSlot frame;
+        int rc = frame.take(v, &v->store->frames, v->copy_stream);
         if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(dev, s->host, img, hipMemcpyHostToDevice, v->copy_stream));
+        HIP_TRY(hipMemcpyAsync(frame.as<float>(), s->host, img, hipMemcpyHostToDevice, v->copy_stream));
         if (!s->copied[i]) HIP_TRY(event_create(s->copied[i]));
         HIP_TRY(hipEventRecord(s->copied[i], v->copy_stream));
         s->copy_queued[i] = true;
         HIP_TRY(hipStreamWaitEvent(v->stream, s->copied[i], 0));
-        float c2b[16];
-        compose_cam2base(v, cam2world, c2b);
-        rc = launch_integrate(v, static_cast<const float *>(dev), nullptr, c2b);
-        if (rc) return rc;
-        rc = stage_end(v, &slot, 1);
+        rc = launch_staged_frame(v, frame, cam2world);
         if (rc) return rc;
     }
     return TSDF_OK;
