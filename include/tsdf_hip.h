@@ -171,8 +171,9 @@ int tsdf_upload(tsdf_volume *vol, const float *tsdf_host, const float *weight_ho
 
 /*
  * Device addresses of the slab's two arrays (x-fastest, slab-local z).  The library keeps a
- * small free-space summary of the TSDF array; after WRITING TSDF values through
- * this pointer call tsdf_refresh_summary().  Reading needs nothing.
+ * small summary of both arrays (segments whose TSDF values are all 1, segments whose weights are all one
+ * count); after WRITING TSDF values OR WEIGHTS through these pointers call
+ * tsdf_refresh_summary().  Reading needs nothing.
  */
 int tsdf_refresh_summary(tsdf_volume *vol);
 int tsdf_device_ptrs(tsdf_volume *vol, float **tsdf_dev, float **weight_dev);

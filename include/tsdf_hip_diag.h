@@ -111,6 +111,14 @@ int tsdf_brick_list_stats(tsdf_volume *vol, uint64_t counts_out[4]);
 int tsdf_classification_info(tsdf_volume *vol, double info_out[2]);
 
 /*
+ * The summary words of the slab (one per 256-voxel segment; csrc/host_derive.h, "the summary word"): out = {segments,
+ * those whose word says that every TSDF value is 1 (bit 0), those whose word carries a weight run (bit 2: every weight
+ * is the count in the word, and the one-frame kernel does not load them)}.  Applies the collected frames and synchronises
+ * the stream; {0, 0, 0} for a grid without summary (dim_x % 4 != 0).
+ */
+int tsdf_summary_stats(tsdf_volume *vol, uint64_t out[3]);
+
+/*
  * The handle's share of the staging store that the handles of its device and image size have in common (frame, mask and
  * tile-table slots): for the frames, the masks and the tables in turn, out = {slots the handle holds, slots it has
  * released that no one has reused yet, slots the class has in the store}.  Reads the store's bookkeeping only: it applies no

@@ -3,6 +3,8 @@
 // Plain C++ (no HIP, no device types): tsdf_capi.hip includes it for the product, and the CPU sanitizer run compiles it by
 // itself with -fsanitize=address,undefined (tests/test_sanitizers.py).
 // Also the launch policy: what a kernel variant means, tile tables, pipelining, classification, the sweep's cache window, batches.
+// And the encoding of the summary word with its transition under a one-frame launch, which the kernels share (the one place
+// where a function here carries the host / device marker, and only when the HIP compiler reads it).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -279,6 +281,49 @@ inline bool batch_classifies(Classify mode, int members, int64_t launch_voxels)
 // members fill the GPU one after the other)
 constexpr int kBatchSideStreams = 4;
 inline int batch_lanes(int members) { return members < 8 ? 1 : kBatchSideStreams; }
+
+// ---- the summary word --------------------------------------------------------------------------------------------
+// One 32-bit word per 256-voxel row segment (tsdf_kernels.hip.h, IntegrateParams::flags).  It holds knowledge about the arrays
+// that lets a load be skipped; the arrays themselves always stay current.
+//   bit 0       every TSDF value of the segment is exactly 1.0f
+//   bit 1       every weight of the segment is finite and >= 0
+//   bit 2       every weight of the segment has the bit pattern of (float)c, c the count below (a "weight run"; implies bit 1)
+//   bits 8..31  the count c, 0 <= c <= kMaxRunCount; zero whenever bit 2 is clear
+// Weights on the one-frame path are counts (every update adds exactly 1.0f), so a segment that every frame so far updated
+// wholly or not at all holds 256 identical integers, and the one-frame kernel takes them from the word instead of the array.
+#if defined(__HIPCC__)
+#define TSDF_HOST_DEVICE __host__ __device__
+#else
+#define TSDF_HOST_DEVICE
+#endif
+
+constexpr uint32_t kSummaryOnes = 1u, kSummarySane = 2u, kSummaryRun = 4u;
+constexpr int kRunCountShift = 8;
+constexpr uint32_t kMaxRunCount = (1u << 24) - 1;   // (float)c is exact, and so is c + 1, up to here
+constexpr uint32_t kSummaryFresh = kSummaryOnes | kSummarySane | kSummaryRun;   // create / reset: TSDF 1, weight 0 = count 0
+
+TSDF_HOST_DEVICE inline bool word_has_run(uint32_t word) { return (word & kSummaryRun) != 0u; }
+TSDF_HOST_DEVICE inline uint32_t word_run_count(uint32_t word) { return word >> kRunCountShift; }
+// bits 0 and 1 of `low` with a run of count c <= kMaxRunCount
+TSDF_HOST_DEVICE inline uint32_t word_with_run(uint32_t low, uint32_t c)
+{
+    return (low & (kSummaryOnes | kSummarySane)) | kSummaryRun | (c << kRunCountShift);
+}
+// ... and without one
+TSDF_HOST_DEVICE inline uint32_t word_without_run(uint32_t word) { return word & (kSummaryOnes | kSummarySane); }
+
+// The word of a segment after a one-frame launch: `touched` = some voxel of it was updated, `all_updated` = all 256 were,
+// `left_not_one` = some updated TSDF value came out != 1.0f.  An untouched segment keeps its word.  A run goes on, one higher,
+// only where the whole segment was updated and the next count still fits; the weights themselves are always w + 1.0f.
+TSDF_HOST_DEVICE inline uint32_t word_after_update(uint32_t word, bool touched, bool all_updated, bool left_not_one)
+{
+    if (!touched) return word;
+    if (left_not_one) word &= ~kSummaryOnes;
+    if (!word_has_run(word)) return word;
+    const uint32_t c = word_run_count(word);
+    if (!all_updated || c >= kMaxRunCount) return word_without_run(word);
+    return word_with_run(word, c + 1u);
+}
 
 // One block carved into regions that each start on a 256-byte boundary: add(bytes) gives the next region's offset, total() the
 // bytes of the block so far (the last region is not padded).

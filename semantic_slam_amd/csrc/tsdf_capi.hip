@@ -157,6 +157,7 @@ struct tsdf_volume {
     int tile = 0;                    // pixels per edge of the depth tiles of this handle's classified launches (tsdf_host::tile_edge)
     bool fine_tables = false;        // ... and, beside them, 4-pixel tiles for brick-sized boxes (tsdf_host::fine_tables)
     bool flags_known_zero = false;
+    bool runs_maybe_set = false;     // summary words may carry a weight run (bit 2 and a count): see forget_weight_runs
 #ifdef TSDF_EXPERIMENTS
     DevBuf<unsigned int> d_super;    // per super-brick frame words of the current fused brick launch (classify_superbricks)
 #endif
@@ -499,9 +500,24 @@ int build_tile_tables(hipStream_t stream, const tsdf_config &c, const tsdfk::Int
     return TSDF_OK;
 }
 
+// Weight runs (host_derive.h, "the summary word") are kept by integrate_tile alone.  Every other launch that writes weights
+// and keeps the summary -- the fused kernels, the brick kernels, the batched kernel -- knows bits 0 and 1 only, so the runs
+// are forgotten ahead of it: one small pass over the words (2 MB at 512^3), once, since no such launch sets a run again.
+int forget_weight_runs(tsdf_volume *v)
+{
+    if (!v->runs_maybe_set || v->n_flags == 0) return TSDF_OK;
+    const unsigned blocks = (unsigned)std::min<size_t>((v->n_flags + 255) / 256, (size_t)256 * 8);
+    hipLaunchKernelGGL(tsdfk::forget_runs, dim3(blocks), dim3(256), 0, v->stream, v->d_flags.get(), v->n_flags);
+    HIP_TRY(hipGetLastError());
+    v->runs_maybe_set = false;
+    return TSDF_OK;
+}
+
 // The same with wavefront bricks (rows that divide into them): class per brick, then the brick kernel.  Queues the launch.
 int launch_masked_bricks(tsdf_volume *v, tsdfk::IntegrateParams &p)
 {
+    int rcf = forget_weight_runs(v);
+    if (rcf) return rcf;
     const int blocks = (p.brick_groups * p.bricks_per_group + 3) / 4, nz = (p.nz + p.brick_s - 1) / p.brick_s;   // slice groups
     StoreSlot table;      // the frame's depth tile tables, first written on the handle's stream
     int rc0 = table.take(v, &v->store->tables, v->stream);
@@ -529,6 +545,7 @@ int drop_summary(tsdf_volume *v)
     if (v->flags_known_zero || v->n_flags == 0) return TSDF_OK;
     HIP_TRY(hipMemsetAsync(v->d_flags, 0, v->n_flags * sizeof(uint32_t), v->stream));
     v->flags_known_zero = true;
+    v->runs_maybe_set = false;
     return TSDF_OK;
 }
 
@@ -542,6 +559,7 @@ int rebuild_summary(tsdf_volume *v)
                        v->chunks_per_slice);
     HIP_TRY(hipGetLastError());
     v->flags_known_zero = false;
+    v->runs_maybe_set = true;
     return TSDF_OK;
 }
 
@@ -641,10 +659,12 @@ int launch_integrate(tsdf_volume *v, const float *depth_dev, const uint8_t *mask
             if (v->variant == 11 && classify) return launch_integrate_experiment(v, depth_dev, mask_dev, c2b);
 #endif
             set_sweep(v, p);
+            v->runs_maybe_set = true;      // ... and the weight runs
             hipLaunchKernelGGL((tsdfk::integrate_tile<2, true>), grid, block, 0, v->stream, p);
         }
     } else {
         set_sweep(v, p);
+        v->runs_maybe_set = true;
         hipLaunchKernelGGL((tsdfk::integrate_tile<2, false>), grid, block, 0, v->stream, p);
     }
     HIP_TRY(hipGetLastError());
@@ -667,6 +687,10 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
     const tsdf_config &c = v->cfg;
     const int nz = c.z_end - c.z_begin;
     if (nz == 0 || n == 0) return TSDF_OK;
+    {
+        int rc = forget_weight_runs(v);    // every kernel below keeps bits 0 and 1 of the summary only
+        if (rc) return rc;
+    }
     auto fill_pose = [&](tsdfk::FramePose &fp, int f) {
         pose_from_params(fp, make_params(v, depth_dev[f], masks_dev ? masks_dev[f] : nullptr, c2b + 16 * f, 4));
         fp.label_im = label_ims ? label_ims[f] : nullptr;
@@ -1146,8 +1170,9 @@ int fill(tsdf_volume *v)
     hipLaunchKernelGGL(tsdfk::fill_grid, dim3(blocks), dim3(256), 0, v->stream, v->d_tsdf, v->d_weight, n);
     HIP_TRY(hipGetLastError());
     if (v->n_flags) {  // every TSDF value is 1: every segment flag is set
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)v->d_flags, 3, v->n_flags, v->stream));
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)v->d_flags, (int)tsdf_host::kSummaryFresh, v->n_flags, v->stream));   // ... and every weight is the count 0
         v->flags_known_zero = false;
+        v->runs_maybe_set = true;
     }
     return TSDF_OK;
 }
@@ -1876,6 +1901,10 @@ int tsdf_batch_integrate_device(tsdf_batch *b, const float *depth_dev, const uin
         defer = defer && tsdf_host::batch_defers(n, total);
         if (defer) return batch_collect(b, depth_dev, masks_dev, cam2world);
         int rc = batch_flush(b);   // the policy changed between calls (tsdf_set_deferral, a kernel variant)
+        if (rc) return rc;
+    }
+    for (tsdf_volume *v : b->vols) {   // the batched kernel maintains the summary, but not the weight runs (on the batch's stream, which the members share)
+        int rc = forget_weight_runs(v);
         if (rc) return rc;
     }
     decltype(b->blocks)::Slot *s = nullptr;

@@ -345,6 +345,26 @@ int tsdf_classification_info(tsdf_volume *v, double info_out[2])
     return TSDF_OK;
 }
 
+int tsdf_summary_stats(tsdf_volume *v, uint64_t out[3])
+{
+    if (!v || !out) return fail(TSDF_ERR_INVALID, "tsdf_summary_stats: NULL argument");
+    int rc = bind_device(v);
+    if (rc) return rc;
+    out[0] = out[1] = out[2] = 0;
+    if (v->n_flags == 0) { HIP_TRY(hipStreamSynchronize(v->stream)); return TSDF_OK; }
+    DevPtr<unsigned long long> d;
+    HIP_TRY(dev_alloc(d, 3 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(d, 0, 3 * sizeof(unsigned long long), v->stream));
+    const unsigned blocks = (unsigned)std::min<size_t>((v->n_flags + 255) / 256, (size_t)256 * 8);
+    hipLaunchKernelGGL(tsdfk::summary_stats, dim3(blocks), dim3(256), 0, v->stream, (const uint32_t *)v->d_flags.get(), v->n_flags, d.get());
+    HIP_TRY(hipGetLastError());
+    unsigned long long h[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, v->stream));
+    HIP_TRY(hipStreamSynchronize(v->stream));
+    out[0] = v->n_flags; out[1] = h[1]; out[2] = h[2];
+    return TSDF_OK;
+}
+
 // (under the store's mutex alone: binding would apply the collected frames, whose slots are what the caller wants to see)
 int tsdf_store_stats(tsdf_volume *v, int64_t out[9])
 {

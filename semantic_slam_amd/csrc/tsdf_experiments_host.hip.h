@@ -85,6 +85,8 @@ int launch_integrate_experiment(tsdf_volume *v, const float *depth_dev, const ui
     tsdfk::IntegrateParams p = make_params(v, depth_dev, mask_dev, c2b, 4);
     if (variant == 11) {   // masked, row-mapped, classified per workgroup (256 x 8 voxels)
         v->flags_known_zero = false;
+        int rcf = forget_weight_runs(v);
+        if (rcf) return rcf;
         const dim3 grid((p.xgroups + 63) / 64, (p.dim_y + 7) / 8, p.nz);
         StoreSlot table;
         int rc = classify_single(v, table, p, (int)grid.x, (int)grid.y, (int)grid.z, 8);
@@ -100,6 +102,8 @@ int launch_integrate_experiment(tsdf_volume *v, const float *depth_dev, const ui
         if (rc) return rc;
     } else {
         v->flags_known_zero = false;
+        int rc = forget_weight_runs(v);    // the ladder's summary kernels know bits 0 and 1 only
+        if (rc) return rc;
     }
     if (variant == 2) {
         dim3 block(64, 4, 1), grid((p.xgroups + 63) / 64, (c.dim_y + 3) / 4, nz);

@@ -19,6 +19,8 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "host_derive.h"
+
 namespace tsdfk {
 
 struct IntegrateParams {
@@ -43,8 +45,11 @@ struct IntegrateParams {
     // free-space summary: one word per 256-voxel row segment (index row * nseg + segment):
     //   bit 0 = every TSDF value of the segment is exactly 1.0f
     //   bit 1 = every weight of the segment is finite and >= 0 (stays true under += 1)
-    // both hold after tsdf_create/tsdf_reset; bit 0 is cleared by the first update that leaves a
-    // value != 1; both are rebuilt from the arrays after tsdf_upload (recompute_flags)
+    //   bit 2 = every weight of the segment is (float)c, bits 8..31 = c (a weight run; host_derive.h, "the summary word")
+    // all hold after tsdf_create/tsdf_reset (c = 0); bit 0 is cleared by the first update that leaves a
+    // value != 1, bit 2 by the first launch that updates part of a segment (integrate_tile) or that does not keep
+    // the count (every other kernel: the host clears the runs ahead of it); all are rebuilt from the arrays after
+    // tsdf_upload (recompute_flags)
     uint32_t *flags;
     int nseg;               // segments per row = dim_x / 256 (row-mapped kernels; dim_x % 256 == 0 only)
     // Linear ("flat") view of a slice, used by the kernels that serve any dim_x % 4 == 0: a slice is
@@ -201,6 +206,11 @@ __global__ __launch_bounds__(256) void integrate_scalar(IntegrateParams p)
 //    in for it and the same arithmetic runs on it -- so free space moves 8 B per voxel, not 12.
 //    The first update that leaves a value != 1 stores the row and clears the flag; flags are
 //    only ever set by fill_grid / recompute_flags (create, reset, upload).
+//  * weight runs.  While the word says "every weight of the segment is the count c" the weight quad is not loaded
+//    either: (float)c stands in for it, the same arithmetic runs on it and the weights are stored as ever, so a
+//    band row moves 12 B per voxel, not 16, and free space 4, not 8.  A launch that updates all 256 voxels of the
+//    segment counts c up in the word; one that updates only some of them ends the run (every weight it did not
+//    load is still c, so what it stores is right).  One store per row and launch, and only of a word that changed.
 //  * exact shared-reciprocal projection and one-instruction pixel rounding (below).
 // The earlier stages of this ladder (no elision, no summary, R = 1 / 4, speculative volume loads, depth tiles staged in
 // LDS) are measurement builds: tsdf_experiments.hip.h, -DTSDF_EXPERIMENTS.
@@ -313,6 +323,12 @@ __device__ __forceinline__ void vol_store_p(bool nt, float *p, float4 v)
     if (nt) vol_store<true>(p, v);
     else vol_store<false>(p, v);
 }
+
+// Store policy of a row's weights: those of a weight run are not read back by the next launch, so they stream even inside the
+// cache window.
+__device__ __forceinline__ std::true_type weights_nt(std::true_type, uint32_t) { return {}; }
+__device__ __forceinline__ bool weights_nt(std::false_type, uint32_t word) { return tsdf_host::word_has_run(word); }
+__device__ __forceinline__ bool weights_nt(bool nt, uint32_t word) { return nt || tsdf_host::word_has_run(word); }
 
 // depth[px] through a 32-bit byte offset from the wave-uniform base: the load takes the base from SGPRs
 // and the offset from one VGPR (global_load_dword v, v_off, s[base]) instead of a 64-bit address built
@@ -475,11 +491,19 @@ __device__ __forceinline__ void integrate_tile_body(const IntegrateParams &p, co
     if (!any) return;
 
     // ---- phase 3: the volume quads; truncated distance -----------------------------------------
+    // (a row's lanes all loaded the same word: in a scalar register from here on, so that its tests are scalar branches)
+#pragma unroll
+    for (int r = 0; r < R; ++r) fl[r] = __builtin_amdgcn_readfirstlane(fl[r]);
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         if (rowany[r]) {
             const float *wp = p.weight + row0 + (size_t)r * p.dim_x, *tp = p.tsdf + row0 + (size_t)r * p.dim_x;
-            w4[r] = vol_load_p(lnt, wp);
+            if (tsdf_host::word_has_run(fl[r])) {
+                const float c = (float)tsdf_host::word_run_count(fl[r]);   // exact: c < 2^24
+                w4[r] = make_float4(c, c, c, c);
+            } else {
+                w4[r] = vol_load_p(lnt, wp);
+            }
             if (!(fl[r] & 1u)) t4[r] = vol_load_p(lnt, tp);
         }
     }
@@ -500,15 +524,21 @@ __device__ __forceinline__ void integrate_tile_body(const IntegrateParams &p, co
     auto store_rows = [&](auto snt_c) {
     #pragma unroll
         for (int r = 0; r < R; ++r) {
-            if (fl[r] == 3u && __ballot(bandr[r]) == 0ull) {
+            // The row's word after this launch (host_derive.h, word_after_update).  All 256 voxels updated = all 64 lanes
+            // updated their four: lanes with nothing to update have left above, so they are counted, not assumed.
+            const bool touched = __ballot(rowany[r]) != 0ull;
+            const bool whole = tsdf_host::word_has_run(fl[r]) && __popcll(__ballot(upd[r][0] & upd[r][1] & upd[r][2] & upd[r][3])) == 64;
+            if ((fl[r] & 3u) == 3u && __ballot(bandr[r]) == 0ull) {
                 // Free space, wave-uniform: every TSDF value of the segment is 1, every weight is finite
                 // and >= 0, and every updated lane has dist == 1.  Then num = fl(1*w + 1) = fl(w + 1) = wn,
                 // the quotient is exactly 1, the TSDF row is unchanged: only the weights move.
                 if (rowany[r]) {
                     const float4 w = w4[r];
-                    vol_store_p(snt_c, p.weight + row0 + (size_t)r * p.dim_x,
+                    vol_store_p(weights_nt(snt_c, fl[r]), p.weight + row0 + (size_t)r * p.dim_x,
                                     make_float4(upd[r][0] ? w.x + 1.0f : w.x, upd[r][1] ? w.y + 1.0f : w.y,
                                                 upd[r][2] ? w.z + 1.0f : w.z, upd[r][3] ? w.w + 1.0f : w.w));
+                    const uint32_t word = tsdf_host::word_after_update(fl[r], touched, whole, false);
+                    if (word != fl[r]) p.flags[flag0 + (size_t)r * p.nseg] = word;
                 }
                 continue;
             }
@@ -540,18 +570,18 @@ __device__ __forceinline__ void integrate_tile_body(const IntegrateParams &p, co
                 tv[j] = newt;
                 wv[j] = upd[r][j] ? wn[j] : wv[j];
             }
-            if ((fl[r] & 1u) && __ballot(notone) != 0ull) {
-                if (notone) p.flags[flag0 + (size_t)r * p.nseg] = fl[r] & 2u;  // segment no longer all ones
-            }
+            // one store of the final word (segment no longer all ones, run counted up or ended), none in the steady state
+            const uint32_t word = tsdf_host::word_after_update(fl[r], touched, whole, (fl[r] & 1u) && __ballot(notone) != 0ull);
             const bool store_t = __ballot(rowany[r] && changed) != 0ull;
             if (rowany[r]) {
+                if (word != fl[r]) p.flags[flag0 + (size_t)r * p.nseg] = word;
                 if (store_t) vol_store_p(snt_c, p.tsdf + row0 + (size_t)r * p.dim_x, make_float4(tv[0], tv[1], tv[2], tv[3]));
-                vol_store_p(snt_c, p.weight + row0 + (size_t)r * p.dim_x, make_float4(wv[0], wv[1], wv[2], wv[3]));
+                vol_store_p(weights_nt(snt_c, fl[r]), p.weight + row0 + (size_t)r * p.dim_x, make_float4(wv[0], wv[1], wv[2], wv[3]));
             }
         }
     };
-    // Register allocation, measured: a branch per store costs the masked kernel 7 VGPRs (53), one branch around all
-    // of this phase costs the plain kernel 7 (53); each kernel takes the form that keeps it at 46.
+    // Register allocation, measured: a branch per store cost the masked kernel 7 VGPRs, one branch around all of this phase the
+    // plain kernel 7; each takes the cheaper form (with the weight runs: plain 48, masked 53 inside the window; 8 waves both).
     if constexpr (MASKED == 1) {
         if (snt) store_rows(std::true_type{});
         else store_rows(std::false_type{});
@@ -706,7 +736,8 @@ __global__ __launch_bounds__(256) void recompute_flags(const float *tsdf, const 
     if (chunk >= chunks_per_slice) return;
     const int q = chunk * 64 + threadIdx.x;
     const size_t base = ((size_t)blockIdx.z * quads_per_slice + q) * 4;
-    bool ones = true, sane = true;
+    bool ones = true, sane = true, same = true;
+    uint32_t first = 0u;
     if (q < quads_per_slice) {
         const float4 t = *reinterpret_cast<const float4 *>(tsdf + base);
         const float4 w = *reinterpret_cast<const float4 *>(weight + base);
@@ -714,9 +745,42 @@ __global__ __launch_bounds__(256) void recompute_flags(const float *tsdf, const 
                __float_as_uint(t.z) == 0x3f800000u && __float_as_uint(t.w) == 0x3f800000u;
         sane = w.x >= 0.0f && w.x < 3.0e38f && w.y >= 0.0f && w.y < 3.0e38f && w.z >= 0.0f && w.z < 3.0e38f &&
                w.w >= 0.0f && w.w < 3.0e38f;
+        first = __float_as_uint(w.x);
+        same = __float_as_uint(w.y) == first && __float_as_uint(w.z) == first && __float_as_uint(w.w) == first;
     }
-    const uint32_t f = (__ballot(!ones) == 0ull ? 1u : 0u) | (__ballot(!sane) == 0ull ? 2u : 0u);
+    uint32_t f = (__ballot(!ones) == 0ull ? 1u : 0u) | (__ballot(!sane) == 0ull ? 2u : 0u);
+    // a weight run: one bit pattern throughout (lane 0 of a chunk always holds a quad), and that of a count
+    const uint32_t lead = __builtin_amdgcn_readfirstlane(first);
+    same = same && (q >= quads_per_slice || first == lead);
+    if ((f & 2u) && __ballot(!same) == 0ull) {
+        const float wl = __uint_as_float(lead);          // finite and >= 0 (bit 1)
+        if (wl <= (float)tsdf_host::kMaxRunCount) {
+            const uint32_t c = (uint32_t)wl;
+            if (__float_as_uint((float)c) == lead) f = tsdf_host::word_with_run(f, c);   // an integer, and not -0
+        }
+    }
     if (threadIdx.x == 0) flags[(size_t)blockIdx.z * chunks_per_slice + chunk] = f;
+}
+
+// The weight runs are forgotten (word &= 3) ahead of a launch that writes weights and keeps only bits 0 and 1 of the summary.
+__global__ __launch_bounds__(256) void forget_runs(uint32_t *flags, size_t n)
+{
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) flags[i] &= 3u;
+}
+
+// Segments, those with bit 0, those with bit 2 (tsdf_summary_stats).  out[3] must be zero.
+__global__ __launch_bounds__(256) void summary_stats(const uint32_t *flags, size_t n, unsigned long long *out)
+{
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    unsigned int ones = 0, runs = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint32_t w = flags[i];
+        ones += w & 1u;
+        runs += (w >> 2) & 1u;
+    }
+    for (int off = 32; off > 0; off >>= 1) { ones += __shfl_down(ones, off); runs += __shfl_down(runs, off); }
+    if ((threadIdx.x & 63) == 0) { atomicAdd(out + 1, (unsigned long long)ones); atomicAdd(out + 2, (unsigned long long)runs); }
 }
 
 // Raw 16-bit depth -> metres on the device: out = raw * scale where (row % row_step == 0 and
