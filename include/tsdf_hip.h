@@ -21,6 +21,13 @@
  *     (ref: the reference holds one TSDF per Object and never shares it, src/Engine.cpp:170-172)
  *   - "host" pointers are ordinary memory the caller owns and may free as soon as the call
  *     returns; "device" pointers are HBM addresses valid on the handle's device
+ *   - a caller's device pointer (every *_dev argument: depth, mask, rgb, raw, label, score, member, render, cluster and halo
+ *     images, in and out) needs the alignment of its element type only -- 4 bytes for float / int32 / uint32, 2 for uint16,
+ *     none for bytes -- so a sub-buffer of a frame ring or an image ROI may be passed as it is.  Exactly the stated number
+ *     of elements is read, or written, and nothing outside them: not a byte before the first element or after the last, not
+ *     even a load whose value is discarded.  Where a kernel takes a wider access it chooses it at run time from the
+ *     pointer's low bits and the image size and falls back to element accesses otherwise (DESIGN.md lists which;
+ *     tests/test_gpu_caller_buffers.py holds every such entry point to this between guard bands)
  */
 #ifndef TSDF_HIP_H
 #define TSDF_HIP_H
