@@ -117,6 +117,14 @@ int tsdf_classification_info(tsdf_volume *vol, double info_out[2]);
  * the stream; {0, 0, 0} for a grid without summary (dim_x % 4 != 0).
  */
 int tsdf_summary_stats(tsdf_volume *vol, uint64_t out[3]);
+/*
+ * The summary words themselves, in the order the kernels index them (word of row segment s of row y of local slice z:
+ * (z * dim_y + y) * (dim_x / 256) + s for rows of a multiple of 256 voxels; otherwise word of 256-voxel chunk c of slice z:
+ * z * ceil(dim_x * dim_y / 256) + c).  *count = the number of words (0 for a grid without summary, dim_x % 4 != 0); they are
+ * copied to out_host when capacity >= *count, and nothing is written to it otherwise (out_host may be NULL with capacity
+ * 0 to ask for the count).  Read-only: applies the collected frames and synchronises the stream, as tsdf_summary_stats does.
+ */
+int tsdf_summary_words(tsdf_volume *vol, uint32_t *out_host, int64_t capacity, int64_t *count);
 
 /*
  * The handle's share of the staging store that the handles of its device and image size have in common (frame, mask and

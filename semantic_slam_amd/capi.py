@@ -21,7 +21,7 @@ ABI_SYMBOLS = [
     "tsdf_integrate_u16", "tsdf_convert_depth_u16", "tsdf_set_deferral",
     "tsdf_integrate_device", "tsdf_integrate_cam2base", "tsdf_integrate_masked_device",
     "tsdf_integrate_frames_device",
-    "tsdf_sync", "tsdf_download", "tsdf_copy_slices", "tsdf_upload", "tsdf_refresh_summary", "tsdf_device_ptrs", "tsdf_slab_voxels", "tsdf_frames_per_launch", "tsdf_shortcut_stats", "tsdf_brick_list_stats", "tsdf_classification_info", "tsdf_store_stats", "tsdf_summary_stats",
+    "tsdf_sync", "tsdf_download", "tsdf_copy_slices", "tsdf_upload", "tsdf_refresh_summary", "tsdf_device_ptrs", "tsdf_slab_voxels", "tsdf_frames_per_launch", "tsdf_shortcut_stats", "tsdf_brick_list_stats", "tsdf_classification_info", "tsdf_store_stats", "tsdf_summary_stats", "tsdf_summary_words",
     "tsdf_get_config", "tsdf_last_cam2base", "tsdf_set_stream", "tsdf_get_stream",
     "tsdf_count_surface", "tsdf_extract_surface", "tsdf_extract_crossings", "tsdf_extract_mesh", "tsdf_save_mesh_ply", "tsdf_save_mesh_welded_ply", "tsdf_save_ply", "tsdf_save_bin", "tsdf_load_bin", "tsdf_save_state", "tsdf_load_state",
     "tsdf_integrate_sequence_timed", "tsdf_integrate_frames_timed", "tsdf_probe_graph_replay", "tsdf_probe_stream", "tsdf_selftest_fastdiv", "tsdf_selftest_fastdiv_band", "tsdf_selftest_round", "tsdf_selftest_tile_tables", "tsdf_set_kernel_variant", "tsdf_set_brick_shape", "tsdf_brick_shape", "tsdf_default_brick_shape", "tsdf_last_error",
@@ -49,7 +49,7 @@ DIAG_SYMBOLS = [
     "tsdf_integrate_sequence_timed", "tsdf_integrate_frames_timed",
     "tsdf_probe_graph_replay", "tsdf_probe_stream",
     "tsdf_selftest_fastdiv", "tsdf_selftest_fastdiv_band", "tsdf_selftest_round", "tsdf_selftest_tile_tables",
-    "tsdf_shortcut_stats", "tsdf_brick_list_stats", "tsdf_classification_info", "tsdf_store_stats", "tsdf_summary_stats", "tsdf_frames_per_launch", "tsdf_last_cam2base",
+    "tsdf_shortcut_stats", "tsdf_brick_list_stats", "tsdf_classification_info", "tsdf_store_stats", "tsdf_summary_stats", "tsdf_summary_words", "tsdf_frames_per_launch", "tsdf_last_cam2base",
     "tsdf_set_kernel_variant", "tsdf_set_brick_shape", "tsdf_brick_shape", "tsdf_default_brick_shape",
 ]
 
@@ -229,6 +229,8 @@ def load():
         L.tsdf_store_stats.argtypes = [vp, i64p]
     if hasattr(L, "tsdf_summary_stats"):    # (likewise)
         L.tsdf_summary_stats.argtypes = [vp, vp]
+    if hasattr(L, "tsdf_summary_words"):    # (likewise)
+        L.tsdf_summary_words.argtypes = [vp, vp, C.c_int64, i64p]
     L.tsdf_get_config.argtypes = [vp, C.POINTER(TsdfConfig)]
     L.tsdf_last_cam2base.argtypes = [vp, vp]
     L.tsdf_set_stream.argtypes = [vp, vp]
@@ -684,6 +686,17 @@ class Volume:
         out = (C.c_uint64 * 3)()
         check(self.lib.tsdf_summary_stats(self._h, out), "tsdf_summary_stats")
         return tuple(int(x) for x in out)
+
+    def summary_words(self):
+        """The summary words of the slab as a uint32 array, in the kernels' order (include/tsdf_hip_diag.h); empty for a
+        grid without summary (dim_x % 4 != 0).  Applies the collected frames and synchronises the stream."""
+        n = C.c_int64(0)
+        check(self.lib.tsdf_summary_words(self._h, None, 0, C.byref(n)), "tsdf_summary_words")
+        out = np.zeros(int(n.value), np.uint32)
+        if out.size:
+            check(self.lib.tsdf_summary_words(self._h, out.ctypes.data, out.size, C.byref(n)), "tsdf_summary_words")
+            assert int(n.value) == out.size
+        return out
 
     @property
     def frames_per_launch(self):

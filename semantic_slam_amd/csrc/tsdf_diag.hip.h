@@ -365,6 +365,18 @@ int tsdf_summary_stats(tsdf_volume *v, uint64_t out[3])
     return TSDF_OK;
 }
 
+int tsdf_summary_words(tsdf_volume *v, uint32_t *out_host, int64_t capacity, int64_t *count)
+{
+    if (!v || !count || capacity < 0 || (capacity > 0 && !out_host)) return fail(TSDF_ERR_INVALID, "tsdf_summary_words: bad argument");
+    int rc = bind_device(v);
+    if (rc) return rc;
+    *count = (int64_t)v->n_flags;
+    if (v->n_flags > 0 && capacity >= (int64_t)v->n_flags)
+        HIP_TRY(hipMemcpyAsync(out_host, v->d_flags.get(), v->n_flags * sizeof(uint32_t), hipMemcpyDeviceToHost, v->stream));
+    HIP_TRY(hipStreamSynchronize(v->stream));
+    return TSDF_OK;
+}
+
 // (under the store's mutex alone: binding would apply the collected frames, whose slots are what the caller wants to see)
 int tsdf_store_stats(tsdf_volume *v, int64_t out[9])
 {

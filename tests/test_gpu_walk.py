@@ -3,10 +3,19 @@
 on the device and in the model, and every observing step -- download, labels, colour, surface count, extent, raycast, the
 counts of a merge -- is compared at once, bit for bit and field for field.  Deferral, kernel variants, brick shapes and
 streams change between the steps and must change no result.  A failure names the seed, the step and the last five ops; the
-case's id replays it alone."""
+case's id replays it alone.
+
+The summary words (tests/summary_spec.py) are read at every download and must be sound for the arrays just downloaded:
+no word may say more than its segment bears out, whatever launched.  The "runs" class keeps the one-frame kernel's weight
+runs alive under every op and holds bit 2 and the count of every word to the prediction after every mutating step (the whole
+word after reset and after a rebuild); test_walk_batch_runs does the same for a batch with a row-mapped member.  A failure
+there names the segment and the word in hex as well."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
+import summary_spec as ss
 import walk_cases as wc
 from semantic_slam_amd import capi
 
@@ -38,6 +47,21 @@ def raycast_params(cfg):
 
 def at_pixels(images, px):
     return {k: v[px[:, 1], px[:, 0]] for k, v in images.items()}
+
+
+class DeviceArray:
+    """n float32 values at a device address, for torch.as_tensor."""
+
+    def __init__(self, ptr, n):
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": "<f4", "data": (ptr, False), "version": 2}
+
+
+def sound_download(vol, lay):
+    """The arrays, with the summary words read beside them held to what the arrays bear out."""
+    words = vol.summary_words()
+    t, w = vol.download()
+    ss.assert_sound(lay, words, t, w, "summary words at a download")
+    return t, w
 
 
 class Inputs:
@@ -74,6 +98,8 @@ class DeviceWalk:
         self.path = str(tmp_path / "state.bin")
         self.vol, self.partner = capi.Volume(inputs["cfg"]), capi.Volume(inputs["partner_cfg"])
         self.ray = raycast_params(inputs["cfg"])
+        self.cuda = cuda
+        self.lay = ss.Layout((inputs["cfg"].dim_x, inputs["cfg"].dim_y, inputs["cfg"].dim_z))
 
     def close(self):
         self.vol.close()
@@ -146,7 +172,11 @@ class DeviceWalk:
             v.colour_enable()
             self.colour = True
         elif op == "download":
-            return v.download()
+            return sound_download(v, self.lay)
+        elif op == "summary_words":                         # (the words first: the download must not be what makes them right)
+            return (v.summary_words(),) + v.download()
+        elif op == "refresh_external":
+            self.refresh_external(a["patch"])
         elif op == "download_labels":
             return v.download_labels()
         elif op == "download_colour":
@@ -162,6 +192,22 @@ class DeviceWalk:
         else:
             raise AssertionError(f"no such op: {op}")
         return None
+
+    def refresh_external(self, patch):
+        """The header's contract for external writes: the arrays through tsdf_device_ptrs, written on the handle's stream,
+        then tsdf_refresh_summary."""
+        v, torch = self.vol, self.cuda
+        idx, t, w = wc.external_patch(self.lay, patch)
+        n = v.n_voxels
+        assert idx.dtype == np.int64 and 0 <= idx.min() and idx.max() < n == self.lay.n_vox and t.size == w.size == idx.size
+        t_ptr, w_ptr = v.device_ptrs()
+        stream = C.c_void_p()
+        capi.check(v.lib.tsdf_get_stream(v._h, C.byref(stream)), "tsdf_get_stream")
+        with torch.cuda.stream(torch.cuda.ExternalStream(stream.value)):
+            i = torch.from_numpy(idx).cuda()
+            for ptr, values in ((t_ptr, t), (w_ptr, w)):
+                torch.as_tensor(DeviceArray(ptr, n), device="cuda").index_put_((i,), torch.from_numpy(values).cuda())
+        capi.check(v.lib.tsdf_refresh_summary(v._h), "tsdf_refresh_summary")
 
     def raycast(self, view, device):
         v, out = self.vol, self.dev.out
@@ -219,7 +265,7 @@ def test_walk_volume(cuda, oracle, tmp_path, seed, cls):
     steps = wc.script(seed, cls)
     device = DeviceWalk(cuda, steps.inputs, tmp_path)
     try:
-        walk(steps, device, wc.Walk(oracle, steps.inputs), wc.compare, f"walk seed {seed} on the {cls} grid")
+        walk(steps, device, wc.Walk(oracle, steps.inputs, predict=cls == "runs"), wc.compare, f"walk seed {seed} on the {cls} grid")
     finally:
         device.close()
 
@@ -271,5 +317,53 @@ def test_walk_batch(cuda, oracle, seed):
     device = DeviceBatchWalk(cuda, steps.inputs)
     try:
         walk(steps, device, wc.BatchWalk(oracle, steps.inputs), wc.compare_batch, f"batch walk seed {seed}")
+    finally:
+        device.close()
+
+
+class DeviceBatchRunsWalk:
+    """walk_cases.batch_runs_script on the device: every member handle launches one frame per call, so the batch applies every
+    frame at once with its batched kernel."""
+
+    def __init__(self, cuda, inputs):
+        self.inp, self.dev = inputs, Inputs(cuda, inputs)
+        self.batch = capi.Batch(inputs["cfgs"])
+        for v in self.batch.volumes:
+            v.set_deferral(0)
+        self.lays = [ss.Layout((c.dim_x, c.dim_y, c.dim_z)) for c in inputs["cfgs"]]
+
+    def close(self):
+        self.batch.close()
+
+    def apply(self, op, a):
+        b, inp, dev = self.batch, self.inp, self.dev
+        i = a.get("member")
+        m = b.volumes[i] if i is not None else None
+        if op == "integrate":
+            b.integrate_device(dev.depth[a["frame"]].data_ptr(), [None if k is None else dev.masks[k].data_ptr() for k in a["masks"]],
+                               inp["frames"][a["frame"]]["pose"])
+        elif op == "member_integrate":
+            m.integrate_device(dev.depth[a["frame"]].data_ptr(), inp["frames"][a["frame"]]["pose"])
+        elif op == "upload":
+            m.upload(*inp["states"][i][a["state"]])
+        elif op == "reset":
+            m.reset()
+        elif op == "fuse":
+            return b.volumes[a["dst"]].fuse_from(b.volumes[a["src"]], fuse_params(a["write"]))
+        elif op == "summary_words":
+            return (m.summary_words(),) + m.download()
+        elif op == "download":
+            return sound_download(m, self.lays[i])
+        else:
+            raise AssertionError(f"no such op: {op}")
+        return None
+
+
+@pytest.mark.parametrize("seed", wc.BATCH_RUNS_SEEDS)
+def test_walk_batch_runs(cuda, oracle, seed):
+    steps = wc.batch_runs_script(seed)
+    device = DeviceBatchRunsWalk(cuda, steps.inputs)
+    try:
+        walk(steps, device, wc.BatchRunsWalk(oracle, steps.inputs), wc.compare_batch_runs, f"batch runs walk seed {seed}")
     finally:
         device.close()
