@@ -212,6 +212,8 @@ __global__ __launch_bounds__(256) void integrate_scalar(IntegrateParams p)
 //    segment counts c up in the word; one that updates only some of them ends the run (every weight it did not
 //    load is still c, so what it stores is right).  One store per row and launch, and only of a word that changed.
 //  * exact shared-reciprocal projection and one-instruction pixel rounding (below).
+//  * diff / trunc through the launch-wide refined reciprocal on wavefronts that took the fast projection path (fast_div_r,
+//    as in the fused kernels): 5 instructions per quotient instead of 11, the same bits.
 // The earlier stages of this ladder (no elision, no summary, R = 1 / 4, speculative volume loads, depth tiles staged in
 // LDS) are measurement builds: tsdf_experiments.hip.h, -DTSDF_EXPERIMENTS.
 // ------------------------------------------------------------------------------------------
@@ -509,10 +511,25 @@ __device__ __forceinline__ void integrate_tile_body(const IntegrateParams &p, co
     }
     float dist[R][4];
     if (__ballot(band) != 0ull) {
+        if (fast && p.trunc_fast != 0) {
+            // The same quotient from the launch-wide refined reciprocal, 5 instructions instead of 11 (fast_div_r; the
+            // condition and the argument are the fused kernels', tsdf_multiframe.hip.h).  2^-20 <= trunc <= 2^20 is
+            // trunc_fast.  The wavefront took the fast projection path, so where a quotient is used cz > cz_margin >=
+            // 2^-57 and diff = depth - cz is 0 or at least 2^-81 in magnitude, at most 2^60.  Lanes whose geometry test
+            // failed read pixel 0: their diff is a difference of two finite floats below 2^59 (or NaN), the sequence
+            // neither traps nor overflows on it, and the quotient is never used (upd is false).  Wavefronts wholly
+            // behind the camera have no updated voxel and left above.
+            const float trunc_r1 = refined_rcp(p.trunc);   // once per wavefront
 #pragma unroll
-        for (int r = 0; r < R; ++r)
+            for (int r = 0; r < R; ++r)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) dist[r][j] = fminf(1.0f, diff[r][j] / p.trunc);  // ref: :53
+                for (int j = 0; j < 4; ++j) dist[r][j] = fminf(1.0f, fast_div_r(diff[r][j], p.trunc, trunc_r1));
+        } else {
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) dist[r][j] = fminf(1.0f, diff[r][j] / p.trunc);  // ref: :53
+        }
     } else {
 #pragma unroll
         for (int r = 0; r < R; ++r)
@@ -581,7 +598,8 @@ __device__ __forceinline__ void integrate_tile_body(const IntegrateParams &p, co
         }
     };
     // Register allocation, measured: a branch per store cost the masked kernel 7 VGPRs, one branch around all of this phase the
-    // plain kernel 7; each takes the cheaper form (with the weight runs: plain 48, masked 53 inside the window; 8 waves both).
+    // plain kernel 7; each takes the cheaper form (with the weight runs: plain 48, masked 53 inside the window; with diff / trunc through the
+    // shared reciprocal: plain 52, masked 53; 8 waves both).
     if constexpr (MASKED == 1) {
         if (snt) store_rows(std::true_type{});
         else store_rows(std::false_type{});

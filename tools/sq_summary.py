@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-dispatch averages of the SQ counters tools/sq_counters.sh collected for the dominant fused kernel, with the derived
+"""Per-dispatch averages of the SQ counters tools/sq_counters.sh collected for the dominant Integrate kernel (fused, brick or one-frame), with the derived
 per-wavefront / per-voxel-frame figures DESIGN.md section 4 argues with.  Writes gpurun_out/sq_<tag>.json."""
 import csv
 import glob
@@ -9,10 +9,11 @@ import sys
 
 tag = sys.argv[1]
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+KERNELS = ("integrate_multi_inline<", "integrate_brick_list<", "integrate_tile<")
 acc, kernel = {}, None
 for part in "ab":
     f = glob.glob(os.path.join(root, "gpurun_out", f"sq_{tag}_{part}", "**", "*counter_collection.csv"), recursive=True)[0]
-    rows = [r for r in csv.DictReader(open(f)) if "integrate_multi_inline<" in r["Kernel_Name"] or "integrate_brick_list<" in r["Kernel_Name"]]
+    rows = [r for r in csv.DictReader(open(f)) if any(k in r["Kernel_Name"] for k in KERNELS)]
     # the dominant instantiation (most dispatches), full-size launches only (the largest grid)
     names = {}
     for r in rows:
@@ -39,6 +40,13 @@ d["cycles_per_wave_frame_per_simd"] = cyc / (waves / 1024 * fpl)
 d["valu_insts_per_wave_frame"] = d["valu_insts_per_wave"] / fpl
 d["cycles_per_valu_inst_if_valu_alone"] = cyc / (acc["SQ_INSTS_VALU"] / 1024)
 d["scalar_unit_busy_if_1p19_cycles_each"] = acc["SQ_INSTS_SALU"] / 256 * 1.19 / cyc
+# where a wavefront's time goes (all three in quad-cycles, summed over the wavefronts): an instruction of it executing, waiting
+# for a counter (memory, mostly), ready but not picked by the issue arbiter
+d["wave_time_share_executing"] = acc["SQ_ACTIVE_INST_ANY"] / acc["SQ_WAVE_CYCLES"]
+d["wave_time_share_waiting_for_memory"] = acc["SQ_WAIT_ANY"] / acc["SQ_WAVE_CYCLES"]
+d["wave_time_share_stalled_at_issue"] = acc["SQ_WAIT_INST_ANY"] / acc["SQ_WAVE_CYCLES"]
+# a SIMD issues at most one VALU instruction every 2 cycles on this mix (packed and 64-wide fp32 alike count once here)
+d["valu_issue_slot_share_at_2_cycles_each"] = acc["SQ_INSTS_VALU"] / 1024 * 2.0 / cyc
 acc["_derived"] = d
 acc["_note"] = (f"per-dispatch averages of {kernel} ({line['config']['workload'][:60]}...), two rocprofv3 --pmc passes; SQ_WAVE_CYCLES / "
                 "SQ_WAIT_* count quad-cycles; GRBM_GUI_ACTIVE is summed over the 8 XCDs; valu_insts_per_voxel_frame counts a wave "
