@@ -5,6 +5,8 @@
 // Also the launch policy: what a kernel variant means, tile tables, pipelining, classification, the sweep's cache window, batches.
 // And the encoding of the summary word with its transition under a one-frame launch, which the kernels share (the one place
 // where a function here carries the host / device marker, and only when the HIP compiler reads it).
+// What a launch's grids, class table, work list and table offsets follow from -- a slab's geometry -- is in launch_geometry.h,
+// which builds on this file.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -180,6 +182,8 @@ inline size_t tile_table_elems(int tiles_w, int tiles_h)
 
 constexpr int64_t kMaxTableTiles = 16384;
 inline bool tiles_fit(int tiles_w, int tiles_h) { return (int64_t)tiles_w * tiles_h <= kMaxTableTiles; }
+// Tiles of `edge` pixels along an image axis of n pixels (the last one may overhang the image)
+inline int tiles_along(int n, int edge) { return (n + edge - 1) / edge; }
 
 // Pixels per depth tile edge for a slab: 8 where a fused launch is long enough to repay tables four times as large (the finer
 // tiles leave a fifth fewer wavefront-frames to the per-voxel path: tsdf_multiframe.hip.h), 16 otherwise and wherever the finer
@@ -190,7 +194,7 @@ inline bool tiles_fit(int tiles_w, int tiles_h) { return (int64_t)tiles_w * tile
 constexpr int64_t kFineTileMinVoxels = 10000000;
 inline int tile_edge(const tsdf_config &c, bool batch_member)
 {
-    const int64_t fine_tiles = (int64_t)((c.im_width + 7) / 8) * ((c.im_height + 7) / 8);
+    const int64_t fine_tiles = (int64_t)tiles_along(c.im_width, 8) * tiles_along(c.im_height, 8);
     return (!batch_member && slab_voxels(c) >= kFineTileMinVoxels && fine_tiles <= kTileLdsEntries) ? 8 : 16;
 }
 
@@ -199,15 +203,25 @@ inline int tile_edge(const tsdf_config &c, bool batch_member)
 constexpr int64_t kFineLevelMinVoxels = 64000000;      // measured: 512^3 S-surf 0.0255 -> 0.0240 ms per frame, 320^3 0.0102 -> 0.0105
 inline bool fine_tables(const tsdf_config &c, int tile) { return tile == 8 && slab_voxels(c) >= kFineLevelMinVoxels; }
 
-// Bytes of a launch's table slot in the frame store: kMaxFramesPerLaunch coarse sparse tables, then (fine) as many fine ones;
-// 0 when the frame's tiles do not fit the tables.
-inline size_t launch_table_bytes(const tsdf_config &c, int tile, bool fine)
+// A launch's table slot in the frame store, in elements of two floats: kMaxFramesPerLaunch coarse sparse tables of coarse_elems
+// each from element 0, then (fine) as many fine ones of fine_elems each from fine_begin; all zero when the frame's tiles do not
+// fit the tables.  A frame's coarse table is f * coarse_elems into the slot, its fine one fine_begin + f * fine_elems.
+struct TableSlotLayout { size_t coarse_elems, fine_begin, fine_elems, bytes; };
+
+inline TableSlotLayout table_slot_layout(const tsdf_config &c, int tile, bool fine)
 {
-    const int tw = (c.im_width + tile - 1) / tile, th = (c.im_height + tile - 1) / tile;
-    const int fw = (c.im_width + kFineTile - 1) / kFineTile, fh = (c.im_height + kFineTile - 1) / kFineTile;
-    const size_t fine_elems = fine ? (size_t)kFineLevels * kFineLevels * fw * fh : 0;
-    return tiles_fit(tw, th) ? kMaxFramesPerLaunch * (tile_table_elems(tw, th) + fine_elems) * (2 * sizeof(float)) : 0;
+    const int tw = tiles_along(c.im_width, tile), th = tiles_along(c.im_height, tile);
+    if (!tiles_fit(tw, th)) return {0, 0, 0, 0};
+    TableSlotLayout l;
+    l.coarse_elems = tile_table_elems(tw, th);
+    l.fine_begin = (size_t)kMaxFramesPerLaunch * l.coarse_elems;
+    l.fine_elems = fine ? (size_t)kFineLevels * kFineLevels * tiles_along(c.im_width, kFineTile) * tiles_along(c.im_height, kFineTile) : 0;
+    l.bytes = (l.fine_begin + (size_t)kMaxFramesPerLaunch * l.fine_elems) * (2 * sizeof(float));
+    return l;
 }
+
+// Bytes of that slot (what the frame store is asked for): 0 when the frame's tiles do not fit the tables.
+inline size_t launch_table_bytes(const tsdf_config &c, int tile, bool fine) { return table_slot_layout(c, tile, fine).bytes; }
 
 // Pipelining pays where a launch is short enough for its small pre-pass kernels to matter and the chip is not full: measured,
 // same box, sequence path, pre-pass on the handle's stream / beside the previous launch: S-surf 200^3 0.00578 -> 0.00546 ms per

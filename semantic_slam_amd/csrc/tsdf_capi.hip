@@ -29,6 +29,7 @@
 
 #include "pose_math.h"
 #include "host_derive.h"
+#include "launch_geometry.h"
 #include "host_copy.h"
 #include "hip_owned.h"
 #include "frame_store.h"
@@ -108,7 +109,10 @@ struct tsdf_volume {
     tsdf_config cfg = {};
     float base2world_inv[16] = {};
     float last_cam2base[16] = {};
-    int64_t n_vox = 0;       // voxels in the slab
+    // the slab's geometry and the layout of its brick work list (launch_geometry.h): set at creation and again wherever the
+    // wavefront brick changes (set_brick); every launch takes its grids and buffer sizes from here
+    tsdf_host::SlabGeometry geo;
+    tsdf_host::WorkListLayout work;
     DevPtr<float> d_tsdf;
     DevPtr<float> d_weight;
     Stream own_stream;
@@ -149,13 +153,6 @@ struct tsdf_volume {
     StageRing<Staged<uint8_t>, kStageSlots> rgb;
     // free-space summary (one word per 256-voxel row segment), see tsdf_kernels.hip.h
     DevPtr<uint32_t> d_flags;
-    size_t n_flags = 0;
-    int nseg = 0;              // chunks per row when dim_x % 256 == 0 (row-mapped kernels), else 0
-    int chunks_per_slice = 0;  // ceil(dim_x*dim_y / 256)
-    bool flat = false;         // dim_x % 256 != 0: summary-maintaining launches use the flat mapping
-    int brick_q = 0, brick_r = 0, brick_s = 0;   // wavefront brick of the classified launches (choose_brick / tsdf_set_brick_shape); q = 0: none
-    int tile = 0;                    // pixels per edge of the depth tiles of this handle's classified launches (tsdf_host::tile_edge)
-    bool fine_tables = false;        // ... and, beside them, 4-pixel tiles for brick-sized boxes (tsdf_host::fine_tables)
     bool flags_known_zero = false;
     bool runs_maybe_set = false;     // summary words may carry a weight run (bit 2 and a count): see forget_weight_runs
 #ifdef TSDF_EXPERIMENTS
@@ -163,8 +160,6 @@ struct tsdf_volume {
 #endif
     DevBuf<uint4> d_work;        // work list of the current fused brick launch: {brick, slice group, free frames, skipped frames}
                                  // per live brick (classify_brick_list); capacity = every brick of the slab, once per list parity
-    int64_t work_nsuper = 0, work_bucket_supers = 0;   // super-bricks of the shape the list was sized for; most of them in one sub-list
-    int work_wedge_mode = -1;                  // ... and the list_bucket mode they were counted under
     // optional diagnostic counters (tsdf_shortcut_stats)
     DevPtr<unsigned int> d_shortcut_stats;
     // adaptive use of the classification: claims of the last classifying launch, read back without blocking
@@ -373,7 +368,25 @@ void choose_brick_for(const tsdf_config &c, int &bq, int &br, int &bs)
     tsdf_host::choose_brick_default(c, bq, br, bs);
 }
 
-void choose_brick(tsdf_volume *v) { choose_brick_for(v->cfg, v->brick_q, v->brick_r, v->brick_s); }
+dim3 to_dim3(const tsdf_host::Grid3 &g) { return dim3(g.x, g.y, g.z); }
+
+// The handle's wavefront brick (q = 0: none), and with it the brick view of its geometry and its work list's layout.
+void set_brick(tsdf_volume *v, int q, int r, int s)
+{
+    int wedge_mode = kWedgeMode;
+#ifdef TSDF_EXPERIMENTS
+    if (const char *e = std::getenv("TSDF_WEDGE_MODE")) wedge_mode = std::atoi(e);     // A/B knob of the measurement build
+#endif
+    v->geo = tsdf_host::slab_geometry(v->cfg, v->geo.tile, v->geo.fine, q, r, s);
+    v->work = tsdf_host::work_list_layout(v->cfg, v->geo, wedge_mode);
+}
+
+void choose_brick(tsdf_volume *v)
+{
+    int q, r, s;
+    choose_brick_for(v->cfg, q, r, s);
+    set_brick(v, q, r, s);
+}
 
 tsdfk::IntegrateParams make_params(const tsdf_volume *v, const float *depth_dev,
                                    const uint8_t *mask_dev, const float *c2b, int vx)
@@ -391,35 +404,28 @@ tsdfk::IntegrateParams make_params(const tsdf_volume *v, const float *depth_dev,
     p.tx = c2b[3]; p.ty = c2b[7]; p.tz = c2b[11];
     p.ox = c.origin[0]; p.oy = c.origin[1]; p.oz = c.origin[2];
     p.vs = c.voxel_size; p.trunc = c.trunc_margin; p.max_depth = c.max_depth;
-    p.dim_x = c.dim_x; p.dim_y = c.dim_y;
-    p.nz = c.z_end - c.z_begin; p.z_begin = c.z_begin;
+    const tsdf_host::SlabGeometry &geo = v->geo;
+    p.dim_x = geo.dim_x; p.dim_y = geo.dim_y;
+    p.nz = geo.nz; p.z_begin = c.z_begin;
     p.H = c.im_height; p.W = c.im_width;
-    p.xgroups = (c.dim_x + vx - 1) / vx;
+    p.xgroups = geo.xgroups(vx);
     p.flags = v->d_flags;
-    p.nseg = v->nseg;
-    p.quads_per_row = c.dim_x / 4;
-    p.quads_per_slice = (int)((int64_t)c.dim_x * c.dim_y / 4);
-    p.chunks_per_slice = v->chunks_per_slice;
+    p.nseg = geo.nseg;
+    p.quads_per_row = geo.quads_per_row;
+    p.quads_per_slice = geo.quads_per_slice;
+    p.chunks_per_slice = geo.chunks_per_slice;
     // brick view (tsdf_multiframe.hip.h, BRICK): the volume's wavefront brick, chosen at creation (choose_brick)
-    p.brick_q = v->brick_q; p.brick_r = v->brick_r; p.brick_s = v->brick_s > 0 ? v->brick_s : 1;
-    p.bricks_per_group = 0; p.brick_groups = 0;
-    p.brick_q_magic = 0; p.brick_per_magic = 0;
-    if (p.brick_q > 0) {
-        p.bricks_per_group = p.quads_per_row / p.brick_q;
-        p.brick_groups = (c.dim_y + p.brick_r - 1) / p.brick_r;
-        p.brick_q_magic = 65536 / p.brick_q + 1;
-        p.brick_per_magic = 65536 / (p.brick_q * p.brick_r) + 1;
-    }
+    p.brick_q = geo.brick_q; p.brick_r = geo.brick_r; p.brick_s = geo.brick_s;
+    p.bricks_per_group = geo.bricks_per_group; p.brick_groups = geo.brick_groups;
+    p.brick_q_magic = geo.brick_q_magic; p.brick_per_magic = geo.brick_per_magic;
     // guards of the exact shortcuts and margins of the box claims: host_derive.h (derive_projection_guards)
     const tsdf_host::ProjectionGuards g = tsdf_host::derive_projection_guards(c, c2b);
     p.cz_margin = g.cz_margin; p.fast_ok = g.fast_ok; p.trunc_fast = g.trunc_fast;
     p.cz_short = g.cz_short; p.cz_pad = g.cz_pad;
-    p.tiles_w = (c.im_width + v->tile - 1) / v->tile;
-    p.tiles_h = (c.im_height + v->tile - 1) / v->tile;
-    p.tile_inv = 1.0f / (float)v->tile;
+    p.tiles_w = geo.tiles_w; p.tiles_h = geo.tiles_h;
+    p.tile_inv = geo.tile_inv;
     p.fine = nullptr;                // set by the launch that builds the fine tables
-    p.fine_w = v->fine_tables ? (c.im_width + tsdfk::kFineTile - 1) / tsdfk::kFineTile : 0;
-    p.fine_h = v->fine_tables ? (c.im_height + tsdfk::kFineTile - 1) / tsdfk::kFineTile : 0;
+    p.fine_w = geo.fine_w; p.fine_h = geo.fine_h;
     p.px_margin_u = g.px_margin_u; p.px_margin_v = g.px_margin_v;
     p.shortcut_stats = v->d_shortcut_stats;
     p.claim_counter = nullptr;
@@ -447,6 +453,9 @@ static_assert(tsdf_host::kMaxFramesPerLaunch == tsdfk::kMaxFramesPerLaunch, "hos
 static_assert(tsdf_host::kTileLdsEntries == tsdfk::kTileLdsEntries, "host_derive.h: kTileLdsEntries");
 static_assert(tsdf_host::kFineTile == tsdfk::kFineTile, "host_derive.h: kFineTile");
 static_assert(tsdf_host::kFineLevels == tsdfk::kFineLevels, "host_derive.h: kFineLevels");
+static_assert(tsdf_host::kListBuckets == tsdfk::kListBuckets, "launch_geometry.h: kListBuckets");
+static_assert(tsdf_host::kSuperBX == tsdfk::kSuperBX && tsdf_host::kSuperBY == tsdfk::kSuperBY && tsdf_host::kSuperBZ == tsdfk::kSuperBZ &&
+              tsdf_host::kSuperBricks == tsdfk::kSuperBricks, "launch_geometry.h: kSuperBX / BY / BZ");
 using tsdf_host::tiles_fit;
 
 // Depth tile tables (summary + sparse table, tsdf_multiframe.hip.h) of n images depth[i] x mask[i] into tables[i], queued
@@ -475,13 +484,10 @@ int build_tile_tables(hipStream_t stream, const tsdf_config &c, const tsdfk::Int
         tp.max_depth = c.max_depth;
         tp.fine = fine; tp.fw = p.fine_w; tp.fh = p.fine_h;      // level (0, 0) of the fine tables in the same pass (8-pixel tiles)
         // whole-row reads: one wavefront per strip of 64 pixels (four 16-pixel tiles or eight 8-pixel ones)
-        if (p.tile_inv == 0.0625f) {
-            const int strips = ((p.tiles_w + 3) / 4) * p.tiles_h;
-            hipLaunchKernelGGL(tsdfk::depth_tile_summary<16>, dim3((unsigned)((strips + 3) / 4), m), dim3(64, 4), 0, stream, tp);
-        } else {
-            const int strips = ((p.tiles_w + 7) / 8) * p.tiles_h;
-            hipLaunchKernelGGL(tsdfk::depth_tile_summary<8>, dim3((unsigned)((strips + 3) / 4), m), dim3(64, 4), 0, stream, tp);
-        }
+        if (p.tile_inv == 0.0625f)
+            hipLaunchKernelGGL(tsdfk::depth_tile_summary<16>, to_dim3(tsdf_host::grid_tile_strips(p.tiles_w, p.tiles_h, 16, m)), dim3(64, 4), 0, stream, tp);
+        else
+            hipLaunchKernelGGL(tsdfk::depth_tile_summary<8>, to_dim3(tsdf_host::grid_tile_strips(p.tiles_w, p.tiles_h, 8, m)), dim3(64, 4), 0, stream, tp);
         if (p.tiles_w * p.tiles_h <= tsdfk::kTileLdsEntries) {
             // (1024 threads when the frame has thousands of tiles: each of the kernel's ~12 barrier-separated passes visits every tile)
             const unsigned threads = (p.tiles_w * p.tiles_h > 2048 && !beside_a_launch) ? 1024 : 256;
@@ -505,9 +511,8 @@ int build_tile_tables(hipStream_t stream, const tsdf_config &c, const tsdfk::Int
 // are forgotten ahead of it: one small pass over the words (2 MB at 512^3), once, since no such launch sets a run again.
 int forget_weight_runs(tsdf_volume *v)
 {
-    if (!v->runs_maybe_set || v->n_flags == 0) return TSDF_OK;
-    const unsigned blocks = (unsigned)std::min<size_t>((v->n_flags + 255) / 256, (size_t)256 * 8);
-    hipLaunchKernelGGL(tsdfk::forget_runs, dim3(blocks), dim3(256), 0, v->stream, v->d_flags.get(), v->n_flags);
+    if (!v->runs_maybe_set || v->geo.n_flags == 0) return TSDF_OK;
+    hipLaunchKernelGGL(tsdfk::forget_runs, to_dim3(tsdf_host::grid_summary_words(v->geo)), dim3(256), 0, v->stream, v->d_flags.get(), v->geo.n_flags);
     HIP_TRY(hipGetLastError());
     v->runs_maybe_set = false;
     return TSDF_OK;
@@ -518,12 +523,11 @@ int launch_masked_bricks(tsdf_volume *v, tsdfk::IntegrateParams &p)
 {
     int rcf = forget_weight_runs(v);
     if (rcf) return rcf;
-    const int blocks = (p.brick_groups * p.bricks_per_group + 3) / 4, nz = (p.nz + p.brick_s - 1) / p.brick_s;   // slice groups
+    const tsdf_host::BrickGrid bg = tsdf_host::brick_grid(v->geo);   // workgroups of four bricks x slice groups, and the class table's bytes
     StoreSlot table;      // the frame's depth tile tables, first written on the handle's stream
     int rc0 = table.take(v, &v->store->tables, v->stream);
     if (rc0) return rc0;
-    const size_t n_bricks = (size_t)blocks * nz * 4;
-    HIP_TRY(v->d_wg_class.ensure(n_bricks));
+    HIP_TRY(v->d_wg_class.ensure(bg.class_elems));
     const float *d = p.depth;
     const uint8_t *m = p.mask;
     int rc = build_tile_tables(v->stream, v->cfg, p, &d, &m, 1, table.as<float2>());
@@ -531,10 +535,10 @@ int launch_masked_bricks(tsdf_volume *v, tsdfk::IntegrateParams &p)
     tsdfk::FramePose pose;
     pose_from_params(pose, p);
     pose.tiles = table.as<float2>();
-    hipLaunchKernelGGL(tsdfk::classify_bricks, dim3((unsigned)((n_bricks + 255) / 256)), dim3(256), 0, v->stream, p, pose,
-                       v->d_wg_class, blocks, nz);
+    hipLaunchKernelGGL(tsdfk::classify_bricks, dim3((unsigned)((bg.class_elems + 255) / 256)), dim3(256), 0, v->stream, p, pose,
+                       v->d_wg_class, (int)bg.grid.x, (int)bg.grid.z);
     p.wg_class = v->d_wg_class;
-    hipLaunchKernelGGL((tsdfk::integrate_single_bricks<kBrickNT>), dim3(blocks, 1, nz), dim3(64, 4, 1), 0, v->stream, p, pose);
+    hipLaunchKernelGGL((tsdfk::integrate_single_bricks<kBrickNT>), to_dim3(bg.grid), dim3(64, 4, 1), 0, v->stream, p, pose);
     HIP_TRY(hipGetLastError());
     return table.release();
 }
@@ -542,8 +546,8 @@ int launch_masked_bricks(tsdf_volume *v, tsdfk::IntegrateParams &p)
 // Kernels that do not maintain the free-space summary must not leave stale "all ones" flags behind.
 int drop_summary(tsdf_volume *v)
 {
-    if (v->flags_known_zero || v->n_flags == 0) return TSDF_OK;
-    HIP_TRY(hipMemsetAsync(v->d_flags, 0, v->n_flags * sizeof(uint32_t), v->stream));
+    if (v->flags_known_zero || v->geo.n_flags == 0) return TSDF_OK;
+    HIP_TRY(hipMemsetAsync(v->d_flags, 0, v->geo.n_flags * sizeof(uint32_t), v->stream));
     v->flags_known_zero = true;
     v->runs_maybe_set = false;
     return TSDF_OK;
@@ -551,12 +555,9 @@ int drop_summary(tsdf_volume *v)
 
 int rebuild_summary(tsdf_volume *v)
 {
-    if (v->n_flags == 0 || v->n_vox == 0) return TSDF_OK;
-    const int nz = v->cfg.z_end - v->cfg.z_begin;
-    const int qps = (int)((int64_t)v->cfg.dim_x * v->cfg.dim_y / 4);
-    dim3 block(64, 4, 1), grid((v->chunks_per_slice + 3) / 4, 1, nz);
-    hipLaunchKernelGGL(tsdfk::recompute_flags, grid, block, 0, v->stream, v->d_tsdf, v->d_weight, v->d_flags, qps,
-                       v->chunks_per_slice);
+    if (v->geo.n_flags == 0 || v->geo.n_vox == 0) return TSDF_OK;
+    hipLaunchKernelGGL(tsdfk::recompute_flags, to_dim3(tsdf_host::grid_recompute_flags(v->geo)), dim3(64, 4, 1), 0, v->stream, v->d_tsdf,
+                       v->d_weight, v->d_flags, v->geo.quads_per_slice, v->geo.chunks_per_slice);
     HIP_TRY(hipGetLastError());
     v->flags_known_zero = false;
     v->runs_maybe_set = true;
@@ -621,36 +622,35 @@ void set_sweep(tsdf_volume *v, tsdfk::IntegrateParams &p)
 int launch_integrate(tsdf_volume *v, const float *depth_dev, const uint8_t *mask_dev,
                      const float *c2b)
 {
-    const tsdf_config &c = v->cfg;
-    const int nz = c.z_end - c.z_begin;
-    if (nz == 0) return TSDF_OK;  // empty slab: nothing to do
+    const tsdf_host::SlabGeometry &geo = v->geo;
+    if (geo.nz == 0) return TSDF_OK;  // empty slab: nothing to do
     std::memcpy(v->last_cam2base, c2b, sizeof v->last_cam2base);
 #ifdef TSDF_EXPERIMENTS
-    if (c.dim_x % 4 == 0 && (v->variant == 2 || (v->variant >= 16 && !mask_dev))) return launch_integrate_experiment(v, depth_dev, mask_dev, c2b);
+    if (geo.quad_rows && (v->variant == 2 || (v->variant >= 16 && !mask_dev))) return launch_integrate_experiment(v, depth_dev, mask_dev, c2b);
 #endif
     const tsdf_host::Variant var = variant_of(v->variant);
-    if (c.dim_x % 4 != 0 || var.scalar) {
+    if (!geo.quad_rows || var.scalar) {
         // rows that are not 16-byte aligned (or the scalar kernel asked for): one voxel per lane; it does not keep the summary
         int rc = drop_summary(v);
         if (rc) return rc;
         const tsdfk::IntegrateParams p = make_params(v, depth_dev, mask_dev, c2b, 1);
-        dim3 block(64, 4, 1), grid((c.dim_x + 63) / 64, (c.dim_y + 3) / 4, nz);
+        const dim3 block(64, 4, 1), grid = to_dim3(tsdf_host::grid_scalar_rows(geo));
         if (mask_dev) hipLaunchKernelGGL((tsdfk::integrate_scalar<true>), grid, block, 0, v->stream, p);
         else hipLaunchKernelGGL((tsdfk::integrate_scalar<false>), grid, block, 0, v->stream, p);
         HIP_TRY(hipGetLastError());
         return TSDF_OK;
     }
-    if (v->flat) {
+    if (geo.flat) {
         // rows that are not a multiple of 256 voxels: the flat mapping (every lane busy, summary kept)
         return launch_multi(v, &depth_dev, mask_dev ? &mask_dev : nullptr, c2b, 1);
     }
     tsdfk::IntegrateParams p = make_params(v, depth_dev, mask_dev, c2b, 4);
     v->flags_known_zero = false;   // integrate_tile keeps the free-space summary up to date
-    const dim3 block(64, 4, 1), grid((p.xgroups + 63) / 64, (p.dim_y + 7) / 8, p.nz);
+    const dim3 block(64, 4, 1), grid = to_dim3(tsdf_host::grid_quad_rows(geo, 8));
     if (mask_dev) {
         // per-object volumes see their instance only, so the bricks the tile table of depth x mask proves untouched are
         // told to leave (variant 7: never; small launches: not worth the three small dispatches ahead of it)
-        const bool classify = tsdf_host::classify_one_frame(var.classify, v->n_vox) && tiles_fit(p.tiles_w, p.tiles_h);
+        const bool classify = tsdf_host::classify_one_frame(var.classify, geo.n_vox) && tiles_fit(p.tiles_w, p.tiles_h);
         if (classify && p.brick_q > 0 && (!kExperiments || v->variant != 11)) {
             int rc = launch_masked_bricks(v, p);    // per wavefront brick: skipped by rows, slices and columns
             if (rc) return rc;
@@ -685,8 +685,8 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
                  const float *c2b, int n, const uint16_t *const *label_ims, const float *const *score_ims, hipEvent_t inputs_ready)
 {
     const tsdf_config &c = v->cfg;
-    const int nz = c.z_end - c.z_begin;
-    if (nz == 0 || n == 0) return TSDF_OK;
+    const tsdf_host::SlabGeometry &geo = v->geo;
+    if (geo.nz == 0 || n == 0) return TSDF_OK;
     {
         int rc = forget_weight_runs(v);    // every kernel below keeps bits 0 and 1 of the summary only
         if (rc) return rc;
@@ -710,19 +710,16 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
             if (rc || handled) return rc;
         }
 #endif
-        if (v->flat && pose.mask != nullptr && tsdf_host::classify_one_frame(variant_of(v->variant).classify, v->n_vox) &&
+        if (geo.flat && pose.mask != nullptr && tsdf_host::classify_one_frame(variant_of(v->variant).classify, geo.n_vox) &&
             tiles_fit(common.tiles_w, common.tiles_h) && common.brick_q > 0) {
             // one masked frame into a flat-mapped volume (the reference's 200^3 object grids), large enough to repay a class table
             tsdfk::IntegrateParams cp = make_params(v, depth_dev[0], pose.mask, c2b, 4);
             return launch_masked_bricks(v, cp);
         }
-        if (v->flat) {
-            dim3 grid((v->chunks_per_slice + 3) / 4, 1, nz);
-            hipLaunchKernelGGL((tsdfk::integrate_multi_single<true, true>), grid, block, 0, v->stream, common, pose);
-        } else {
-            dim3 grid((common.xgroups + 63) / 64, (c.dim_y + 3) / 4, nz);
-            hipLaunchKernelGGL((tsdfk::integrate_multi_single<true, false>), grid, block, 0, v->stream, common, pose);
-        }
+        if (geo.flat)
+            hipLaunchKernelGGL((tsdfk::integrate_multi_single<true, true>), to_dim3(tsdf_host::grid_flat(geo)), block, 0, v->stream, common, pose);
+        else
+            hipLaunchKernelGGL((tsdfk::integrate_multi_single<true, false>), to_dim3(tsdf_host::grid_quad_rows(geo, 4)), block, 0, v->stream, common, pose);
         HIP_TRY(hipGetLastError());
         return TSDF_OK;
     }
@@ -803,50 +800,21 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
         if (e != hipSuccess) return fail(TSDF_ERR_HIP, "side streams: %s", hipGetErrorString(e));
         v->pre_stream = std::move(a); v->rb_stream = std::move(b);
     }
-    const int nz_groups = (nz + mi.common.brick_s - 1) / mi.common.brick_s;   // a brick spans brick_s slices
     // the brick work list (below), sized and allocated before anything is queued on the side stream
     bool listed = classify;
 #ifdef TSDF_EXPERIMENTS
     listed = listed && !experiment_takes_multi(v, label_ims != nullptr, classify);
 #endif
-    tsdfk::BrickListParams bl;
-    int64_t n_super = 0, cap = 0;
+    const tsdf_host::WorkListLayout &wl = v->work;
     const size_t lists = v->pipeline_ok ? 2 : 1;     // one list per parity
     if (listed) {
         // A pre-pass compacts the bricks some frame may touch into a work list and the launch runs one wavefront per entry.
-        bl.nsx = (mi.common.bricks_per_group + tsdfk::kSuperBX - 1) / tsdfk::kSuperBX;
-        bl.nsy = (mi.common.brick_groups + tsdfk::kSuperBY - 1) / tsdfk::kSuperBY;
-        bl.nsz = (nz_groups + tsdfk::kSuperBZ - 1) / tsdfk::kSuperBZ;
-        bl.wedge_mode = kWedgeMode;
-#ifdef TSDF_EXPERIMENTS
-        if (const char *e = std::getenv("TSDF_WEDGE_MODE")) bl.wedge_mode = std::atoi(e);     // A/B knob of the measurement build
-#endif
-        bl.super_h = tsdfk::kSuperBY * mi.common.brick_r;
-        bl.super_d = tsdfk::kSuperBZ * mi.common.brick_s;
-        bl.wedge_oy = (int)std::lround(std::fmax(-30000.0, std::fmin(30000.0, (double)c.origin[1] / c.voxel_size)));
-        bl.wedge_oz = (int)std::lround(std::fmax(-30000.0, std::fmin(30000.0, (double)c.origin[2] / c.voxel_size + c.z_begin)));
-        bl.fy_px = (int)std::lround(std::fmax(1.0, std::fmin(16000.0, std::fabs((double)c.cam_K[4]))));
-        if (!(c.voxel_size > 0) || std::isnan(c.origin[1]) || std::isnan(c.origin[2])) bl.wedge_mode = 0;
-        n_super = (int64_t)bl.nsx * bl.nsy * bl.nsz;
-        // a sub-list must hold every brick of every super-brick list_bucket deals to it: counted exactly, once per grid shape
-        if (v->work_nsuper != n_super || v->work_wedge_mode != bl.wedge_mode) {
-            std::vector<int64_t> per((size_t)tsdfk::kListBuckets, 0);
-            for (int64_t id = 0; id < n_super; ++id) {      // the index order of classify_brick_list: slice groups fastest, then x, then y
-                const int sz = (int)(id % bl.nsz), sx = (int)((id / bl.nsz) % bl.nsx), sy = (int)((id / bl.nsz) / bl.nsx);
-                ++per[(size_t)tsdfk::list_bucket((unsigned int)id, sx, sy, sz, bl)];
-            }
-            v->work_bucket_supers = *std::max_element(per.begin(), per.end());
-            v->work_nsuper = n_super;
-            v->work_wedge_mode = bl.wedge_mode;
-        }
-        cap = v->work_bucket_supers * tsdfk::kSuperBricks;
-        const int64_t total = cap * tsdfk::kListBuckets;
-        if (total > 0x7fffffffll - 1024) return fail(TSDF_ERR_INVALID, "fused launch: %lld bricks exceed the work list's 32-bit index", (long long)total);
-        if (!v->d_work.fits(lists * (size_t)total) && v->d_work) {      // (a list in flight on either stream is done before its memory goes)
+        if (!wl.fits) return fail(TSDF_ERR_INVALID, "fused launch: %lld bricks exceed the work list's 32-bit index", (long long)wl.total);
+        if (!v->d_work.fits(lists * (size_t)wl.total) && v->d_work) {      // (a list in flight on either stream is done before its memory goes)
             if (v->pre_stream) HIP_TRY(hipStreamSynchronize(v->pre_stream));
             HIP_TRY(hipStreamSynchronize(v->stream));
         }
-        HIP_TRY(v->d_work.ensure(lists * (size_t)total));
+        HIP_TRY(v->d_work.ensure(lists * (size_t)wl.total));
     }
     const hipStream_t ps = pipelined ? v->pre_stream : v->stream;
     // a failure from here on joins the side stream back into the handle's stream (the table slot then goes back behind the join)
@@ -865,16 +833,15 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
     if (count_claims) mi.common.claim_counter = claims_p + 1;   // bucket 0's claims word (the pre-pass adds the bucket's offset)
     if (classify) {
         // depth tile tables of the n frames (two small launches), then the kernels that consult them
-        const size_t per_frame = tsdf_host::tile_table_elems(mi.common.tiles_w, mi.common.tiles_h);
+        const tsdf_host::TableSlotLayout slot = tsdf_host::table_slot_layout(c, geo.tile, geo.fine);
         int rc = table.take(v, &v->store->tables, ps);
         if (rc) return unwind(rc);
         float2 *const tiles = table.as<float2>();
-        // (fine_tables) the fine tables of the launch's frames sit behind its kMaxFramesPerLaunch coarse ones in the same slot
-        float2 *fine = v->fine_tables ? tiles + (size_t)tsdfk::kMaxFramesPerLaunch * per_frame : nullptr;
+        float2 *fine = geo.fine ? tiles + slot.fine_begin : nullptr;   // behind the coarse tables, in the same slot
         rc = build_tile_tables(ps, c, mi.common, depth_dev, masks_dev, n, tiles, claims_p, fine, pipelined);
         if (rc) return unwind(rc);
         mi.common.fine = fine;
-        for (int f = 0; f < n; ++f) mi.frames[f].tiles = tiles + (size_t)f * per_frame;
+        for (int f = 0; f < n; ++f) mi.frames[f].tiles = tiles + (size_t)f * slot.coarse_elems;
         for (int f = n; f < tsdfk::kMaxFramesPerLaunch; ++f) mi.frames[f] = mi.frames[0];
     }
     double claims_total = 0.0;
@@ -886,28 +853,32 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
     }
 #endif
     if (listed) {
-        const int64_t per_group = (int64_t)mi.common.brick_groups * mi.common.bricks_per_group;
+        const int64_t per_group = (int64_t)geo.brick_groups * geo.bricks_per_group;
         uint4 *const work_p = v->d_work + (size_t)P * (v->d_work.capacity() / lists);
+        tsdfk::BrickListParams bl;
         bl.list = work_p;
         bl.counters = reinterpret_cast<unsigned char *>(claims_p);
-        bl.bucket_cap = (unsigned int)cap;
+        bl.bucket_cap = (unsigned int)wl.bucket_cap;
         bl.poses = reinterpret_cast<tsdfk::ClassPoseTable *>(bl.counters + tsdfk::kCounterBytes);
-        hipLaunchKernelGGL(tsdfk::classify_brick_list, dim3((unsigned)((n_super + 3) / 4)), block, 0, ps, mi, bl);
+        bl.nsx = wl.nsx; bl.nsy = wl.nsy; bl.nsz = wl.nsz;
+        bl.wedge_mode = wl.wedge_mode; bl.wedge_oy = wl.wedge_oy; bl.wedge_oz = wl.wedge_oz;
+        bl.super_h = wl.super_h; bl.super_d = wl.super_d; bl.fy_px = wl.fy_px;
+        hipLaunchKernelGGL(tsdfk::classify_brick_list, to_dim3(tsdf_host::grid_classify_list(wl)), block, 0, ps, mi, bl);
         if (pipelined) {       // the Integrate kernel waits for its pre-pass; everything before it on the handle's stream does not
             HIP_TRY_OR(unwind, hipEventRecord(v->pre_done[P], ps));
             HIP_TRY_OR(unwind, hipStreamWaitEvent(v->stream, v->pre_done[P], 0));
         }
-        const dim3 grid_list((unsigned)(((cap + 3) / 4 + 1) * tsdfk::kListBuckets));   // front groups + back groups of every sub-list
-        const uint4 *wl = work_p;
+        const dim3 grid_list = to_dim3(tsdf_host::grid_brick_list(wl));   // front groups + back groups of every sub-list
+        const uint4 *wlist = work_p;
         const unsigned char *wc = bl.counters;
         const tsdfk::ClassPoseTable *wp = bl.poses;
         if (label_ims)
-            hipLaunchKernelGGL((tsdfk::integrate_brick_list<kBrickNT, true, false>), grid_list, block, 0, v->stream, mi, wl, wc, bl.bucket_cap, wp);
+            hipLaunchKernelGGL((tsdfk::integrate_brick_list<kBrickNT, true, false>), grid_list, block, 0, v->stream, mi, wlist, wc, bl.bucket_cap, wp);
         else if (any_mask)
-            hipLaunchKernelGGL((tsdfk::integrate_brick_list<kBrickNT, false, true>), grid_list, block, 0, v->stream, mi, wl, wc, bl.bucket_cap, wp);
+            hipLaunchKernelGGL((tsdfk::integrate_brick_list<kBrickNT, false, true>), grid_list, block, 0, v->stream, mi, wlist, wc, bl.bucket_cap, wp);
         else
-            hipLaunchKernelGGL((tsdfk::integrate_brick_list<kBrickNT, false, false>), grid_list, block, 0, v->stream, mi, wl, wc, bl.bucket_cap, wp);
-        claims_total = (double)per_group * nz_groups * n;   // wavefront-frames = bricks x frames
+            hipLaunchKernelGGL((tsdfk::integrate_brick_list<kBrickNT, false, false>), grid_list, block, 0, v->stream, mi, wlist, wc, bl.bucket_cap, wp);
+        claims_total = (double)per_group * geo.nz_groups * n;   // wavefront-frames = bricks x frames
         launched = true;
     }
     if (!launched) {
@@ -915,25 +886,22 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
         // (x, y) footprint, i.e. the windows of the launch's up to 32 depth frames (39 MB, more than the L2s hold) they gather
         // from (512^3 S-surf with a depth frame per pose: 0.1325 -> 0.1148 ms per frame; 1024^3 fr3 trajectory 0.529 ->
         // 0.376) -- and rotated, (z + x + y) mod n, so that a slice group's workgroups are spread over all eight XCDs.
-        dim3 grid_flat((v->chunks_per_slice + 3) / 4, 1, nz), grid_rows((mi.common.xgroups + 63) / 64, (c.dim_y + 3) / 4, nz);
-        const dim3 &g0 = v->flat ? grid_flat : grid_rows;
+        tsdf_host::Grid3 g0 = geo.flat ? tsdf_host::grid_flat(geo) : tsdf_host::grid_quad_rows(geo, 4);
         if (g0.x > 65535u) mi.z_fastest = 0;   // slices fastest puts the blocks of a slice into grid.z: 65535 at most (then: memory order)
-        if (mi.z_fastest) {
-            std::swap(grid_flat.x, grid_flat.z);
-            std::swap(grid_rows.x, grid_rows.z);
-        }
-        if (label_ims && v->flat)
-            hipLaunchKernelGGL((tsdfk::integrate_multi_inline<1, true, true, true, false>), grid_flat, block, 0, v->stream, mi);
+        if (mi.z_fastest) std::swap(g0.x, g0.z);
+        const dim3 grid = to_dim3(g0);
+        if (label_ims && geo.flat)
+            hipLaunchKernelGGL((tsdfk::integrate_multi_inline<1, true, true, true, false>), grid, block, 0, v->stream, mi);
         else if (label_ims)
-            hipLaunchKernelGGL((tsdfk::integrate_multi_inline<1, true, false, true, false>), grid_rows, block, 0, v->stream, mi);
-        else if (v->flat && any_mask)
-            hipLaunchKernelGGL((tsdfk::integrate_multi_inline<1, true, true, false, true>), grid_flat, block, 0, v->stream, mi);
-        else if (v->flat)
-            hipLaunchKernelGGL((tsdfk::integrate_multi_inline<1, true, true, false, false>), grid_flat, block, 0, v->stream, mi);
+            hipLaunchKernelGGL((tsdfk::integrate_multi_inline<1, true, false, true, false>), grid, block, 0, v->stream, mi);
+        else if (geo.flat && any_mask)
+            hipLaunchKernelGGL((tsdfk::integrate_multi_inline<1, true, true, false, true>), grid, block, 0, v->stream, mi);
+        else if (geo.flat)
+            hipLaunchKernelGGL((tsdfk::integrate_multi_inline<1, true, true, false, false>), grid, block, 0, v->stream, mi);
         else if (any_mask)
-            hipLaunchKernelGGL((tsdfk::integrate_multi_inline<1, true, false, false, true>), grid_rows, block, 0, v->stream, mi);
+            hipLaunchKernelGGL((tsdfk::integrate_multi_inline<1, true, false, false, true>), grid, block, 0, v->stream, mi);
         else
-            hipLaunchKernelGGL((tsdfk::integrate_multi_inline<1, true, false, false, false>), grid_rows, block, 0, v->stream, mi);
+            hipLaunchKernelGGL((tsdfk::integrate_multi_inline<1, true, false, false, false>), grid, block, 0, v->stream, mi);
     }
     if (listed) {
         // after this parity's Integrate kernel: its buffers may be rebuilt (a pre-pass on the side stream waits for it)
@@ -969,7 +937,7 @@ int frames_per_launch(const tsdf_volume *)
     return tsdfk::kMaxFramesPerLaunch;
 }
 
-bool can_fuse(const tsdf_volume *v) { return variant_of(v->variant).fuses && v->cfg.dim_x % 4 == 0; }
+bool can_fuse(const tsdf_volume *v) { return variant_of(v->variant).fuses && v->geo.quad_rows; }
 
 // A sequence of frames: fused frames_per_launch() at a time when the default kernel is selected.
 // label_ims / score_ims (both or neither): as launch_multi takes them; such a sequence is always fused.
@@ -1122,14 +1090,12 @@ int stage_frame_u16(tsdf_volume *v, const uint16_t *raw_host, float depth_factor
 // The colour pass of a frame (tsdf_colour.hip.h), queued behind its Integrate launch.
 int launch_colour(tsdf_volume *v, const float *depth_dev, const uint8_t *rgb_dev, const float *c2b)
 {
-    const int nz = v->cfg.z_end - v->cfg.z_begin;
-    if (nz == 0) return TSDF_OK;
+    if (v->geo.nz == 0) return TSDF_OK;
     tsdfk::ColourParams cp;
     cp.g = make_params(v, depth_dev, nullptr, c2b, 4);
     cp.rgb = rgb_dev;
     cp.colour = v->d_colour;
-    dim3 block(64, 4, 1), grid((cp.g.xgroups + 63) / 64, (v->cfg.dim_y + 3) / 4, nz);
-    hipLaunchKernelGGL(tsdfk::integrate_colour, grid, block, 0, v->stream, cp);
+    hipLaunchKernelGGL(tsdfk::integrate_colour, to_dim3(tsdf_host::grid_quad_rows(v->geo, 4)), dim3(64, 4, 1), 0, v->stream, cp);
     HIP_TRY(hipGetLastError());
     return TSDF_OK;
 }
@@ -1163,14 +1129,11 @@ int apply_host_frame(tsdf_volume *v, StoreSlot &frame, const float cam2world[16]
 
 int fill(tsdf_volume *v)
 {
-    if (v->n_vox == 0) return TSDF_OK;
-    size_t n = (size_t)v->n_vox;
-    int blocks = (int)std::min<size_t>((n / 4 + 255) / 256, 256 * 8);
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(tsdfk::fill_grid, dim3(blocks), dim3(256), 0, v->stream, v->d_tsdf, v->d_weight, n);
+    if (v->geo.n_vox == 0) return TSDF_OK;
+    hipLaunchKernelGGL(tsdfk::fill_grid, to_dim3(tsdf_host::grid_fill(v->geo)), dim3(256), 0, v->stream, v->d_tsdf, v->d_weight, (size_t)v->geo.n_vox);
     HIP_TRY(hipGetLastError());
-    if (v->n_flags) {  // every TSDF value is 1: every segment flag is set
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)v->d_flags, (int)tsdf_host::kSummaryFresh, v->n_flags, v->stream));   // ... and every weight is the count 0
+    if (v->geo.n_flags) {  // every TSDF value is 1: every segment flag is set
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)v->d_flags, (int)tsdf_host::kSummaryFresh, v->geo.n_flags, v->stream));   // ... and every weight is the count 0
         v->flags_known_zero = false;
         v->runs_maybe_set = true;
     }
@@ -1223,21 +1186,24 @@ int tsdf_config_default(tsdf_config *cfg, int32_t im_height, int32_t im_width)
 // What tsdf_create refuses in a configuration before it looks for a device (also behind tsdf_extent_regrid: host arithmetic only).
 static int config_ok(const tsdf_config *cfg)
 {
-    if (cfg->dim_x <= 0 || cfg->dim_y <= 0 || cfg->dim_z <= 0)
-        return fail(TSDF_ERR_INVALID, "tsdf_create: grid dims must be positive (%d,%d,%d)",
-                    cfg->dim_x, cfg->dim_y, cfg->dim_z);
-    if (cfg->z_begin < 0 || cfg->z_end < cfg->z_begin || cfg->z_end > cfg->dim_z)
-        return fail(TSDF_ERR_INVALID, "tsdf_create: slab [%d,%d) outside grid z range [0,%d)",
-                    cfg->z_begin, cfg->z_end, cfg->dim_z);
-    if (cfg->im_height <= 0 || cfg->im_width <= 0 ||
-        (int64_t)cfg->im_height * cfg->im_width > (int64_t)1 << 30)
-        return fail(TSDF_ERR_INVALID, "tsdf_create: bad image size %dx%d", cfg->im_height, cfg->im_width);
-    if (!(cfg->voxel_size > 0.0f) || !(cfg->trunc_margin > 0.0f))
-        return fail(TSDF_ERR_INVALID, "tsdf_create: voxel_size and trunc_margin must be > 0");
-    if (cfg->dim_y > 65535 * 4 || (cfg->z_end - cfg->z_begin) > 65535)
-        return fail(TSDF_ERR_INVALID, "tsdf_create: slab exceeds launch limits (dim_y <= 262140, slices <= 65535)");
-    if ((int64_t)cfg->dim_x * cfg->dim_y > ((int64_t)1 << 31) - 1024)
-        return fail(TSDF_ERR_INVALID, "tsdf_create: a slice may hold at most 2^31 voxels (dim_x * dim_y)");
+    using tsdf_host::ConfigLimit;
+    switch (tsdf_host::config_limits_ok(*cfg)) {
+        case ConfigLimit::Ok: break;
+        case ConfigLimit::GridDims:
+            return fail(TSDF_ERR_INVALID, "tsdf_create: grid dims must be positive (%d,%d,%d)",
+                        cfg->dim_x, cfg->dim_y, cfg->dim_z);
+        case ConfigLimit::SlabRange:
+            return fail(TSDF_ERR_INVALID, "tsdf_create: slab [%d,%d) outside grid z range [0,%d)",
+                        cfg->z_begin, cfg->z_end, cfg->dim_z);
+        case ConfigLimit::ImageSize:
+            return fail(TSDF_ERR_INVALID, "tsdf_create: bad image size %dx%d", cfg->im_height, cfg->im_width);
+        case ConfigLimit::VoxelAndTrunc:
+            return fail(TSDF_ERR_INVALID, "tsdf_create: voxel_size and trunc_margin must be > 0");
+        case ConfigLimit::LaunchLimits:
+            return fail(TSDF_ERR_INVALID, "tsdf_create: slab exceeds launch limits (dim_y <= 262140, slices <= 65535)");
+        case ConfigLimit::SliceVoxels:
+            return fail(TSDF_ERR_INVALID, "tsdf_create: a slice may hold at most 2^31 voxels (dim_x * dim_y)");
+    }
     return TSDF_OK;
 }
 
@@ -1257,7 +1223,13 @@ static int create_volume(const tsdf_config *cfg, bool batch_member, tsdf_volume 
     tsdf_volume *v = new (std::nothrow) tsdf_volume();
     if (!v) return fail(TSDF_ERR_INVALID, "tsdf_create: out of host memory");
     v->cfg = *cfg;
-    v->n_vox = (int64_t)cfg->dim_x * cfg->dim_y * (cfg->z_end - cfg->z_begin);
+    // geometry: the depth tiles (tsdf_host::tile_edge, fine_tables), then the wavefront brick with the views that follow from it
+    v->geo.tile = tsdf_host::tile_edge(*cfg, batch_member);
+    v->geo.fine = tsdf_host::fine_tables(*cfg, v->geo.tile);
+#ifdef TSDF_EXPERIMENTS
+    if (const char *e = std::getenv("TSDF_FINE_TILES")) v->geo.fine = v->geo.tile == 8 && std::atoi(e) != 0;   // A/B knob of the measurement build
+#endif
+    choose_brick(v);
     // ref: src/tsdf.cu:74 -- the inverse stays zero when base2world is singular, silently
     tsdf_host::invert_matrix(cfg->base2world, v->base2world_inv);
 
@@ -1269,28 +1241,19 @@ static int create_volume(const tsdf_config *cfg, bool batch_member, tsdf_volume 
     if ((e = stream_create(v->own_stream)) != hipSuccess)
         return cleanup(fail(TSDF_ERR_HIP, "tsdf_create: hipStreamCreate: %s", hipGetErrorString(e)));
     v->stream = v->own_stream;
-    size_t bytes = (size_t)(v->n_vox > 0 ? v->n_vox : 1) * sizeof(float);
+    size_t bytes = (size_t)(v->geo.n_vox > 0 ? v->geo.n_vox : 1) * sizeof(float);
     if ((e = dev_alloc(v->d_tsdf, bytes)) != hipSuccess ||
         (e = dev_alloc(v->d_weight, bytes)) != hipSuccess)
         return cleanup(fail(TSDF_ERR_HIP, "tsdf_create: hipMalloc of %zu bytes x2: %s", bytes, hipGetErrorString(e)));
-    v->flat = cfg->dim_x % 256 != 0;
-    v->nseg = v->flat ? 0 : cfg->dim_x / 256;
-    v->chunks_per_slice = (int)(((int64_t)cfg->dim_x * cfg->dim_y + 255) / 256);
-    choose_brick(v);
-    v->n_flags = cfg->dim_x % 4 == 0 ? (size_t)v->chunks_per_slice * (size_t)(cfg->z_end - cfg->z_begin) : 0;
-    if ((e = dev_alloc(v->d_flags, (v->n_flags ? v->n_flags : 1) * sizeof(uint32_t))) != hipSuccess)
+    if ((e = dev_alloc(v->d_flags, (v->geo.n_flags ? v->geo.n_flags : 1) * sizeof(uint32_t))) != hipSuccess)
         return cleanup(fail(TSDF_ERR_HIP, "tsdf_create: hipMalloc of the summary: %s", hipGetErrorString(e)));
     // staging, deferral and tile-table memory: the store shared by every handle of this device and image size (nothing is
     // allocated until a frame arrives)
-    v->tile = tsdf_host::tile_edge(*cfg, batch_member);
-    v->fine_tables = tsdf_host::fine_tables(*cfg, v->tile);
     v->pipeline_ok = tsdf_host::pipelines(*cfg);
 #ifdef TSDF_EXPERIMENTS
-    // A/B knobs of the measurement build
-    if (const char *e = std::getenv("TSDF_FINE_TILES")) v->fine_tables = v->tile == 8 && std::atoi(e) != 0;
-    if (const char *e = std::getenv("TSDF_PIPELINE")) v->pipeline_ok = std::atoi(e) != 0;
+    if (const char *e = std::getenv("TSDF_PIPELINE")) v->pipeline_ok = std::atoi(e) != 0;   // A/B knob of the measurement build
 #endif
-    const size_t table_bytes = tsdf_host::launch_table_bytes(*cfg, v->tile, v->fine_tables);
+    const size_t table_bytes = tsdf_host::launch_table_bytes(*cfg, v->geo.tile, v->geo.fine);
     if ((e = tsdf_store::store_ref(cfg->device, (size_t)cfg->im_height * cfg->im_width, table_bytes, &v->store)) != hipSuccess ||
         (e = event_create(v->flush_done[0])) != hipSuccess ||
         (e = event_create(v->flush_done[1])) != hipSuccess ||
@@ -1446,7 +1409,7 @@ int tsdf_download(tsdf_volume *v, float *tsdf_host, float *weight_host)
     if (!v) return fail(TSDF_ERR_INVALID, "tsdf_download: NULL handle");
     int rc = bind_device(v);
     if (rc) return rc;
-    size_t bytes = (size_t)v->n_vox * sizeof(float);
+    size_t bytes = (size_t)v->geo.n_vox * sizeof(float);
     HIP_TRY(hipStreamSynchronize(v->stream));
     if (bytes == 0) return TSDF_OK;
     if (tsdf_host) HIP_TRY(hipMemcpy(tsdf_host, v->d_tsdf, bytes, hipMemcpyDeviceToHost));
@@ -1476,7 +1439,7 @@ int tsdf_upload(tsdf_volume *v, const float *tsdf_host, const float *weight_host
     if (!v) return fail(TSDF_ERR_INVALID, "tsdf_upload: NULL handle");
     int rc = bind_device(v);
     if (rc) return rc;
-    size_t bytes = (size_t)v->n_vox * sizeof(float);
+    size_t bytes = (size_t)v->geo.n_vox * sizeof(float);
     HIP_TRY(hipStreamSynchronize(v->stream));
     if (bytes == 0) return TSDF_OK;
     if (tsdf_host) HIP_TRY(hipMemcpy(v->d_tsdf, tsdf_host, bytes, hipMemcpyHostToDevice));
@@ -1502,7 +1465,7 @@ int tsdf_device_ptrs(tsdf_volume *v, float **tsdf_dev, float **weight_dev)
     return TSDF_OK;
 }
 
-int64_t tsdf_slab_voxels(const tsdf_volume *v) { return v ? v->n_vox : 0; }
+int64_t tsdf_slab_voxels(const tsdf_volume *v) { return v ? v->geo.n_vox : 0; }
 
 int tsdf_get_config(const tsdf_volume *v, tsdf_config *out)
 {
@@ -1557,11 +1520,11 @@ int tsdf_object_origin(int32_t device, const float *depth_dev, const uint8_t *ma
 int tsdf_labels_enable(tsdf_volume *v, float prob_threshold)
 {
     if (!v) return fail(TSDF_ERR_INVALID, "tsdf_labels_enable: NULL handle");
-    if (v->cfg.dim_x % 4 != 0) return fail(TSDF_ERR_INVALID, "tsdf_labels_enable: dim_x must be a multiple of 4");
+    if (!v->geo.quad_rows) return fail(TSDF_ERR_INVALID, "tsdf_labels_enable: dim_x must be a multiple of 4");
     int rc = bind_device(v);
     if (rc) return rc;
     v->prob_thd = prob_threshold;
-    const size_t n = (size_t)(v->n_vox > 0 ? v->n_vox : 1);
+    const size_t n = (size_t)(v->geo.n_vox > 0 ? v->geo.n_vox : 1);
     if (!v->d_label) {      // all three or none: the other entry points test d_label alone
         DevPtr<uint16_t> label;
         DevPtr<float> fp, bp;
@@ -1584,16 +1547,14 @@ int tsdf_integrate_labels_device(tsdf_volume *v, const float *depth_dev, const u
     if (!v->d_label) return fail(TSDF_ERR_INVALID, "tsdf_integrate_labels_device: call tsdf_labels_enable first");
     int rc = bind_device(v);
     if (rc) return rc;
-    const int nz = v->cfg.z_end - v->cfg.z_begin;
-    if (nz == 0) return TSDF_OK;
+    if (v->geo.nz == 0) return TSDF_OK;
     float c2b[16];
     compose_cam2base(v, cam2world, c2b);
     tsdfk::LabelParams lp;
     lp.g = make_params(v, depth_dev, nullptr, c2b, 4);
     lp.label_im = label_im_dev; lp.score_im = score_im_dev;
     lp.label = v->d_label; lp.fp = v->d_fp; lp.bp = v->d_bp; lp.prob_thd = v->prob_thd;
-    dim3 block(64, 4, 1), grid((lp.g.xgroups + 63) / 64, (v->cfg.dim_y + 3) / 4, nz);
-    hipLaunchKernelGGL(tsdfk::integrate_labels, grid, block, 0, v->stream, lp);
+    hipLaunchKernelGGL(tsdfk::integrate_labels, to_dim3(tsdf_host::grid_quad_rows(v->geo, 4)), dim3(64, 4, 1), 0, v->stream, lp);
     HIP_TRY(hipGetLastError());
     return TSDF_OK;
 }
@@ -1605,7 +1566,7 @@ int tsdf_download_labels(tsdf_volume *v, uint16_t *label_host, float *fp_host, f
     int rc = bind_device(v);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(v->stream));
-    const size_t n = (size_t)v->n_vox;
+    const size_t n = (size_t)v->geo.n_vox;
     if (n == 0) return TSDF_OK;
     if (label_host) HIP_TRY(hipMemcpy(label_host, v->d_label, n * sizeof(uint16_t), hipMemcpyDeviceToHost));
     if (fp_host) HIP_TRY(hipMemcpy(fp_host, v->d_fp, n * sizeof(float), hipMemcpyDeviceToHost));
@@ -1636,10 +1597,10 @@ int tsdf_compose_labels(tsdf_volume *v, const uint8_t *masks_dev, const uint16_t
 int tsdf_colour_enable(tsdf_volume *v)
 {
     if (!v) return fail(TSDF_ERR_INVALID, "tsdf_colour_enable: NULL handle");
-    if (v->cfg.dim_x % 4 != 0) return fail(TSDF_ERR_INVALID, "tsdf_colour_enable: dim_x must be a multiple of 4");
+    if (!v->geo.quad_rows) return fail(TSDF_ERR_INVALID, "tsdf_colour_enable: dim_x must be a multiple of 4");
     int rc = bind_device(v);
     if (rc) return rc;
-    const size_t n = (size_t)(v->n_vox > 0 ? v->n_vox : 1);
+    const size_t n = (size_t)(v->geo.n_vox > 0 ? v->geo.n_vox : 1);
     if (!v->d_colour) HIP_TRY(dev_alloc(v->d_colour, n * sizeof(uint32_t)));
     HIP_TRY(hipMemsetAsync(v->d_colour, 0, n * sizeof(uint32_t), v->stream));
     return TSDF_OK;
@@ -1690,7 +1651,7 @@ int tsdf_download_colour(tsdf_volume *v, uint32_t *colour_host)
     int rc = bind_device(v);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(v->stream));
-    if (v->n_vox > 0) HIP_TRY(hipMemcpy(colour_host, v->d_colour, (size_t)v->n_vox * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (v->geo.n_vox > 0) HIP_TRY(hipMemcpy(colour_host, v->d_colour, (size_t)v->geo.n_vox * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return TSDF_OK;
 }
 
@@ -1840,7 +1801,7 @@ int tsdf_batch_create(const tsdf_config *cfgs, int32_t n, tsdf_batch **out)
         b->vols.push_back(v);
         const int nz = cfgs[i].z_end - cfgs[i].z_begin;
         for (int z = 0; z < nz; ++z) map.push_back(make_int2(i, z));
-        b->max_blocks = std::max(b->max_blocks, (v->chunks_per_slice + 3) / 4);
+        b->max_blocks = std::max(b->max_blocks, (int)tsdf_host::grid_flat(v->geo).x);
     }
     b->total_slices = (int)map.size();
     if (b->total_slices > 65535) return cleanup(fail(TSDF_ERR_INVALID, "tsdf_batch_create: %d slices in total exceed the launch limit 65535", b->total_slices));
@@ -1897,7 +1858,7 @@ int tsdf_batch_integrate_device(tsdf_batch *b, const float *depth_dev, const uin
     {
         bool defer = b->vols[0]->defer_n > 1;
         int64_t total = 0;
-        for (tsdf_volume *v : b->vols) { defer = defer && can_fuse(v); total += v->n_vox; }
+        for (tsdf_volume *v : b->vols) { defer = defer && can_fuse(v); total += v->geo.n_vox; }
         defer = defer && tsdf_host::batch_defers(n, total);
         if (defer) return batch_collect(b, depth_dev, masks_dev, cam2world);
         int rc = batch_flush(b);   // the policy changed between calls (tsdf_set_deferral, a kernel variant)
@@ -1929,12 +1890,13 @@ int tsdf_batch_integrate_device(tsdf_batch *b, const float *depth_dev, const uin
     bool same_range = true;   // one tile table per object, but all made with one depth-range test
     for (int i = 1; i < n; ++i) same_range = same_range && b->vols[i]->cfg.max_depth == b->vols[0]->cfg.max_depth;
     int64_t launch_voxels = 0;
-    for (tsdf_volume *v : b->vols) launch_voxels += v->n_vox;
+    for (tsdf_volume *v : b->vols) launch_voxels += v->geo.n_vox;
     // ... when the launch is large enough, and not for many small volumes (tsdf_host::batch_classifies)
     const bool classify = any_mask && same_range && tsdf_host::batch_classifies(variant_of(b->vols[0]->variant).classify, n, launch_voxels) &&
                           tiles_fit(h_params[0].tiles_w, h_params[0].tiles_h);
     if (classify) {
-        const size_t per = tsdf_host::tile_table_elems(h_params[0].tiles_w, h_params[0].tiles_h);
+        // one coarse table per member, laid out as a launch's table slot lays out its frames' coarse ones
+        const size_t per = tsdf_host::table_slot_layout(b->vols[0]->cfg, b->vols[0]->geo.tile, false).coarse_elems;
         if (!b->d_tiles) {      // (and, in the measurement build, the class table beside them: both or neither)
             DevPtr<float2> tiles;
             DevPtr<uint8_t> wg_class;
@@ -1955,9 +1917,8 @@ int tsdf_batch_integrate_device(tsdf_batch *b, const float *depth_dev, const uin
     int brick_blocks = 0;
     bool bricks = classify && !(kExperiments && b->vols[0]->variant == 11);
     for (int i = 0; i < n && bricks; ++i) {
-        const tsdfk::IntegrateParams &q = h_params[i];
-        bricks = q.brick_q > 0;
-        brick_blocks = std::max(brick_blocks, (q.brick_groups * q.bricks_per_group + 3) / 4);
+        bricks = b->vols[i]->geo.brick_q > 0;
+        brick_blocks = std::max(brick_blocks, tsdf_host::brick_blocks(b->vols[i]->geo));
     }
     if (bricks) {
         // z index of the brick launches: slice groups (rebuilt when a member's brick depth changed: tsdf_set_brick_shape)
@@ -1967,20 +1928,19 @@ int tsdf_batch_integrate_device(tsdf_batch *b, const float *depth_dev, const uin
             std::vector<int2> gmap;
             b->group_s.assign((size_t)n, 1);
             for (int i = 0; i < n; ++i) {
-                const tsdfk::IntegrateParams &q = h_params[i];
-                b->group_s[i] = q.brick_s;
-                for (int g = 0; g < (q.nz + q.brick_s - 1) / q.brick_s; ++g) gmap.push_back(make_int2(i, g));
+                b->group_s[i] = b->vols[i]->geo.brick_s;
+                for (int g = 0; g < b->vols[i]->geo.nz_groups; ++g) gmap.push_back(make_int2(i, g));
             }
             HIP_TRY(hipStreamSynchronize(b->stream));
             HIP_TRY(dev_alloc(b->d_group_map, std::max<size_t>(gmap.size(), 1) * sizeof(int2)));
             HIP_TRY(hipMemcpy(b->d_group_map, gmap.data(), gmap.size() * sizeof(int2), hipMemcpyHostToDevice));
             b->total_groups = (int)gmap.size();
         }
-        const size_t n_bricks = (size_t)brick_blocks * b->total_groups * 4;
-        HIP_TRY(b->d_brick_class.ensure(n_bricks));
-        hipLaunchKernelGGL(tsdfk::classify_bricks_batched, dim3((unsigned)((n_bricks + 255) / 256)), dim3(256), 0, b->stream,
+        const tsdf_host::BrickGrid bg = tsdf_host::brick_grid(brick_blocks, b->total_groups);   // the widest member's blocks x all slice groups
+        HIP_TRY(b->d_brick_class.ensure(bg.class_elems));
+        hipLaunchKernelGGL(tsdfk::classify_bricks_batched, dim3((unsigned)((bg.class_elems + 255) / 256)), dim3(256), 0, b->stream,
                            d_params, d_poses, b->d_group_map, b->d_brick_class, brick_blocks, b->total_groups);
-        hipLaunchKernelGGL((tsdfk::integrate_multi_batched_bricks<kBrickNT>), dim3(brick_blocks, 1, b->total_groups), block, 0, b->stream,
+        hipLaunchKernelGGL((tsdfk::integrate_multi_batched_bricks<kBrickNT>), to_dim3(bg.grid), block, 0, b->stream,
                            d_params, d_poses, b->d_group_map, b->d_brick_class);
 #ifdef TSDF_EXPERIMENTS
     } else if (classify) {   // variant 11: a class per 1024-voxel workgroup patch (round 2a's shape)

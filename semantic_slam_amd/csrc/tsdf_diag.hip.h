@@ -113,8 +113,8 @@ int tsdf_probe_stream(tsdf_volume *v, int32_t non_temporal, int32_t n_iters, flo
     if (!v || n_iters <= 0 || !elapsed_ms) return fail(TSDF_ERR_INVALID, "tsdf_probe_stream: bad argument");
     int rc = bind_device(v);
     if (rc) return rc;
-    if (v->n_vox % 4 != 0 || v->n_vox == 0) return fail(TSDF_ERR_INVALID, "tsdf_probe_stream: slab voxels must be a positive multiple of 4");
-    const size_t nq = (size_t)v->n_vox / 4;
+    if (v->geo.n_vox % 4 != 0 || v->geo.n_vox == 0) return fail(TSDF_ERR_INVALID, "tsdf_probe_stream: slab voxels must be a positive multiple of 4");
+    const size_t nq = (size_t)v->geo.n_vox / 4;
     const int blocks = (int)std::min<size_t>((nq + 255) / 256, (size_t)256 * 8);
     return time_on_stream(v, "tsdf_probe_stream", elapsed_ms, [&]() -> int {
         for (int i = 0; i < n_iters; ++i) {
@@ -199,7 +199,7 @@ int tsdf_selftest_tile_tables(int32_t device, const float *depth_dev, const uint
     HIP_TRY(hipSetDevice(device));
     uint64_t bad = 0;
     for (const int tile : {16, 8}) {      // both tile sizes the library uses (tsdf_host::tile_edge)
-        const int tw = (im_width + tile - 1) / tile, th = (im_height + tile - 1) / tile;
+        const int tw = tsdf_host::tiles_along(im_width, tile), th = tsdf_host::tiles_along(im_height, tile);
         if (!tiles_fit(tw, th)) continue;
         const size_t per = tsdf_host::tile_table_elems(tw, th);
         DevPtr<float2> d_a, d_b;
@@ -214,9 +214,9 @@ int tsdf_selftest_tile_tables(int32_t device, const float *depth_dev, const uint
         // a: the kernels the library launches (strips of 64 pixels; doubling in LDS when the frame's tiles fit)
         tp.tiles = d_a;
         if (tile == 16)
-            hipLaunchKernelGGL(tsdfk::depth_tile_summary<16>, dim3((unsigned)((((tw + 3) / 4) * th + 3) / 4), 1), dim3(64, 4), 0, 0, tp);
+            hipLaunchKernelGGL(tsdfk::depth_tile_summary<16>, to_dim3(tsdf_host::grid_tile_strips(tw, th, 16, 1)), dim3(64, 4), 0, 0, tp);
         else
-            hipLaunchKernelGGL(tsdfk::depth_tile_summary<8>, dim3((unsigned)((((tw + 7) / 8) * th + 3) / 4), 1), dim3(64, 4), 0, 0, tp);
+            hipLaunchKernelGGL(tsdfk::depth_tile_summary<8>, to_dim3(tsdf_host::grid_tile_strips(tw, th, 8, 1)), dim3(64, 4), 0, 0, tp);
         if (tw * th <= tsdfk::kTileLdsEntries)
             hipLaunchKernelGGL(tsdfk::tile_sparse_table, dim3(lj, 1), dim3(tw * th > 2048 ? 1024 : 256), 0, 0, d_a, tw, th, (unsigned long long *)nullptr);
         else
@@ -237,7 +237,7 @@ int tsdf_selftest_tile_tables(int32_t device, const float *depth_dev, const uint
         for (size_t i = 0; i < per; ++i) bad += std::memcmp(&a[i], &b[i], sizeof(float2)) != 0;
     }
     {   // the fine table (4-pixel tiles, nine levels): the two kernels the library launches against the pixel-by-pixel one
-        const int fw = (im_width + tsdfk::kFineTile - 1) / tsdfk::kFineTile, fh = (im_height + tsdfk::kFineTile - 1) / tsdfk::kFineTile;
+        const int fw = tsdf_host::tiles_along(im_width, tsdfk::kFineTile), fh = tsdf_host::tiles_along(im_height, tsdfk::kFineTile);
         const size_t per = tsdfk::fine_table_elems(fw, fh);
         DevPtr<float2> d_a, d_b;
         HIP_TRY(dev_alloc(d_a, per * sizeof(float2)));
@@ -263,7 +263,7 @@ int tsdf_selftest_tile_tables(int32_t device, const float *depth_dev, const uint
                 hipLaunchKernelGGL(tsdfk::fine_tile_base, dim3((unsigned)((fw + 63) / 64), (unsigned)fh, 1), dim3(64), 0, 0, fp);
                 hipLaunchKernelGGL(tsdfk::fine_tile_levels, dim3((unsigned)((fw * fh + 255) / 256), 1), dim3(256), 0, 0, d_a, fw, fh);
             } else {
-                const int tw = (im_width + 7) / 8, th = (im_height + 7) / 8;
+                const int tw = tsdf_host::tiles_along(im_width, 8), th = tsdf_host::tiles_along(im_height, 8);
                 if ((int64_t)tw * th > tsdfk::kTileLdsEntries) break;
                 DevPtr<float2> d_c;
                 if (dev_alloc(d_c, tsdf_host::tile_table_elems(tw, th) * sizeof(float2)) != hipSuccess) { e = hipErrorOutOfMemory; break; }
@@ -271,7 +271,7 @@ int tsdf_selftest_tile_tables(int32_t device, const float *depth_dev, const uint
                 for (int f = 0; f < tsdfk::kMaxFramesPerLaunch; ++f) { tp.depth[f] = depth_dev; tp.mask[f] = mask_dev; }
                 tp.H = im_height; tp.W = im_width; tp.tiles_w = tw; tp.tiles_h = th; tp.max_depth = max_depth;
                 tp.tiles = d_c; tp.fine = d_a; tp.fw = fw; tp.fh = fh;
-                hipLaunchKernelGGL(tsdfk::depth_tile_summary<8>, dim3((unsigned)((((tw + 7) / 8) * th + 3) / 4), 1), dim3(64, 4), 0, 0, tp);
+                hipLaunchKernelGGL(tsdfk::depth_tile_summary<8>, to_dim3(tsdf_host::grid_tile_strips(tw, th, 8, 1)), dim3(64, 4), 0, 0, tp);
                 const unsigned threads = tw * th > 2048 ? 1024 : 256;
                 hipLaunchKernelGGL(tsdfk::tile_sparse_table, dim3((unsigned)tsdf_host::tile_levels(tw) + ((unsigned)(fw * fh) + threads - 1) / threads, 1), dim3(threads), 0, 0,
                                    d_c, tw, th, (unsigned long long *)nullptr, d_a, fw, fh);
@@ -351,17 +351,17 @@ int tsdf_summary_stats(tsdf_volume *v, uint64_t out[3])
     int rc = bind_device(v);
     if (rc) return rc;
     out[0] = out[1] = out[2] = 0;
-    if (v->n_flags == 0) { HIP_TRY(hipStreamSynchronize(v->stream)); return TSDF_OK; }
+    if (v->geo.n_flags == 0) { HIP_TRY(hipStreamSynchronize(v->stream)); return TSDF_OK; }
     DevPtr<unsigned long long> d;
     HIP_TRY(dev_alloc(d, 3 * sizeof(unsigned long long)));
     HIP_TRY(hipMemsetAsync(d, 0, 3 * sizeof(unsigned long long), v->stream));
-    const unsigned blocks = (unsigned)std::min<size_t>((v->n_flags + 255) / 256, (size_t)256 * 8);
-    hipLaunchKernelGGL(tsdfk::summary_stats, dim3(blocks), dim3(256), 0, v->stream, (const uint32_t *)v->d_flags.get(), v->n_flags, d.get());
+    hipLaunchKernelGGL(tsdfk::summary_stats, to_dim3(tsdf_host::grid_summary_words(v->geo)), dim3(256), 0, v->stream, (const uint32_t *)v->d_flags.get(),
+                       v->geo.n_flags, d.get());
     HIP_TRY(hipGetLastError());
     unsigned long long h[3] = {0, 0, 0};
     HIP_TRY(hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, v->stream));
     HIP_TRY(hipStreamSynchronize(v->stream));
-    out[0] = v->n_flags; out[1] = h[1]; out[2] = h[2];
+    out[0] = v->geo.n_flags; out[1] = h[1]; out[2] = h[2];
     return TSDF_OK;
 }
 
@@ -370,9 +370,9 @@ int tsdf_summary_words(tsdf_volume *v, uint32_t *out_host, int64_t capacity, int
     if (!v || !count || capacity < 0 || (capacity > 0 && !out_host)) return fail(TSDF_ERR_INVALID, "tsdf_summary_words: bad argument");
     int rc = bind_device(v);
     if (rc) return rc;
-    *count = (int64_t)v->n_flags;
-    if (v->n_flags > 0 && capacity >= (int64_t)v->n_flags)
-        HIP_TRY(hipMemcpyAsync(out_host, v->d_flags.get(), v->n_flags * sizeof(uint32_t), hipMemcpyDeviceToHost, v->stream));
+    *count = (int64_t)v->geo.n_flags;
+    if (v->geo.n_flags > 0 && capacity >= (int64_t)v->geo.n_flags)
+        HIP_TRY(hipMemcpyAsync(out_host, v->d_flags.get(), v->geo.n_flags * sizeof(uint32_t), hipMemcpyDeviceToHost, v->stream));
     HIP_TRY(hipStreamSynchronize(v->stream));
     return TSDF_OK;
 }
@@ -411,14 +411,14 @@ int tsdf_set_brick_shape(tsdf_volume *v, int32_t quads, int32_t rows, int32_t sl
     if (!brick_shape_ok(v->cfg, quads, rows, slices))
         return fail(TSDF_ERR_INVALID, "tsdf_set_brick_shape: %d quads x %d rows x %d slices: needs quads * rows * slices <= 64 and "
                     "quads dividing dim_x / 4 = %d", quads, rows, slices, v->cfg.dim_x / 4);
-    v->brick_q = quads; v->brick_r = rows; v->brick_s = slices;
+    set_brick(v, quads, rows, slices);
     return TSDF_OK;
 }
 
 int tsdf_brick_shape(const tsdf_volume *v, int32_t shape_out[3])
 {
     if (!v || !shape_out) return fail(TSDF_ERR_INVALID, "tsdf_brick_shape: NULL argument");
-    shape_out[0] = v->brick_q; shape_out[1] = v->brick_q ? v->brick_r : 0; shape_out[2] = v->brick_q ? v->brick_s : 0;
+    shape_out[0] = v->geo.brick_q; shape_out[1] = v->geo.brick_q ? v->geo.brick_r : 0; shape_out[2] = v->geo.brick_q ? v->geo.brick_s : 0;
     return TSDF_OK;
 }
 

@@ -45,9 +45,8 @@ void experiment_adjust(const tsdf_volume *v, bool labels, bool *classify, int *z
 template <int R, bool ELIDE, bool NT, bool MASKED, bool SUM, bool EARLY = false, bool FAST = false>
 void launch_ladder(const tsdf_volume *v, const tsdfk::IntegrateParams &p)
 {
-    dim3 block(64, 4, 1);
-    dim3 grid((p.xgroups + 63) / 64, (p.dim_y + 4 * R - 1) / (4 * R), p.nz);
-    hipLaunchKernelGGL((tsdfk::ladder_tile<R, ELIDE, NT, MASKED, SUM, EARLY, FAST>), grid, block, 0, v->stream, p);
+    hipLaunchKernelGGL((tsdfk::ladder_tile<R, ELIDE, NT, MASKED, SUM, EARLY, FAST>), to_dim3(tsdf_host::grid_quad_rows(v->geo, 4 * R)), dim3(64, 4, 1), 0,
+                       v->stream, p);
 }
 
 // One masked frame into one volume: tile table of depth x mask, then the class of every workgroup of the coming launch
@@ -78,16 +77,14 @@ int classify_single(tsdf_volume *v, StoreSlot &table, tsdfk::IntegrateParams &p,
 // One-frame launches of the ladder (variants 2, 16 .. 119, unmasked) and variant 11's masked one-frame launch.
 int launch_integrate_experiment(tsdf_volume *v, const float *depth_dev, const uint8_t *mask_dev, const float *c2b)
 {
-    const tsdf_config &c = v->cfg;
-    const int nz = c.z_end - c.z_begin;
     const int variant = v->variant;
-    if (v->flat && variant != 2) return launch_multi(v, &depth_dev, mask_dev ? &mask_dev : nullptr, c2b, 1);   // the flat mapping serves them all
+    if (v->geo.flat && variant != 2) return launch_multi(v, &depth_dev, mask_dev ? &mask_dev : nullptr, c2b, 1);   // the flat mapping serves them all
     tsdfk::IntegrateParams p = make_params(v, depth_dev, mask_dev, c2b, 4);
     if (variant == 11) {   // masked, row-mapped, classified per workgroup (256 x 8 voxels)
         v->flags_known_zero = false;
         int rcf = forget_weight_runs(v);
         if (rcf) return rcf;
-        const dim3 grid((p.xgroups + 63) / 64, (p.dim_y + 7) / 8, p.nz);
+        const dim3 grid = to_dim3(tsdf_host::grid_quad_rows(v->geo, 8));
         StoreSlot table;
         int rc = classify_single(v, table, p, (int)grid.x, (int)grid.y, (int)grid.z, 8);
         if (rc) return rc;
@@ -106,7 +103,7 @@ int launch_integrate_experiment(tsdf_volume *v, const float *depth_dev, const ui
         if (rc) return rc;
     }
     if (variant == 2) {
-        dim3 block(64, 4, 1), grid((p.xgroups + 63) / 64, (c.dim_y + 3) / 4, nz);
+        const dim3 block(64, 4, 1), grid = to_dim3(tsdf_host::grid_quad_rows(v->geo, 4));
         if (mask_dev) hipLaunchKernelGGL((tsdfk::ladder_rows<4, true>), grid, block, 0, v->stream, p);
         else hipLaunchKernelGGL((tsdfk::ladder_rows<4, false>), grid, block, 0, v->stream, p);
     } else if (variant >= 32) {
@@ -121,9 +118,9 @@ int launch_integrate_experiment(tsdf_volume *v, const float *depth_dev, const ui
             FAST_CASE(64 + 10, 4, false, false) FAST_CASE(64 + 11, 4, true, false)
 #undef FAST_CASE
             case 80 + 3: hipLaunchKernelGGL((tsdfk::ladder_tile<1, true, true, false, true, false, true, true>),
-                                            dim3((p.xgroups + 63) / 64, (p.dim_y + 3) / 4, p.nz), dim3(64, 4, 1), 0, v->stream, p); break;
+                                            to_dim3(tsdf_host::grid_quad_rows(v->geo, 4)), dim3(64, 4, 1), 0, v->stream, p); break;
             case 80 + 7: hipLaunchKernelGGL((tsdfk::ladder_tile<2, true, true, false, true, false, true, true>),
-                                            dim3((p.xgroups + 63) / 64, (p.dim_y + 7) / 8, p.nz), dim3(64, 4, 1), 0, v->stream, p); break;
+                                            to_dim3(tsdf_host::grid_quad_rows(v->geo, 8)), dim3(64, 4, 1), 0, v->stream, p); break;
             SUM_CASE(2, 1, false, true, false) SUM_CASE(3, 1, true, true, false)
             SUM_CASE(6, 2, false, true, false) SUM_CASE(7, 2, true, true, false)
             SUM_CASE(10, 4, false, true, false) SUM_CASE(11, 4, true, true, false)
@@ -158,14 +155,13 @@ int launch_single_experiment(tsdf_volume *v, tsdfk::IntegrateParams &common, tsd
                              const float *c2b, bool *handled)
 {
     *handled = false;
-    if (!(v->variant == 11 && v->flat && pose.mask != nullptr && tsdf_host::classify_one_frame(variant_of(v->variant).classify, v->n_vox) &&
+    if (!(v->variant == 11 && v->geo.flat && pose.mask != nullptr && tsdf_host::classify_one_frame(variant_of(v->variant).classify, v->geo.n_vox) &&
           tiles_fit(common.tiles_w, common.tiles_h)))
         return TSDF_OK;
-    const int nz = v->cfg.z_end - v->cfg.z_begin;
-    dim3 block(64, 4, 1), grid((v->chunks_per_slice + 3) / 4, 1, nz);
+    const dim3 block(64, 4, 1), grid = to_dim3(tsdf_host::grid_flat(v->geo));
     tsdfk::IntegrateParams cp = make_params(v, depth_dev, pose.mask, c2b, 4);
     StoreSlot table;
-    int rc = classify_single(v, table, cp, (int)grid.x, 1, nz, 0);
+    int rc = classify_single(v, table, cp, (int)grid.x, 1, (int)grid.z, 0);
     if (rc) return rc;
     common.wg_class = cp.wg_class;
     hipLaunchKernelGGL((tsdfk::integrate_multi_single_cls<true, true, true>), grid, block, 0, v->stream, common, pose);
@@ -188,8 +184,7 @@ int launch_multi_experiment(tsdf_volume *v, tsdfk::MultiParamsInline &mi, const 
 {
     *handled = false;
     if (!experiment_takes_multi(v, labels, classify)) return TSDF_OK;
-    const tsdf_config &c = v->cfg;
-    const int nz = c.z_end - c.z_begin;
+    const tsdf_host::SlabGeometry &geo = v->geo;
     const dim3 block(64, 4, 1);
     mi.super_mask = nullptr;
     mi.nz_super = 1;
@@ -205,42 +200,37 @@ int launch_multi_experiment(tsdf_volume *v, tsdfk::MultiParamsInline &mi, const 
         mp.n_frames = n;
         for (int f = 0; f < n; ++f) { s->host[f] = mi.frames[f]; s->host[f].tiles = nullptr; }
         HIP_TRY(hipMemcpyAsync(s->dev, s->host, n * sizeof(tsdfk::FramePose), hipMemcpyHostToDevice, v->stream));
-        if (v->flat) {
-            dim3 grid((v->chunks_per_slice + 3) / 4, 1, nz);
-            hipLaunchKernelGGL((tsdfk::integrate_multi<1, true, true>), grid, block, 0, v->stream, mp);
-        } else if (v->variant == 5) {   // XCD-aware block order
-            dim3 grid((mp.common.xgroups + 63) / 64, (c.dim_y + 3) / 4, nz);
-            hipLaunchKernelGGL((tsdfk::integrate_multi_xcd<true>), grid, block, 0, v->stream, mp);
-        } else if (v->variant == 4) {   // two rows per lane
-            dim3 grid((mp.common.xgroups + 63) / 64, (c.dim_y + 7) / 8, nz);
-            hipLaunchKernelGGL((tsdfk::integrate_multi<2, true, false>), grid, block, 0, v->stream, mp);
-        } else {                        // variant 6: the default kernel with staged frame blocks (A/B of the kernarg path)
-            dim3 grid((mp.common.xgroups + 63) / 64, (c.dim_y + 3) / 4, nz);
-            hipLaunchKernelGGL((tsdfk::integrate_multi<1, true, false>), grid, block, 0, v->stream, mp);
-        }
+        if (geo.flat)
+            hipLaunchKernelGGL((tsdfk::integrate_multi<1, true, true>), to_dim3(tsdf_host::grid_flat(geo)), block, 0, v->stream, mp);
+        else if (v->variant == 5)     // XCD-aware block order
+            hipLaunchKernelGGL((tsdfk::integrate_multi_xcd<true>), to_dim3(tsdf_host::grid_quad_rows(geo, 4)), block, 0, v->stream, mp);
+        else if (v->variant == 4)     // two rows per lane
+            hipLaunchKernelGGL((tsdfk::integrate_multi<2, true, false>), to_dim3(tsdf_host::grid_quad_rows(geo, 8)), block, 0, v->stream, mp);
+        else                          // variant 6: the default kernel with staged frame blocks (A/B of the kernarg path)
+            hipLaunchKernelGGL((tsdfk::integrate_multi<1, true, false>), to_dim3(tsdf_host::grid_quad_rows(geo, 4)), block, 0, v->stream, mp);
         HIP_TRY(hipGetLastError());
         HIP_TRY(v->frames.consumed(s, v->stream));
         *handled = true;
         *claims_total = 0.0;
         return TSDF_OK;
     }
-    dim3 grid_flat((v->chunks_per_slice + 3) / 4, 1, nz), grid_rows((mi.common.xgroups + 63) / 64, (c.dim_y + 3) / 4, nz);
-    const int nz_groups = (nz + mi.common.brick_s - 1) / mi.common.brick_s;
+    const int nz_groups = geo.nz_groups;
     if (v->variant == 11) {   // rows / 1024 consecutive voxels, classified per workgroup in the prologue
-        if ((v->flat ? grid_flat.x : grid_rows.x) > 65535u) mi.z_fastest = 0;
-        if (mi.z_fastest) { std::swap(grid_flat.x, grid_flat.z); std::swap(grid_rows.x, grid_rows.z); }
-        if (v->flat && any_mask)
-            hipLaunchKernelGGL((tsdfk::integrate_multi_wg<1, true, true, false, true, true>), grid_flat, block, 0, v->stream, mi);
+        tsdf_host::Grid3 g = geo.flat ? tsdf_host::grid_flat(geo) : tsdf_host::grid_quad_rows(geo, 4);
+        if (g.x > 65535u) mi.z_fastest = 0;
+        if (mi.z_fastest) std::swap(g.x, g.z);
+        const dim3 grid = to_dim3(g);
+        if (geo.flat && any_mask)
+            hipLaunchKernelGGL((tsdfk::integrate_multi_wg<1, true, true, false, true, true>), grid, block, 0, v->stream, mi);
         else if (any_mask)
-            hipLaunchKernelGGL((tsdfk::integrate_multi_wg<1, true, false, false, true, true>), grid_rows, block, 0, v->stream, mi);
-        else if (v->flat)
-            hipLaunchKernelGGL((tsdfk::integrate_multi_wg<1, true, true, false, false, true>), grid_flat, block, 0, v->stream, mi);
+            hipLaunchKernelGGL((tsdfk::integrate_multi_wg<1, true, false, false, true, true>), grid, block, 0, v->stream, mi);
+        else if (geo.flat)
+            hipLaunchKernelGGL((tsdfk::integrate_multi_wg<1, true, true, false, false, true>), grid, block, 0, v->stream, mi);
         else
-            hipLaunchKernelGGL((tsdfk::integrate_multi_wg<1, true, false, false, false, true>), grid_rows, block, 0, v->stream, mi);
-        const dim3 &g = v->flat ? grid_flat : grid_rows;
+            hipLaunchKernelGGL((tsdfk::integrate_multi_wg<1, true, false, false, false, true>), grid, block, 0, v->stream, mi);
         *claims_total = (double)g.x * g.y * g.z * n;
     } else {                  // 12, 13: a workgroup per four bricks of the whole slab, each wavefront classifying its brick
-        const unsigned wgs = (unsigned)(((int64_t)mi.common.brick_groups * mi.common.bricks_per_group + 3) / 4);
+        const unsigned wgs = (unsigned)tsdf_host::brick_blocks(geo);
         if (wgs > 65535u) mi.z_fastest = 0;   // the slow grid dimensions hold 65535 at most
         const dim3 grid_bricks = mi.z_fastest ? dim3((unsigned)nz_groups, 1, wgs) : dim3(wgs, 1, (unsigned)nz_groups);
         if (v->variant == 13) {

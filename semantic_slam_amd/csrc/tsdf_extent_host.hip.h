@@ -24,9 +24,9 @@ int extent_volume_ok(const char *who, const tsdf_volume *v)
 {
     const tsdf_config &c = v->cfg;
     const unsigned __int128 m = (unsigned __int128)std::max(c.dim_x, std::max(c.dim_y, c.dim_z));
-    if ((unsigned __int128)v->n_vox * m * m >> 64)
+    if ((unsigned __int128)v->geo.n_vox * m * m >> 64)
         return fail(TSDF_ERR_INVALID, "%s: %lld voxels of a %dx%dx%d grid: the second moments could reach 2^64", who,
-                    (long long)v->n_vox, c.dim_x, c.dim_y, c.dim_z);
+                    (long long)v->geo.n_vox, c.dim_x, c.dim_y, c.dim_z);
     return TSDF_OK;
 }
 

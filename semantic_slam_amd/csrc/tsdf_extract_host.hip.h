@@ -104,11 +104,11 @@ int extract_pass(tsdf_volume *v, ListKind kind, const float *halo_tsdf, const fl
     int rc = bind_device(v);
     if (rc) return rc;
     *count = 0;
-    if (v->n_vox == 0) return TSDF_OK;
+    if (v->geo.n_vox == 0) return TSDF_OK;
     if (!surface && (halo_tsdf == nullptr) != (halo_weight == nullptr))
         return fail(TSDF_ERR_INVALID, "zero crossings: give both halo arrays or neither");
     const tsdf_config &c = v->cfg;
-    const int64_t n = v->n_vox;
+    const int64_t n = v->geo.n_vox;
     const int64_t n_chunks = (n + tsdfx::kChunk - 1) / tsdfx::kChunk;
     if (n_chunks > 0x7fffffff) return fail(TSDF_ERR_INVALID, "%s: slab too large", what);
     const size_t slice = (size_t)c.dim_x * c.dim_y;
@@ -132,7 +132,7 @@ int extract_pass(tsdf_volume *v, ListKind kind, const float *halo_tsdf, const fl
         }
         g.n = n; g.dim_x = c.dim_x; g.dim_y = c.dim_y; g.nz = c.z_end - c.z_begin; g.z_begin = c.z_begin;
         g.thr = weight_thresh; g.ox = c.origin[0]; g.oy = c.origin[1]; g.oz = c.origin[2]; g.vs = c.voxel_size;
-        g.flags = v->nseg > 0 ? v->d_flags : nullptr; g.nseg = v->nseg;     // segments that are all free / unseen space are skipped
+        g.flags = v->geo.nseg > 0 ? v->d_flags : nullptr; g.nseg = v->geo.nseg;     // segments that are all free / unseen space are skipped
     }
     const dim3 grid((unsigned)n_chunks), block(256);
     if (surface) hipLaunchKernelGGL(tsdfx::surface_count, grid, block, 0, v->stream, v->d_tsdf, v->d_weight, n, weight_thresh, d_counts);
@@ -185,7 +185,7 @@ int mesh_for_file(tsdf_volume *v, float weight_thresh, std::vector<float> &tri, 
         return extract_pass(v, kind, nullptr, nullptr, weight_thresh, ListDest::to_host(dst, capacity), count);
     }, ListKind::Mesh, tri, n, admit);
     if (rc || !v->d_colour) return rc;
-    colour.resize((size_t)(v->n_vox > 0 ? v->n_vox : 1));
+    colour.resize((size_t)(v->geo.n_vox > 0 ? v->geo.n_vox : 1));
     return tsdf_download_colour(v, colour.data());
 }
 
@@ -274,7 +274,7 @@ int tsdf_save_bin(tsdf_volume *v, const char *path)
     if (rc) return rc;
     mesh_files::OutFile f(path, "wb");
     mesh_files::write_bin_header(f, v->cfg);
-    if (f.good()) rc = stream_device_to_file(v, f.get(), v->d_tsdf, (size_t)v->n_vox * sizeof(float), who, path);
+    if (f.good()) rc = stream_device_to_file(v, f.get(), v->d_tsdf, (size_t)v->geo.n_vox * sizeof(float), who, path);
     return close_streamed(f, rc, who, path);
 }
 
@@ -290,10 +290,10 @@ int tsdf_load_bin(tsdf_volume *v, const char *path)
     {
         InFile f(path);
         if (!f.fp) return fail(TSDF_ERR_IO, "tsdf_load_bin: cannot open %s", path);
-        host.resize((size_t)(v->n_vox > 0 ? v->n_vox : 1));
+        host.resize((size_t)(v->geo.n_vox > 0 ? v->geo.n_vox : 1));
         float hdr[8];
         const bool ok = f.read(hdr, sizeof(float), 8) && hdr[0] == (float)c.dim_x && hdr[1] == (float)c.dim_y && hdr[2] == (float)nz &&
-                        f.read(host.data(), sizeof(float), (size_t)v->n_vox);
+                        f.read(host.data(), sizeof(float), (size_t)v->geo.n_vox);
         if (!ok) return fail(TSDF_ERR_IO, "tsdf_load_bin: %s is not a %dx%dx%d TSDF dump", path, c.dim_x, c.dim_y, nz);
     }
     return tsdf_upload(v, host.data(), nullptr);   // weights are not in the reference's format
@@ -308,8 +308,8 @@ int tsdf_save_state(tsdf_volume *v, const char *path)
     mesh_files::OutFile f(path, "wb");
     f.write(kStateMagic, 1, 8);
     f.write(&v->cfg, sizeof(tsdf_config), 1);
-    if (f.good()) rc = stream_device_to_file(v, f.get(), v->d_tsdf, (size_t)v->n_vox * sizeof(float), who, path);
-    if (f.good() && rc == TSDF_OK) rc = stream_device_to_file(v, f.get(), v->d_weight, (size_t)v->n_vox * sizeof(float), who, path);
+    if (f.good()) rc = stream_device_to_file(v, f.get(), v->d_tsdf, (size_t)v->geo.n_vox * sizeof(float), who, path);
+    if (f.good() && rc == TSDF_OK) rc = stream_device_to_file(v, f.get(), v->d_weight, (size_t)v->geo.n_vox * sizeof(float), who, path);
     return close_streamed(f, rc, who, path);
 }
 
@@ -320,14 +320,14 @@ int tsdf_load_state(tsdf_volume *v, const char *path)
     {
         InFile f(path);
         if (!f.fp) return fail(TSDF_ERR_IO, "tsdf_load_state: cannot open %s", path);
-        t.resize((size_t)(v->n_vox > 0 ? v->n_vox : 1));
+        t.resize((size_t)(v->geo.n_vox > 0 ? v->geo.n_vox : 1));
         w.resize(t.size());
         char magic[8];
         tsdf_config c;
         const bool ok = f.read(magic, 1, 8) && std::memcmp(magic, kStateMagic, 8) == 0 && f.read(&c, sizeof c, 1) &&
                         c.dim_x == v->cfg.dim_x && c.dim_y == v->cfg.dim_y && c.dim_z == v->cfg.dim_z &&
                         c.z_begin == v->cfg.z_begin && c.z_end == v->cfg.z_end &&
-                        f.read(t.data(), sizeof(float), (size_t)v->n_vox) && f.read(w.data(), sizeof(float), (size_t)v->n_vox);
+                        f.read(t.data(), sizeof(float), (size_t)v->geo.n_vox) && f.read(w.data(), sizeof(float), (size_t)v->geo.n_vox);
         if (!ok) return fail(TSDF_ERR_IO, "tsdf_load_state: %s does not hold the state of this slab", path);
     }
     return tsdf_upload(v, t.data(), w.data());

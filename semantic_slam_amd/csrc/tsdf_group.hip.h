@@ -427,7 +427,7 @@ int tsdf_group_save_bin(tsdf_group *g, const char *path)
     for (size_t i = 0; f.good() && rc == TSDF_OK && i < g->slabs.size(); ++i) {
         tsdf_volume *v = g->slabs[i];
         if ((rc = bind_device(v)) != TSDF_OK) break;
-        rc = stream_device_to_file(v, f.get(), v->d_tsdf, (size_t)v->n_vox * sizeof(float), who, path);
+        rc = stream_device_to_file(v, f.get(), v->d_tsdf, (size_t)v->geo.n_vox * sizeof(float), who, path);
     }
     return close_streamed(f, rc, who, path);
 }

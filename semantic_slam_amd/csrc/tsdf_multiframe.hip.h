@@ -13,6 +13,7 @@
 //   the quads; update in registers } -> store weights / changed TSDF rows / cleared flag.
 // The per-frame arithmetic is the FAST + ELIDE + SUM path of integrate_tile (same helpers).
 #pragma once
+#include "launch_geometry.h"
 #include "tsdf_kernels.hip.h"
 
 namespace tsdfk {
@@ -1240,33 +1241,7 @@ struct BrickListParams {
     int wedge_mode, wedge_oy, wedge_oz, super_h, super_d, fy_px;
 };
 
-// The sub-list (bucket) of super-brick `id` = (sx, sy, sz): workgroup j of integrate_brick_list takes its entries from sub-list
-// j % kListBuckets, and workgroups are dealt to the eight XCDs round robin by their index, so sub-list b is served by XCD b % 8.
-// wedge_mode 0 (what ships): a multiplicative hash of the index -- every sub-list, and with it every XCD, samples the whole
-// volume: the sub-lists run dry together, but every XCD's L2 ends up fetching every depth frame of the launch (32 x 1.2 MB; an
-// XCD has 4 MB).  wedge_mode 1 .. 3 (measurement build only, TSDF_WEDGE_MODE): the low three bits -- the XCD -- come from WHERE
-// the super-brick lies in the image: its centre's row under the base camera, in stripes of 16 (mode 3: 8) pixels dealt round
-// robin (a stripe is a wedge of the volume through the camera centre, so under any pose of the launch it projects onto a compact
-// part of the image); modes 2 and 3 rotate the stripe -> XCD map by three every four super-bricks along x, so that the image's top
-// and bottom rows -- where the bricks that straddle the border sit -- go round all XCDs.  Measured, round 4, same box, S-surf 512^3:
-// the Integrate kernel's measured traffic 908 -> 558 / 599 / 692 MB per launch (modes 1 / 2 / 3: the depth frames are no longer
-// fetched into all eight L2s) but 0.0256 -> 0.0305 / 0.0283 / 0.0276 ms per frame (4.5 - 5.0 resident wavefronts per SIMD instead
-// of 5.6: the XCDs' shares of the per-voxel work are no longer alike, and the launch is bound by instruction issue, not by
-// bytes); the fr3 trajectory 4.15 -> 3.82 GB, 0.1498 -> 0.1507.  Integer arithmetic only: the host counts the sub-lists'
-// capacities with the same function.
-__host__ __device__ inline unsigned int list_bucket(const unsigned int id, const int sx, const int sy, const int sz, const BrickListParams &bl)
-{
-    const unsigned int h = id * 2654435761u;
-    if (bl.wedge_mode == 0) return h >> 26;
-    const int yc = bl.wedge_oy + (2 * sy + 1) * bl.super_h / 2;
-    int zc = bl.wedge_oz + (2 * sz + 1) * bl.super_d / 2;
-    if (zc < 1) zc = 1;
-    int t = (yc * 256) / zc;                             // 256 * tan of the elevation; |yc| < 2^16
-    t = t > 65536 ? 65536 : (t < -65536 ? -65536 : t);   // (a tangent beyond 256 is outside any image; keeps the product below 2^31)
-    const int stripe = (t * bl.fy_px) >> (bl.wedge_mode == 3 ? 11 : 12);       // rows / 16 or / 8 (arithmetic shift: floor)
-    const int rot = bl.wedge_mode >= 2 ? 3 * (sx >> 2) : 0;
-    return ((h >> 29) << 3) | ((unsigned int)(stripe + rot) & 7u);
-}
+// The sub-list (bucket) of a super-brick: tsdf_host::list_bucket (launch_geometry.h), which the host sizes the sub-lists with too.
 
 __global__ __launch_bounds__(256) void classify_brick_list(MultiParamsInline mp, BrickListParams bl)
 {
@@ -1298,7 +1273,7 @@ __global__ __launch_bounds__(256) void classify_brick_list(MultiParamsInline mp,
     // (index mod 64 would be the slice group -- the sub-lists of slice groups in free space or behind the walls would run dry
     // long before the others and the launch would end on a quarter of its wavefronts)
     static_assert(kListBuckets == 64, "six bits: list_bucket");
-    const unsigned int bkt = list_bucket((unsigned int)id, sx, sy, sz, bl);
+    const unsigned int bkt = tsdf_host::list_bucket((unsigned int)id, sx, sy, sz, bl.wedge_mode, bl.wedge_oy, bl.wedge_oz, bl.super_h, bl.super_d, bl.fy_px);
     unsigned char *bucket = bl.counters + (size_t)bkt * kBucketStride;
     if (lane == 0) {
         // claims at super-brick granularity (what the per-launch decision is made from; the host adds the buckets up); the
