@@ -6,6 +6,8 @@
 // record at creation and wherever the brick shape changes; the launch sites read it and compute nothing of this themselves.
 // tests/launch_geometry_check.cpp sweeps all of it on the CPU under -fsanitize=address,undefined: a grid that overhangs an
 // allocation is a memory fault on the device, and here it is a failed comparison.
+// Last, the two launch decisions that go with the geometry: what a launch keeps of the summary words with the host's record of
+// them (SummaryRecord), and the kernel one frame runs (one_frame); tests/summary_duty_check.cpp walks both the same way.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -230,5 +232,52 @@ inline WorkListLayout work_list_layout(const tsdf_config &c, const SlabGeometry 
 inline Grid3 grid_classify_list(const WorkListLayout &w) { return {(unsigned)((w.n_super + 3) / 4), 1u, 1u}; }
 // integrate_brick_list: a wavefront per entry, sized for the worst case: the front groups and the back groups of every sub-list
 inline Grid3 grid_brick_list(const WorkListLayout &w) { return {(unsigned)(((w.bucket_cap + 3) / 4 + 1) * kListBuckets), 1u, 1u}; }
+
+// ---- the summary duty ----------------------------------------------------------------------------------------------
+// What a launch that writes weights keeps of the summary words (host_derive.h, "the summary word"):
+//   Nothing   the scalar kernel and the measurement build's kernels without a summary: the words are zeroed ahead of them
+//   Bits      bits 0 and 1: the fused, flat, brick and batched kernels, the ladder's summary kernels, variant 11; a kernel that
+//             meets a run does not load the segment's weights, so the runs are forgotten ahead of them (forget_runs)
+//   Runs      bits 0 and 1 and the weight runs: integrate_tile alone
+enum class Keeps { Nothing, Bits, Runs };
+enum class SummaryAction { None, Zero, ForgetRuns };   // what to queue ahead of the launch
+
+// What the host knows of a handle's words without reading them.  The words are zeroed only when they are not known to be zero
+// and the runs forgotten only when one may be set; every transition that drops an action errs to the cautious side.
+struct SummaryRecord {
+    bool known_zero = false;   // every word is zero
+    bool runs_maybe = false;   // some word may carry a run (bit 2 and a count)
+
+    SummaryAction before_launch(Keeps keeps)
+    {
+        if (keeps == Keeps::Nothing) {
+            if (known_zero) return SummaryAction::None;
+            known_zero = true;
+            runs_maybe = false;
+            return SummaryAction::Zero;
+        }
+        const bool forget = keeps == Keeps::Bits && runs_maybe;
+        known_zero = false;
+        runs_maybe = keeps == Keeps::Runs;
+        return forget ? SummaryAction::ForgetRuns : SummaryAction::None;
+    }
+    void after_fill() { known_zero = false; runs_maybe = true; }      // every word is kSummaryFresh: the count 0
+    void after_rebuild() { known_zero = false; runs_maybe = true; }   // recompute_flags finds the runs the arrays hold
+};
+
+// ---- the kernel of a one-frame launch ------------------------------------------------------------------------------
+// Scalar: rows of no multiple of 4 voxels, or the scalar variant.  MaskedBricks: a masked frame whose launch is classified
+// (classify_one_frame), given tile tables that fit and a brick view, row-mapped or flat.  Otherwise FlatSingle (rows of no
+// multiple of 256 voxels: the fused kernel with one frame) or Tile (integrate_tile).  With what the choice keeps of the words.
+enum class OneFrameKernel { Scalar, FlatSingle, MaskedBricks, Tile };
+struct OneFrame { OneFrameKernel kernel; Keeps keeps; };
+
+inline OneFrame one_frame(const SlabGeometry &g, const Variant &var, bool masked, bool tiles_fit)
+{
+    if (!g.quad_rows || var.scalar) return {OneFrameKernel::Scalar, Keeps::Nothing};
+    if (masked && classify_one_frame(var.classify, g.n_vox) && tiles_fit && g.brick_q > 0) return {OneFrameKernel::MaskedBricks, Keeps::Bits};
+    if (g.flat) return {OneFrameKernel::FlatSingle, Keeps::Bits};
+    return {OneFrameKernel::Tile, Keeps::Runs};
+}
 
 }  // namespace tsdf_host

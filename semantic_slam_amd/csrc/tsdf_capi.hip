@@ -1,8 +1,8 @@
-// tsdf_capi.hip -- implementation of include/tsdf_hip.h (libtsdf_hip.so).  Handles, integration, labels, colour and batches
-// are here; raycasting, tracking, merging, extents, association and segmentation each in a tsdf_<feature>_host.hip.h beside its
-// kernels, extraction, the file writers and the checkpoint calls in tsdf_extract_host.hip.h (the file formats themselves in
-// mesh_files.h, host-only), the group in tsdf_group.hip.h and include/tsdf_hip_diag.h in tsdf_diag.hip.h, all included at the
-// end (one translation unit).
+// tsdf_capi.hip -- implementation of include/tsdf_hip.h (libtsdf_hip.so).  Handles, integration, labels and colour are here;
+// batches, raycasting, tracking, merging, extents, association and segmentation each in a tsdf_<feature>_host.hip.h (the last
+// six beside their kernels), extraction, the file writers and the checkpoint calls in tsdf_extract_host.hip.h (the file formats
+// themselves in mesh_files.h, host-only), the group in tsdf_group.hip.h and include/tsdf_hip_diag.h in tsdf_diag.hip.h, all
+// included at the end (one translation unit).
 //
 // One handle = one z-slab of the voxel grid resident in HBM on one device + one HIP stream.
 // Host work per frame is the 4x4 pose composition (pose_math.h) and one kernel launch; the
@@ -153,8 +153,7 @@ struct tsdf_volume {
     StageRing<Staged<uint8_t>, kStageSlots> rgb;
     // free-space summary (one word per 256-voxel row segment), see tsdf_kernels.hip.h
     DevPtr<uint32_t> d_flags;
-    bool flags_known_zero = false;
-    bool runs_maybe_set = false;     // summary words may carry a weight run (bit 2 and a count): see forget_weight_runs
+    tsdf_host::SummaryRecord summary;   // what the host knows of the words; every weight-writing launch asks it first (summary_before)
 #ifdef TSDF_EXPERIMENTS
     DevBuf<unsigned int> d_super;    // per super-brick frame words of the current fused brick launch (classify_superbricks)
 #endif
@@ -506,22 +505,30 @@ int build_tile_tables(hipStream_t stream, const tsdf_config &c, const tsdfk::Int
     return TSDF_OK;
 }
 
-// Weight runs (host_derive.h, "the summary word") are kept by integrate_tile alone.  Every other launch that writes weights
-// and keeps the summary -- the fused kernels, the brick kernels, the batched kernel -- knows bits 0 and 1 only, so the runs
-// are forgotten ahead of it: one small pass over the words (2 MB at 512^3), once, since no such launch sets a run again.
-int forget_weight_runs(tsdf_volume *v)
+// Ahead of every launch that writes weights: what the launch keeps of the summary words decides what is queued first on the
+// handle's stream (launch_geometry.h, SummaryRecord).  A kernel that keeps nothing must not leave stale words behind, so they
+// are zeroed, unless they are known to be; one that keeps bits 0 and 1 only does not know the weight runs integrate_tile keeps,
+// so they are forgotten: one small pass over the words (2 MB at 512^3), once, since no such launch sets a run again.  A failed
+// call leaves the record as it was, but for "known zero", which goes.
+int summary_before(tsdf_volume *v, tsdf_host::Keeps keeps)
 {
-    if (!v->runs_maybe_set || v->geo.n_flags == 0) return TSDF_OK;
-    hipLaunchKernelGGL(tsdfk::forget_runs, to_dim3(tsdf_host::grid_summary_words(v->geo)), dim3(256), 0, v->stream, v->d_flags.get(), v->geo.n_flags);
-    HIP_TRY(hipGetLastError());
-    v->runs_maybe_set = false;
+    tsdf_host::SummaryRecord next = v->summary;
+    const tsdf_host::SummaryAction act = next.before_launch(keeps);
+    v->summary.known_zero = false;
+    if (act == tsdf_host::SummaryAction::Zero && v->geo.n_flags != 0)
+        HIP_TRY(hipMemsetAsync(v->d_flags, 0, v->geo.n_flags * sizeof(uint32_t), v->stream));
+    if (act == tsdf_host::SummaryAction::ForgetRuns && v->geo.n_flags != 0) {
+        hipLaunchKernelGGL(tsdfk::forget_runs, to_dim3(tsdf_host::grid_summary_words(v->geo)), dim3(256), 0, v->stream, v->d_flags.get(), v->geo.n_flags);
+        HIP_TRY(hipGetLastError());
+    }
+    v->summary = next;
     return TSDF_OK;
 }
 
 // The same with wavefront bricks (rows that divide into them): class per brick, then the brick kernel.  Queues the launch.
 int launch_masked_bricks(tsdf_volume *v, tsdfk::IntegrateParams &p)
 {
-    int rcf = forget_weight_runs(v);
+    int rcf = summary_before(v, tsdf_host::Keeps::Bits);
     if (rcf) return rcf;
     const tsdf_host::BrickGrid bg = tsdf_host::brick_grid(v->geo);   // workgroups of four bricks x slice groups, and the class table's bytes
     StoreSlot table;      // the frame's depth tile tables, first written on the handle's stream
@@ -543,24 +550,13 @@ int launch_masked_bricks(tsdf_volume *v, tsdfk::IntegrateParams &p)
     return table.release();
 }
 
-// Kernels that do not maintain the free-space summary must not leave stale "all ones" flags behind.
-int drop_summary(tsdf_volume *v)
-{
-    if (v->flags_known_zero || v->geo.n_flags == 0) return TSDF_OK;
-    HIP_TRY(hipMemsetAsync(v->d_flags, 0, v->geo.n_flags * sizeof(uint32_t), v->stream));
-    v->flags_known_zero = true;
-    v->runs_maybe_set = false;
-    return TSDF_OK;
-}
-
 int rebuild_summary(tsdf_volume *v)
 {
     if (v->geo.n_flags == 0 || v->geo.n_vox == 0) return TSDF_OK;
     hipLaunchKernelGGL(tsdfk::recompute_flags, to_dim3(tsdf_host::grid_recompute_flags(v->geo)), dim3(64, 4, 1), 0, v->stream, v->d_tsdf,
                        v->d_weight, v->d_flags, v->geo.quads_per_slice, v->geo.chunks_per_slice);
     HIP_TRY(hipGetLastError());
-    v->flags_known_zero = false;
-    v->runs_maybe_set = true;
+    v->summary.after_rebuild();
     return TSDF_OK;
 }
 
@@ -626,12 +622,15 @@ int launch_integrate(tsdf_volume *v, const float *depth_dev, const uint8_t *mask
     if (geo.nz == 0) return TSDF_OK;  // empty slab: nothing to do
     std::memcpy(v->last_cam2base, c2b, sizeof v->last_cam2base);
 #ifdef TSDF_EXPERIMENTS
-    if (geo.quad_rows && (v->variant == 2 || (v->variant >= 16 && !mask_dev))) return launch_integrate_experiment(v, depth_dev, mask_dev, c2b);
+    if (geo.quad_rows && (v->variant == 2 || (v->variant >= 16 && !mask_dev) ||
+                          (v->variant == 11 && mask_dev && !geo.flat && tiles_fit(geo.tiles_w, geo.tiles_h))))
+        return launch_integrate_experiment(v, depth_dev, mask_dev, c2b);
 #endif
-    const tsdf_host::Variant var = variant_of(v->variant);
-    if (!geo.quad_rows || var.scalar) {
-        // rows that are not 16-byte aligned (or the scalar kernel asked for): one voxel per lane; it does not keep the summary
-        int rc = drop_summary(v);
+    // which kernel, and what it keeps of the summary words (launch_geometry.h)
+    const tsdf_host::OneFrame one = tsdf_host::one_frame(geo, variant_of(v->variant), mask_dev != nullptr, tiles_fit(geo.tiles_w, geo.tiles_h));
+    if (one.kernel == tsdf_host::OneFrameKernel::Scalar) {
+        // rows that are not 16-byte aligned (or the scalar kernel asked for): one voxel per lane
+        int rc = summary_before(v, one.keeps);
         if (rc) return rc;
         const tsdfk::IntegrateParams p = make_params(v, depth_dev, mask_dev, c2b, 1);
         const dim3 block(64, 4, 1), grid = to_dim3(tsdf_host::grid_scalar_rows(geo));
@@ -645,28 +644,16 @@ int launch_integrate(tsdf_volume *v, const float *depth_dev, const uint8_t *mask
         return launch_multi(v, &depth_dev, mask_dev ? &mask_dev : nullptr, c2b, 1);
     }
     tsdfk::IntegrateParams p = make_params(v, depth_dev, mask_dev, c2b, 4);
-    v->flags_known_zero = false;   // integrate_tile keeps the free-space summary up to date
+    // per-object volumes see their instance only, so the bricks the tile table of depth x mask proves untouched are told to
+    // leave (variant 7: never; small launches: not worth the three small dispatches ahead of it): per wavefront brick, skipped
+    // by rows, slices and columns
+    if (one.kernel == tsdf_host::OneFrameKernel::MaskedBricks) return launch_masked_bricks(v, p);
+    int rc = summary_before(v, one.keeps);   // integrate_tile keeps the free-space summary up to date, and the weight runs
+    if (rc) return rc;
     const dim3 block(64, 4, 1), grid = to_dim3(tsdf_host::grid_quad_rows(geo, 8));
-    if (mask_dev) {
-        // per-object volumes see their instance only, so the bricks the tile table of depth x mask proves untouched are
-        // told to leave (variant 7: never; small launches: not worth the three small dispatches ahead of it)
-        const bool classify = tsdf_host::classify_one_frame(var.classify, geo.n_vox) && tiles_fit(p.tiles_w, p.tiles_h);
-        if (classify && p.brick_q > 0 && (!kExperiments || v->variant != 11)) {
-            int rc = launch_masked_bricks(v, p);    // per wavefront brick: skipped by rows, slices and columns
-            if (rc) return rc;
-        } else {
-#ifdef TSDF_EXPERIMENTS
-            if (v->variant == 11 && classify) return launch_integrate_experiment(v, depth_dev, mask_dev, c2b);
-#endif
-            set_sweep(v, p);
-            v->runs_maybe_set = true;      // ... and the weight runs
-            hipLaunchKernelGGL((tsdfk::integrate_tile<2, true>), grid, block, 0, v->stream, p);
-        }
-    } else {
-        set_sweep(v, p);
-        v->runs_maybe_set = true;
-        hipLaunchKernelGGL((tsdfk::integrate_tile<2, false>), grid, block, 0, v->stream, p);
-    }
+    set_sweep(v, p);
+    if (mask_dev) hipLaunchKernelGGL((tsdfk::integrate_tile<2, true>), grid, block, 0, v->stream, p);
+    else hipLaunchKernelGGL((tsdfk::integrate_tile<2, false>), grid, block, 0, v->stream, p);
     HIP_TRY(hipGetLastError());
     return TSDF_OK;
 }
@@ -688,7 +675,7 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
     const tsdf_host::SlabGeometry &geo = v->geo;
     if (geo.nz == 0 || n == 0) return TSDF_OK;
     {
-        int rc = forget_weight_runs(v);    // every kernel below keeps bits 0 and 1 of the summary only
+        int rc = summary_before(v, tsdf_host::Keeps::Bits);    // every kernel below keeps bits 0 and 1 of the summary only
         if (rc) return rc;
     }
     auto fill_pose = [&](tsdfk::FramePose &fp, int f) {
@@ -702,7 +689,6 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
         tsdfk::FramePose pose;
         fill_pose(pose, 0);
         std::memcpy(v->last_cam2base, c2b, sizeof v->last_cam2base);
-        v->flags_known_zero = false;
 #ifdef TSDF_EXPERIMENTS
         {
             bool handled = false;
@@ -710,8 +696,8 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
             if (rc || handled) return rc;
         }
 #endif
-        if (geo.flat && pose.mask != nullptr && tsdf_host::classify_one_frame(variant_of(v->variant).classify, geo.n_vox) &&
-            tiles_fit(common.tiles_w, common.tiles_h) && common.brick_q > 0) {
+        const tsdf_host::OneFrame one = tsdf_host::one_frame(geo, variant_of(v->variant), pose.mask != nullptr, tiles_fit(geo.tiles_w, geo.tiles_h));
+        if (geo.flat && one.kernel == tsdf_host::OneFrameKernel::MaskedBricks) {
             // one masked frame into a flat-mapped volume (the reference's 200^3 object grids), large enough to repay a class table
             tsdfk::IntegrateParams cp = make_params(v, depth_dev[0], pose.mask, c2b, 4);
             return launch_masked_bricks(v, cp);
@@ -724,7 +710,6 @@ int launch_multi(tsdf_volume *v, const float *const *depth_dev, const uint8_t *c
         return TSDF_OK;
     }
     std::memcpy(v->last_cam2base, c2b + 16 * (n - 1), sizeof v->last_cam2base);
-    v->flags_known_zero = false;   // the fused kernels maintain the summary
     // the frame blocks travel in the kernarg: nothing is staged on the stream ahead of the launch
     tsdfk::MultiParamsInline mi;
     mi.common = make_params(v, depth_dev[0], nullptr, c2b, 4);
@@ -966,6 +951,19 @@ int integrate_frames(tsdf_volume *v, const float *const *depth_dev, const uint8_
     return rc;
 }
 
+// n collected frames (c2b: their n x 16 composed poses; masks[f] null: frame f has no mask): one fused launch, or with a single
+// frame (or a variant that does not fuse) the one-frame kernels.  *some_mask (may be null): some frame has a mask.
+int apply_collected(tsdf_volume *v, const float *const *depth, const uint8_t *const *masks, const float *c2b, int n, bool *some_mask = nullptr)
+{
+    bool any_mask = false;
+    for (int f = 0; f < n; ++f) any_mask = any_mask || masks[f] != nullptr;
+    if (some_mask) *some_mask = any_mask;
+    if (can_fuse(v) && n > 1) return launch_multi(v, depth, any_mask ? masks : nullptr, c2b, n);
+    int rc = TSDF_OK;
+    for (int f = 0; f < n && rc == TSDF_OK; ++f) rc = launch_integrate(v, depth[f], masks[f], c2b + 16 * f);
+    return rc;
+}
+
 // Apply the collected frames (poses already composed) as one sequence; their store slots go back after the launch.
 int flush_pending(tsdf_volume *v)
 {
@@ -980,12 +978,7 @@ int flush_pending(tsdf_volume *v)
     if (e == hipSuccess) e = hipStreamWaitEvent(v->stream, v->pend_copied, 0);
     if (e == hipSuccess) {
         bool any_mask = false;
-        for (int f = 0; f < n; ++f) any_mask = any_mask || v->pend_mask[f] != nullptr;
-        if (can_fuse(v) && n > 1) {
-            rc = launch_multi(v, v->pend_depth, any_mask ? v->pend_mask : nullptr, v->pend_c2b, n);
-        } else {   // a single collected frame (or a variant that does not fuse): the one-frame kernels
-            for (int f = 0; f < n && rc == TSDF_OK; ++f) rc = launch_integrate(v, v->pend_depth[f], v->pend_mask[f], v->pend_c2b + 16 * f);
-        }
+        rc = apply_collected(v, v->pend_depth, v->pend_mask, v->pend_c2b, n, &any_mask);
         // whatever the launch returned: kernels it queued on the handle's stream may read the slots, so they go back behind them
         // (and without a word when the launch has failed: its message is the one to report)
         hipError_t re = StoreSlot::release_all(v, &v->store->frames, v->pend_slot, n);
@@ -1134,8 +1127,7 @@ int fill(tsdf_volume *v)
     HIP_TRY(hipGetLastError());
     if (v->geo.n_flags) {  // every TSDF value is 1: every segment flag is set
         HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)v->d_flags, (int)tsdf_host::kSummaryFresh, v->geo.n_flags, v->stream));   // ... and every weight is the count 0
-        v->flags_known_zero = false;
-        v->runs_maybe_set = true;
+        v->summary.after_fill();
     }
     return TSDF_OK;
 }
@@ -1655,312 +1647,9 @@ int tsdf_download_colour(tsdf_volume *v, uint32_t *colour_host)
     return TSDF_OK;
 }
 
-// ---------------------------------------------------------------------------------------------
-// batched per-object volumes
-// ---------------------------------------------------------------------------------------------
-namespace {
-
-
-// Apply the frames the batch has collected: one fused launch per member, in member order, on the batch's stream.
-int batch_flush(tsdf_batch *b)
-{
-    if (b->pend_count == 0 || b->in_flush) return TSDF_OK;
-    b->in_flush = true;
-    const int n = b->pend_count, members = (int)b->vols.size();
-    b->pend_count = 0;
-    const size_t px = (size_t)b->vols[0]->cfg.im_height * b->vols[0]->cfg.im_width;
-    const float *ptrs[tsdfk::kMaxFramesPerLaunch];
-    for (int f = 0; f < n; ++f) ptrs[f] = b->d_depth_pool + (size_t)f * px;
-    int rc = TSDF_OK;
-    if (hipSetDevice(b->device) != hipSuccess) rc = fail(TSDF_ERR_HIP, "tsdf_batch: hipSetDevice failed");
-    // fork: the side streams start when everything queued on the batch's stream so far (the frames' copies) is done
-    const int lanes = tsdf_host::batch_lanes(members);
-    hipError_t e = hipSuccess;
-    if (rc == TSDF_OK && lanes > 1) {
-        if (!b->collected) {      // all or none
-            Event collected, side_done[kBatchSideStreams];
-            Stream side[kBatchSideStreams];
-            e = event_create(collected);
-            for (int k = 0; k < kBatchSideStreams && e == hipSuccess; ++k) {
-                e = stream_create(side[k]);
-                if (e == hipSuccess) e = event_create(side_done[k]);
-            }
-            if (e == hipSuccess) {
-                b->collected = std::move(collected);
-                for (int k = 0; k < kBatchSideStreams; ++k) { b->side[k] = std::move(side[k]); b->side_done[k] = std::move(side_done[k]); }
-            }
-        }
-        if (e == hipSuccess) e = hipEventRecord(b->collected, b->stream);
-        for (int k = 0; k < lanes && e == hipSuccess; ++k) e = hipStreamWaitEvent(b->side[k], b->collected, 0);
-        if (e != hipSuccess) rc = fail(TSDF_ERR_HIP, "tsdf_batch: side streams: %s", hipGetErrorString(e));
-    }
-    for (int i = 0; i < members && rc == TSDF_OK; ++i) {
-        tsdf_volume *v = b->vols[i];
-        const uint8_t *const *masks = b->pend_mask.data() + (size_t)i * tsdfk::kMaxFramesPerLaunch;
-        const float *c2b = b->pend_c2b.data() + (size_t)i * tsdfk::kMaxFramesPerLaunch * 16;
-        bool any_mask = false;
-        for (int f = 0; f < n; ++f) any_mask = any_mask || masks[f] != nullptr;
-        if (lanes > 1) v->stream = b->side[i % lanes];
-        if (can_fuse(v) && n > 1) {
-            rc = launch_multi(v, ptrs, any_mask ? masks : nullptr, c2b, n);
-        } else {
-            for (int f = 0; f < n && rc == TSDF_OK; ++f) rc = launch_integrate(v, ptrs[f], masks[f], c2b + 16 * f);
-        }
-        v->stream = b->stream;
-    }
-    // join: whatever follows on the batch's stream (the next frames' copies into the pool, a download) comes after them
-    for (int k = 0; k < lanes && lanes > 1; ++k) {
-        if (hipEventRecord(b->side_done[k], b->side[k]) != hipSuccess || hipStreamWaitEvent(b->stream, b->side_done[k], 0) != hipSuccess) {
-            (void)hipDeviceSynchronize();   // never leave the streams unordered
-            if (rc == TSDF_OK) rc = fail(TSDF_ERR_HIP, "tsdf_batch: joining the side streams failed");
-        }
-    }
-    b->in_flush = false;
-    return rc;
-}
-
-// Collect one frame for every member: the depth image once, the masks by one gather launch, the poses composed now.
-// Everything is queued on the batch's stream, so the caller's buffers are free for reuse under that stream's order and the
-// pool is not overwritten before the launches that read it have run.
-int batch_collect(tsdf_batch *b, const float *depth_dev, const uint8_t *const *masks_dev, const float cam2world[16])
-{
-    const int members = (int)b->vols.size(), slot = b->pend_count;
-    const size_t px = (size_t)b->vols[0]->cfg.im_height * b->vols[0]->cfg.im_width;
-    if (!b->d_depth_pool) {
-        HIP_TRY(dev_alloc(b->d_depth_pool, (size_t)tsdfk::kMaxFramesPerLaunch * px * sizeof(float)));
-        b->pend_c2b.assign((size_t)members * tsdfk::kMaxFramesPerLaunch * 16, 0.0f);
-        b->pend_mask.assign((size_t)members * tsdfk::kMaxFramesPerLaunch, nullptr);
-    }
-    bool any_mask = false;
-    for (int i = 0; i < members && masks_dev; ++i) any_mask = any_mask || masks_dev[i] != nullptr;
-    if (any_mask && !b->d_mask_pool)
-        HIP_TRY(dev_alloc(b->d_mask_pool, (size_t)tsdfk::kMaxFramesPerLaunch * members * px));
-    HIP_TRY(hipMemcpyAsync(b->d_depth_pool + (size_t)slot * px, depth_dev, px * sizeof(float), hipMemcpyDeviceToDevice, b->stream));
-    for (int i0 = 0; i0 < members && any_mask; i0 += tsdfk::kGatherMasks) {
-        tsdfk::MaskGatherParams gp;
-        const int m = std::min(tsdfk::kGatherMasks, members - i0);
-        bool some = false;
-        for (int k = 0; k < tsdfk::kGatherMasks; ++k) {
-            gp.src[k] = k < m ? masks_dev[i0 + k] : nullptr;
-            gp.dst[k] = k < m ? b->d_mask_pool + ((size_t)slot * members + i0 + k) * px : nullptr;
-            some = some || gp.src[k] != nullptr;
-        }
-        gp.bytes = px;
-        if (some) hipLaunchKernelGGL(tsdfk::gather_masks, dim3((unsigned)((px + 4095) / 4096), (unsigned)m), dim3(256), 0, b->stream, gp);
-    }
-    HIP_TRY(hipGetLastError());
-    for (int i = 0; i < members; ++i) {
-        tsdf_volume *v = b->vols[i];
-        float *c2b = b->pend_c2b.data() + ((size_t)i * tsdfk::kMaxFramesPerLaunch + slot) * 16;
-        compose_cam2base(v, cam2world, c2b);   // each object has its own base frame (ref: src/Object.cpp:23-29)
-        std::memcpy(v->last_cam2base, c2b, 16 * sizeof(float));
-        b->pend_mask[(size_t)i * tsdfk::kMaxFramesPerLaunch + slot] =
-            (masks_dev && masks_dev[i]) ? b->d_mask_pool + ((size_t)slot * members + i) * px : nullptr;
-    }
-    b->pend_count = slot + 1;
-    if (b->pend_count >= std::min(b->vols[0]->defer_n, (int)tsdfk::kMaxFramesPerLaunch)) return batch_flush(b);
-    return TSDF_OK;
-}
-
-}  // namespace
-
-int tsdf_batch_destroy(tsdf_batch *b)
-{
-    if (!b) return TSDF_OK;
-    (void)hipSetDevice(b->device);
-    if (b->stream) (void)hipStreamSynchronize(b->stream);
-    for (tsdf_volume *v : b->vols) {
-        if (v) { v->stream = v->own_stream; v->owner = nullptr; tsdf_destroy(v); }
-    }
-    for (Stream &side : b->side)
-        if (side) (void)hipStreamSynchronize(side);
-    delete b;            // the owners release the batch's memory, events and streams
-    return TSDF_OK;
-}
-
-int tsdf_batch_create(const tsdf_config *cfgs, int32_t n, tsdf_batch **out)
-{
-    if (!cfgs || !out || n <= 0) return fail(TSDF_ERR_INVALID, "tsdf_batch_create: bad argument");
-    *out = nullptr;
-    for (int i = 0; i < n; ++i) {
-        if (cfgs[i].device != cfgs[0].device || cfgs[i].im_height != cfgs[0].im_height ||
-            cfgs[i].im_width != cfgs[0].im_width)
-            return fail(TSDF_ERR_INVALID, "tsdf_batch_create: volume %d differs in device or image size", i);
-        if (cfgs[i].dim_x % 4 != 0)
-            return fail(TSDF_ERR_INVALID, "tsdf_batch_create: volume %d: dim_x must be a multiple of 4", i);
-    }
-    tsdf_batch *b = new (std::nothrow) tsdf_batch();
-    if (!b) return fail(TSDF_ERR_INVALID, "tsdf_batch_create: out of host memory");
-    b->device = cfgs[0].device;
-    auto cleanup = [&](int code) { tsdf_batch_destroy(b); return code; };
-    std::vector<int2> map;
-    for (int i = 0; i < n; ++i) {
-        tsdf_volume *v = nullptr;
-        int rc = create_volume(&cfgs[i], true, &v);
-        if (rc) return cleanup(rc);
-        b->vols.push_back(v);
-        const int nz = cfgs[i].z_end - cfgs[i].z_begin;
-        for (int z = 0; z < nz; ++z) map.push_back(make_int2(i, z));
-        b->max_blocks = std::max(b->max_blocks, (int)tsdf_host::grid_flat(v->geo).x);
-    }
-    b->total_slices = (int)map.size();
-    if (b->total_slices > 65535) return cleanup(fail(TSDF_ERR_INVALID, "tsdf_batch_create: %d slices in total exceed the launch limit 65535", b->total_slices));
-    hipError_t e = hipSetDevice(b->device);
-    if (e == hipSuccess) e = stream_create(b->stream);
-    if (e == hipSuccess && !map.empty()) e = dev_alloc(b->d_slice_map, map.size() * sizeof(int2));
-    if (e == hipSuccess && !map.empty()) e = hipMemcpy(b->d_slice_map, map.data(), map.size() * sizeof(int2), hipMemcpyHostToDevice);
-    for (auto &s : b->blocks.slots) {
-        if (e == hipSuccess) e = host_alloc(s.params.host, n * sizeof(tsdfk::IntegrateParams), hipHostMallocDefault);
-        if (e == hipSuccess) e = dev_alloc(s.params.dev, n * sizeof(tsdfk::IntegrateParams));
-        if (e == hipSuccess) e = host_alloc(s.poses.host, n * sizeof(tsdfk::FramePose), hipHostMallocDefault);
-        if (e == hipSuccess) e = dev_alloc(s.poses.dev, n * sizeof(tsdfk::FramePose));
-        if (e == hipSuccess) e = event_create(s.done);
-    }
-    if (e != hipSuccess) return cleanup(fail(TSDF_ERR_HIP, "tsdf_batch_create: %s", hipGetErrorString(e)));
-    for (tsdf_volume *v : b->vols) {   // creation fills ran on each volume's own stream: finish them, then share ours
-        if (hipStreamSynchronize(v->stream) != hipSuccess) return cleanup(fail(TSDF_ERR_HIP, "tsdf_batch_create: sync failed"));
-        v->stream = b->stream;
-        v->owner = b;
-    }
-    *out = b;
-    return TSDF_OK;
-}
-
-int tsdf_batch_size(const tsdf_batch *b) { return b ? (int)b->vols.size() : 0; }
-
-int tsdf_batch_volume(tsdf_batch *b, int32_t i, tsdf_volume **vol)
-{
-    if (!b || !vol || i < 0 || i >= (int)b->vols.size()) return fail(TSDF_ERR_INVALID, "tsdf_batch_volume: bad argument");
-    *vol = b->vols[i];
-    return TSDF_OK;
-}
-
-int tsdf_batch_sync(tsdf_batch *b)
-{
-    if (!b) return fail(TSDF_ERR_INVALID, "tsdf_batch_sync: NULL handle");
-    HIP_TRY(hipSetDevice(b->device));
-    int rc = batch_flush(b);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    return TSDF_OK;
-}
-
-int tsdf_batch_integrate_device(tsdf_batch *b, const float *depth_dev, const uint8_t *const *masks_dev,
-                                const float cam2world[16])
-{
-    if (!b || !depth_dev || !cam2world) return fail(TSDF_ERR_INVALID, "tsdf_batch_integrate_device: NULL argument");
-    HIP_TRY(hipSetDevice(b->device));
-    if (b->total_slices == 0) return TSDF_OK;
-    const int n = (int)b->vols.size();
-    for (tsdf_volume *v : b->vols)
-        if (v->pend_count > 0) { int rc = flush_pending(v); if (rc) return rc; }   // frames given to a borrowed handle come first
-    // Deferral as for a single handle (tsdf_set_deferral on the FIRST member switches it), where it pays (tsdf_host::batch_defers)
-    {
-        bool defer = b->vols[0]->defer_n > 1;
-        int64_t total = 0;
-        for (tsdf_volume *v : b->vols) { defer = defer && can_fuse(v); total += v->geo.n_vox; }
-        defer = defer && tsdf_host::batch_defers(n, total);
-        if (defer) return batch_collect(b, depth_dev, masks_dev, cam2world);
-        int rc = batch_flush(b);   // the policy changed between calls (tsdf_set_deferral, a kernel variant)
-        if (rc) return rc;
-    }
-    for (tsdf_volume *v : b->vols) {   // the batched kernel maintains the summary, but not the weight runs (on the batch's stream, which the members share)
-        int rc = forget_weight_runs(v);
-        if (rc) return rc;
-    }
-    decltype(b->blocks)::Slot *s = nullptr;
-    HIP_TRY(b->blocks.take(&s));
-    tsdfk::IntegrateParams *const h_params = s->params.host, *const d_params = s->params.dev;
-    tsdfk::FramePose *const h_poses = s->poses.host, *const d_poses = s->poses.dev;
-    for (int i = 0; i < n; ++i) {
-        tsdf_volume *v = b->vols[i];
-        float c2b[16];
-        compose_cam2base(v, cam2world, c2b);   // each object has its own base frame (ref: src/Object.cpp:23-29)
-        std::memcpy(v->last_cam2base, c2b, sizeof c2b);
-        const tsdfk::IntegrateParams q = make_params(v, depth_dev, masks_dev ? masks_dev[i] : nullptr, c2b, 4);
-        h_params[i] = q;
-        pose_from_params(h_poses[i], q);
-        v->flags_known_zero = false;           // the batched kernel maintains the summary
-    }
-    // Instance masks given: every object sees only its own instance (ref: src/Engine.cpp:192-193), so most workgroups of
-    // most objects see nothing.  Tile tables of depth x mask per object, the class of every workgroup of the launch
-    // (one thread each), and the launch's untouched workgroups leave at once.  (First volume on variant 7: never.)
-    bool any_mask = false;
-    for (int i = 0; i < n && masks_dev; ++i) any_mask = any_mask || masks_dev[i] != nullptr;
-    bool same_range = true;   // one tile table per object, but all made with one depth-range test
-    for (int i = 1; i < n; ++i) same_range = same_range && b->vols[i]->cfg.max_depth == b->vols[0]->cfg.max_depth;
-    int64_t launch_voxels = 0;
-    for (tsdf_volume *v : b->vols) launch_voxels += v->geo.n_vox;
-    // ... when the launch is large enough, and not for many small volumes (tsdf_host::batch_classifies)
-    const bool classify = any_mask && same_range && tsdf_host::batch_classifies(variant_of(b->vols[0]->variant).classify, n, launch_voxels) &&
-                          tiles_fit(h_params[0].tiles_w, h_params[0].tiles_h);
-    if (classify) {
-        // one coarse table per member, laid out as a launch's table slot lays out its frames' coarse ones
-        const size_t per = tsdf_host::table_slot_layout(b->vols[0]->cfg, b->vols[0]->geo.tile, false).coarse_elems;
-        if (!b->d_tiles) {      // (and, in the measurement build, the class table beside them: both or neither)
-            DevPtr<float2> tiles;
-            DevPtr<uint8_t> wg_class;
-            HIP_TRY(dev_alloc(tiles, (size_t)n * per * sizeof(float2)));
-            if (kExperiments) HIP_TRY(dev_alloc(wg_class, (size_t)b->max_blocks * b->total_slices));
-            b->d_tiles = std::move(tiles); b->d_wg_class = std::move(wg_class);
-            b->tiles_per_object = per;
-        }
-        std::vector<const float *> depths((size_t)n, depth_dev);
-        int rc = build_tile_tables(b->stream, b->vols[0]->cfg, h_params[0], depths.data(), masks_dev, n, b->d_tiles);
-        if (rc) return rc;
-        for (int i = 0; i < n; ++i) h_poses[i].tiles = b->d_tiles + (size_t)i * per;
-    }
-    HIP_TRY(hipMemcpyAsync(d_params, h_params, n * sizeof(tsdfk::IntegrateParams), hipMemcpyHostToDevice, b->stream));
-    HIP_TRY(hipMemcpyAsync(d_poses, h_poses, n * sizeof(tsdfk::FramePose), hipMemcpyHostToDevice, b->stream));
-    dim3 block(64, 4, 1), grid(b->max_blocks, 1, b->total_slices);
-    // a class per wavefront brick (every member has a brick view: dim_x % 4 == 0 is a condition of tsdf_batch_create)
-    int brick_blocks = 0;
-    bool bricks = classify && !(kExperiments && b->vols[0]->variant == 11);
-    for (int i = 0; i < n && bricks; ++i) {
-        bricks = b->vols[i]->geo.brick_q > 0;
-        brick_blocks = std::max(brick_blocks, tsdf_host::brick_blocks(b->vols[i]->geo));
-    }
-    if (bricks) {
-        // z index of the brick launches: slice groups (rebuilt when a member's brick depth changed: tsdf_set_brick_shape)
-        bool same = b->d_group_map != nullptr && (int)b->group_s.size() == n;
-        for (int i = 0; i < n && same; ++i) same = b->group_s[i] == h_params[i].brick_s;
-        if (!same) {
-            std::vector<int2> gmap;
-            b->group_s.assign((size_t)n, 1);
-            for (int i = 0; i < n; ++i) {
-                b->group_s[i] = b->vols[i]->geo.brick_s;
-                for (int g = 0; g < b->vols[i]->geo.nz_groups; ++g) gmap.push_back(make_int2(i, g));
-            }
-            HIP_TRY(hipStreamSynchronize(b->stream));
-            HIP_TRY(dev_alloc(b->d_group_map, std::max<size_t>(gmap.size(), 1) * sizeof(int2)));
-            HIP_TRY(hipMemcpy(b->d_group_map, gmap.data(), gmap.size() * sizeof(int2), hipMemcpyHostToDevice));
-            b->total_groups = (int)gmap.size();
-        }
-        const tsdf_host::BrickGrid bg = tsdf_host::brick_grid(brick_blocks, b->total_groups);   // the widest member's blocks x all slice groups
-        HIP_TRY(b->d_brick_class.ensure(bg.class_elems));
-        hipLaunchKernelGGL(tsdfk::classify_bricks_batched, dim3((unsigned)((bg.class_elems + 255) / 256)), dim3(256), 0, b->stream,
-                           d_params, d_poses, b->d_group_map, b->d_brick_class, brick_blocks, b->total_groups);
-        hipLaunchKernelGGL((tsdfk::integrate_multi_batched_bricks<kBrickNT>), to_dim3(bg.grid), block, 0, b->stream,
-                           d_params, d_poses, b->d_group_map, b->d_brick_class);
-#ifdef TSDF_EXPERIMENTS
-    } else if (classify) {   // variant 11: a class per 1024-voxel workgroup patch (round 2a's shape)
-        const size_t n_wg = (size_t)b->max_blocks * b->total_slices;
-        hipLaunchKernelGGL(tsdfk::classify_workgroups_batched, dim3((unsigned)((n_wg + 255) / 256)), dim3(256), 0, b->stream,
-                           d_params, d_poses, b->d_slice_map, b->d_wg_class, b->max_blocks, b->total_slices);
-        hipLaunchKernelGGL((tsdfk::integrate_multi_batched_cls<true, true>), grid, block, 0, b->stream, d_params, d_poses,
-                           b->d_slice_map, b->d_wg_class);
-#endif
-    } else {
-        hipLaunchKernelGGL((tsdfk::integrate_multi_batched<true>), grid, block, 0, b->stream, d_params, d_poses,
-                           b->d_slice_map);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(b->blocks.consumed(s, b->stream));
-    return TSDF_OK;
-}
-
 }  // extern "C"
 
+#include "tsdf_batch_host.hip.h"
 #include "tsdf_raycast_host.hip.h"
 #include "tsdf_track_host.hip.h"
 #include "tsdf_fuse_host.hip.h"

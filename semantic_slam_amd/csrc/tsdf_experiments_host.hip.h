@@ -81,8 +81,7 @@ int launch_integrate_experiment(tsdf_volume *v, const float *depth_dev, const ui
     if (v->geo.flat && variant != 2) return launch_multi(v, &depth_dev, mask_dev ? &mask_dev : nullptr, c2b, 1);   // the flat mapping serves them all
     tsdfk::IntegrateParams p = make_params(v, depth_dev, mask_dev, c2b, 4);
     if (variant == 11) {   // masked, row-mapped, classified per workgroup (256 x 8 voxels)
-        v->flags_known_zero = false;
-        int rcf = forget_weight_runs(v);
+        int rcf = summary_before(v, tsdf_host::Keeps::Bits);
         if (rcf) return rcf;
         const dim3 grid = to_dim3(tsdf_host::grid_quad_rows(v->geo, 8));
         StoreSlot table;
@@ -94,14 +93,8 @@ int launch_integrate_experiment(tsdf_volume *v, const float *depth_dev, const ui
     }
     // which launches keep the free-space summary up to date: the SUM kernels; the rows kernel and the plain tile variants do not
     const bool summary = variant != 2 && ((variant >= 32 && variant < 64) || (variant >= 80 && variant < 96) || variant >= 112);
-    if (!summary) {
-        int rc = drop_summary(v);
-        if (rc) return rc;
-    } else {
-        v->flags_known_zero = false;
-        int rc = forget_weight_runs(v);    // the ladder's summary kernels know bits 0 and 1 only
-        if (rc) return rc;
-    }
+    int rcs = summary_before(v, summary ? tsdf_host::Keeps::Bits : tsdf_host::Keeps::Nothing);   // the ladder's summary kernels know bits 0 and 1 only
+    if (rcs) return rcs;
     if (variant == 2) {
         const dim3 block(64, 4, 1), grid = to_dim3(tsdf_host::grid_quad_rows(v->geo, 4));
         if (mask_dev) hipLaunchKernelGGL((tsdfk::ladder_rows<4, true>), grid, block, 0, v->stream, p);

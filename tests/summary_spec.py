@@ -2,8 +2,10 @@
 about its segment at any moment (sound), what a rebuild makes of the arrays (rebuilt), how a word moves under a one-frame
 launch of integrate_tile (after_update) and under every other writer of weights (Predictor).  Restated from
 csrc/host_derive.h ("the summary word", word_after_update), csrc/tsdf_kernels.hip.h (IntegrateParams::flags, recompute_flags,
-forget_runs) and csrc/tsdf_capi.hip (fill, drop_summary, forget_weight_runs, rebuild_summary and their callers); nothing here
-calls the library.  tsdf_summary_words (include/tsdf_hip_diag.h) reads the words this file speaks about.
+forget_runs), csrc/launch_geometry.h ("the summary duty": Keeps and SummaryRecord, whose actions are Predictor.drop and
+Predictor.forget; one_frame, restated as one_frame_kind) and csrc/tsdf_capi.hip (fill, rebuild_summary, summary_before and its
+callers); nothing here calls the library, and tests/test_summary_duty.py holds one_frame_kind and the Predictor's step to
+one_frame without a device.  tsdf_summary_words (include/tsdf_hip_diag.h) reads the words this file speaks about.
 
   bit 0       every TSDF value of the segment has the bit pattern of 1.0f
   bit 1       every weight of the segment is finite and >= 0
@@ -171,7 +173,7 @@ def stale_run_errors(lay, stale, upd, w1):
 
 
 def one_frame_kind(lay, variant, masked, n_vox):
-    """What launch_integrate queues for one frame: "scalar" (variant 1, or rows of no multiple of 4 voxels), "multi" (the flat
+    """What launch_integrate queues for one frame (csrc/launch_geometry.h, one_frame): "scalar" (variant 1, or rows of no multiple of 4 voxels), "multi" (the flat
     mapping: launch_multi with one frame), "bricks" (a masked frame that is classified: variant 8 always, 7 never, else from
     48 M voxels: classify_one_frame) or "tile" (integrate_tile).  Frames of the walks have tile tables that fit and every
     grid with rows of a multiple of 4 voxels has a brick view."""
@@ -213,13 +215,13 @@ class Predictor:
         self.claim = np.ones(self.lay.n_words, bool)
         self.exact = True
 
-    def forget(self):                               # forget_weight_runs ahead of launch_multi, masked bricks, the batched kernel
+    def forget(self):                               # summary_before, bits 0 and 1 kept: launch_multi, masked bricks, the batched kernel
         self.note("forget")
         self.words = self.words & u32(ONES | SANE)
         self.claim[:] = True
         self.exact = False
 
-    def drop(self):                                 # drop_summary ahead of the scalar kernel
+    def drop(self):                                 # summary_before, nothing kept: the scalar kernel
         self.note("drop")
         self.words = np.zeros(self.lay.n_words, u32)
         self.claim[:] = True
