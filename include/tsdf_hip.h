@@ -450,6 +450,54 @@ int tsdf_fuse_params_default(const tsdf_config *dst_cfg, tsdf_fuse_params *out);
 int tsdf_fuse_volume(tsdf_volume *dst, tsdf_volume *src, const tsdf_fuse_params *p, tsdf_fuse_counts *counts /* may be NULL */);
 
 /*
+ * Registration of one volume against another, and the merge at a given pose.  tsdf_fuse_volume samples src through
+ * M = inverse(base2world_src) * base2world_dst and nothing else, so both base2world must already put the volumes in the same
+ * place.  A duplicate object fused from another stretch of the trajectory carries that stretch's drift, and a moved object a
+ * stale pose; there the write = 0 comparison reports a low agree_band / both_band.  tsdf_align_volume estimates the rigid motion
+ * dst2src that takes dst's base frame to src's from the two signed-distance fields themselves (direct SDF-to-SDF alignment,
+ * Gauss-Newton on the TSDF difference over a coarse-to-fine lattice of dst's voxels), and tsdf_fuse_volume_at merges at it.
+ * Not a reference function; the rule is stated exactly in csrc/tsdf_align.hip.h and restated in tests/align_spec.py.
+ *   weight_thresh   finite: a voxel or a source corner counts as observed when its weight is > this
+ *   resid_thresh    finite, > 0: a pair is dropped when the two TSDF values (dst truncation units) differ by more than this
+ *   n_levels        1..3; level l takes every 2^l-th voxel of dst per axis; levels run n_levels - 1 .. 0
+ *   iters[l]        >= 0 iterations at level l (0 skips the level)
+ *   min_pairs       >= 0: fewer pairs in an iteration and the run is lost
+ *   eps_rot, eps_trans   finite, > 0: a level ends when a step is below both (radians, metres)
+ * Result: dst2src (row-major 4 x 4, last row 0 0 0 1; on a lost run the starting matrix's own bits), status 0 converged,
+ * 1 iterations exhausted, 2 lost (too few pairs, or a failed Cholesky pivot; not an error: TSDF_OK), iters_run per level, and
+ * the pairs and rmse = sqrt(sum r^2 / pairs) (dst truncation units) of the last iteration run.
+ * Limits: a residual exists only where both fields are inside their truncation bands, so the basin is about one truncation
+ * distance of surface displacement; the coarse levels subsample, they do not widen it.  A caller with a larger error starts
+ * from a better guess, for instance the two centroids of tsdf_extent_metric.  The library decides nothing: whether the result
+ * is trusted is the caller's call from pairs, rmse and a following write = 0 merge.  Labels and colours are not read.
+ * tsdf_align_params_default: weight_thresh 0.9, resid_thresh 1.0, 2 levels, iters {10, 10, 0}, min_pairs 300, eps 1e-5 rad /
+ * 1e-5 m: choices, not measurements.  tsdf_fuse_pose_default: the M tsdf_fuse_volume composes from the two configurations.
+ * Both are host arithmetic only and need no device.
+ * tsdf_align_volume: guess_dst2src NULL starts from tsdf_fuse_pose_default's matrix; only the first three rows of a pose are
+ * read, and they are taken as given (rigidity is the caller's duty).  tsdf_align_system: one pass of level `level` at the given
+ * pose in tsdf_track_system's layout (21 of J^T J, 6 of J^T r, sum r^2, the pair count), for callers who combine terms.
+ * tsdf_fuse_volume_at: tsdf_fuse_volume with the first three rows of dst2src in place of M; rule, counts, summary rebuild and
+ * refusals are unchanged, and with tsdf_fuse_pose_default's matrix it equals tsdf_fuse_volume bit for bit.
+ * All three take the handles tsdf_fuse_volume takes and apply the collected frames of both first.  Queued as tsdf_fuse_volume
+ * queues its kernel; each returns when the result is on the host.  The align calls read both volumes only: not one bit of
+ * either changes.  Refused with TSDF_ERR_INVALID: everything tsdf_fuse_volume refuses about the handles; a src dim < 2; a
+ * weight_thresh that is not finite; a resid_thresh that is not finite or not > 0; n_levels outside 1..3; a negative iters[l]
+ * or min_pairs; an eps that is not finite or not > 0; a level outside [0, n_levels); a non-finite entry in the first three
+ * rows of a given pose; a NULL dst2src where it is not optional.
+ */
+typedef struct tsdf_align_params { float weight_thresh, resid_thresh; int32_t n_levels; int32_t iters[3];
+                                   int32_t min_pairs; float eps_rot, eps_trans; } tsdf_align_params;
+typedef struct tsdf_align_result { float dst2src[16]; int32_t status; int32_t iters_run[3]; int32_t pairs; float rmse; } tsdf_align_result;
+int tsdf_align_params_default(const tsdf_config *dst_cfg, tsdf_align_params *out);                 /* host arithmetic only */
+int tsdf_fuse_pose_default(const tsdf_config *dst_cfg, const tsdf_config *src_cfg, float dst2src[16]); /* the M tsdf_fuse_volume composes; host only */
+int tsdf_align_volume(tsdf_volume *dst, tsdf_volume *src, const tsdf_align_params *p,
+                      const float guess_dst2src[16] /* may be NULL */, tsdf_align_result *out);
+int tsdf_align_system(tsdf_volume *dst, tsdf_volume *src, const tsdf_align_params *p, const float dst2src[16],
+                      int32_t level, double system_out[29]);   /* one pass at the given pose, tsdf_track_system's layout */
+int tsdf_fuse_volume_at(tsdf_volume *dst, tsdf_volume *src, const tsdf_fuse_params *p, const float dst2src[16],
+                        tsdf_fuse_counts *counts /* may be NULL */);
+
+/*
  * Extent: what a fused volume holds -- how many voxels were observed, how many lie near a surface, where those are (sums,
  * second moments, index bounds) and how many of them sit against each face of the grid.  Three decisions of the per-object
  * loop read it: whether an object has outgrown the grid placed from its first frame (ref: src/Object.cpp:37-49 places it once;

@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "tsdf_track_params_default", "tsdf_track", "tsdf_track_system",
     "tsdf_batch_track", "tsdf_batch_track_system", "tsdf_track_member_systems",
     "tsdf_fuse_params_default", "tsdf_fuse_volume",
+    "tsdf_align_params_default", "tsdf_fuse_pose_default", "tsdf_align_volume", "tsdf_align_system", "tsdf_fuse_volume_at",
     "tsdf_extent_params_default", "tsdf_volume_extent", "tsdf_batch_extents", "tsdf_group_extent", "tsdf_extent_combine",
     "tsdf_extent_metric", "tsdf_extent_regrid",
     "tsdf_associate_params_default", "tsdf_associate_count", "tsdf_associate_assign", "tsdf_batch_associate",
@@ -119,6 +120,18 @@ class FuseParams(C.Structure):
 class FuseCounts(C.Structure):
     """Mirror of `struct tsdf_fuse_counts` (include/tsdf_hip.h)."""
     _fields_ = [("sampled", C.c_uint64), ("both", C.c_uint64), ("both_band", C.c_uint64), ("agree_band", C.c_uint64)]
+
+
+class AlignParams(C.Structure):
+    """Mirror of `struct tsdf_align_params` (include/tsdf_hip.h)."""
+    _fields_ = [("weight_thresh", C.c_float), ("resid_thresh", C.c_float), ("n_levels", C.c_int32), ("iters", C.c_int32 * 3),
+                ("min_pairs", C.c_int32), ("eps_rot", C.c_float), ("eps_trans", C.c_float)]
+
+
+class AlignResult(C.Structure):
+    """Mirror of `struct tsdf_align_result` (include/tsdf_hip.h)."""
+    _fields_ = [("dst2src", C.c_float * 16), ("status", C.c_int32), ("iters_run", C.c_int32 * 3), ("pairs", C.c_int32),
+                ("rmse", C.c_float)]
 
 
 class ExtentParams(C.Structure):
@@ -285,6 +298,11 @@ def load():
                                             C.c_int32, vp]
     L.tsdf_fuse_params_default.argtypes = [C.POINTER(TsdfConfig), C.POINTER(FuseParams)]
     L.tsdf_fuse_volume.argtypes = [vp, vp, C.POINTER(FuseParams), C.POINTER(FuseCounts)]
+    L.tsdf_align_params_default.argtypes = [C.POINTER(TsdfConfig), C.POINTER(AlignParams)]
+    L.tsdf_fuse_pose_default.argtypes = [C.POINTER(TsdfConfig), C.POINTER(TsdfConfig), vp]
+    L.tsdf_align_volume.argtypes = [vp, vp, C.POINTER(AlignParams), vp, C.POINTER(AlignResult)]
+    L.tsdf_align_system.argtypes = [vp, vp, C.POINTER(AlignParams), vp, C.c_int32, vp]
+    L.tsdf_fuse_volume_at.argtypes = [vp, vp, C.POINTER(FuseParams), vp, C.POINTER(FuseCounts)]
     L.tsdf_extent_params_default.argtypes = [C.POINTER(TsdfConfig), C.POINTER(ExtentParams)]
     L.tsdf_volume_extent.argtypes = [vp, C.POINTER(ExtentParams), C.POINTER(Extent)]
     L.tsdf_batch_extents.argtypes = [vp, C.POINTER(ExtentParams), C.POINTER(Extent)]
@@ -432,6 +450,22 @@ def fuse_params_default(cfg):
     p = FuseParams()
     check(load().tsdf_fuse_params_default(C.byref(cfg), C.byref(p)), "tsdf_fuse_params_default")
     return p
+
+
+def align_params_default(cfg):
+    """Registration parameters for a destination config (include/tsdf_hip.h): weight_thresh 0.9, resid_thresh 1.0, 2 levels,
+    iterations {10, 10, 0}, min_pairs 300, eps 1e-5 rad / 1e-5 m (no device)."""
+    p = AlignParams()
+    check(load().tsdf_align_params_default(C.byref(cfg), C.byref(p)), "tsdf_align_params_default")
+    return p
+
+
+def fuse_pose_default(dst_cfg, src_cfg):
+    """The pose tsdf_fuse_volume composes from two configs: inverse(base2world_src) * base2world_dst, float32 [16] (no
+    device)."""
+    out = np.empty(16, np.float32)
+    check(load().tsdf_fuse_pose_default(C.byref(dst_cfg), C.byref(src_cfg), out.ctypes.data), "tsdf_fuse_pose_default")
+    return out
 
 
 def extent_params_default(cfg):
@@ -971,15 +1005,47 @@ class Volume:
         return A, out[21:27].copy(), float(out[27]), int(out[28])
 
     # -- merging ----------------------------------------------------------------------------
-    def fuse_from(self, src, params=None):
+    def fuse_from(self, src, params=None, dst2src=None):
         """Merge the volume `src` into this one by trilinear resampling (csrc/tsdf_fuse.hip.h): every voxel of this grid
         samples src at its own position.  params: a FuseParams, default fuse_params_default(cfg); write = 0 compares only.
-        Returns the counts as a dict: sampled, both, both_band, agree_band."""
+        dst2src: the pose to sample through (16 float32, this grid's base frame to src's; tsdf_fuse_volume_at) in place of
+        the one the two base2world give.  Returns the counts as a dict: sampled, both, both_band, agree_band."""
         p = fuse_params_default(self.cfg) if params is None else params
         c = FuseCounts()
-        check(self.lib.tsdf_fuse_volume(self._h, src._h, C.byref(p), C.byref(c)), "tsdf_fuse_volume")
+        if dst2src is None:
+            check(self.lib.tsdf_fuse_volume(self._h, src._h, C.byref(p), C.byref(c)), "tsdf_fuse_volume")
+        else:
+            m = _f32(dst2src, 16)
+            check(self.lib.tsdf_fuse_volume_at(self._h, src._h, C.byref(p), m.ctypes.data, C.byref(c)), "tsdf_fuse_volume_at")
         return {"sampled": int(c.sampled), "both": int(c.both), "both_band": int(c.both_band),
                 "agree_band": int(c.agree_band)}
+
+    # -- registration -----------------------------------------------------------------------
+    def align_to(self, src, params=None, guess=None):
+        """Register this volume (the destination) against `src` (csrc/tsdf_align.hip.h).  Returns (dst2src [4, 4] float32,
+        status dict with status, status_name, iters_run, pairs, rmse); a lost run returns the start itself with status 2.
+        params: an AlignParams, default align_params_default(cfg); guess: the starting dst2src (16 float32), default the
+        pose the two base2world give (fuse_pose_default).  Reads both volumes only."""
+        p = align_params_default(self.cfg) if params is None else params
+        g = None if guess is None else _f32(guess, 16)
+        res = AlignResult()
+        check(self.lib.tsdf_align_volume(self._h, src._h, C.byref(p), None if g is None else g.ctypes.data, C.byref(res)),
+              "tsdf_align_volume")
+        pose = np.array(res.dst2src, np.float32).reshape(4, 4)
+        return pose, {"status": res.status, "status_name": TRACK_STATUS[res.status], "iters_run": list(res.iters_run),
+                      "pairs": res.pairs, "rmse": res.rmse}
+
+    def align_system(self, src, dst2src, level=0, params=None):
+        """The linear system of one registration pass at `level` and the pose dst2src: (A = J^T J [6, 6] float64,
+        b = J^T r [6], sum r^2, pair count)."""
+        p = align_params_default(self.cfg) if params is None else params
+        m = _f32(dst2src, 16)
+        out = np.zeros(29, np.float64)
+        check(self.lib.tsdf_align_system(self._h, src._h, C.byref(p), m.ctypes.data, level, out.ctypes.data), "tsdf_align_system")
+        A = np.zeros((6, 6))
+        A[np.triu_indices(6)] = out[:21]
+        A = A + np.triu(A, 1).T
+        return A, out[21:27].copy(), float(out[27]), int(out[28])
 
     # -- extent -----------------------------------------------------------------------------
     def extent(self, params=None):

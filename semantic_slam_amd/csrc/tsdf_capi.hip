@@ -1,8 +1,8 @@
 // tsdf_capi.hip -- implementation of include/tsdf_hip.h (libtsdf_hip.so).  Handles, integration, labels and colour are here;
-// batches, raycasting, tracking, merging, extents, association and segmentation each in a tsdf_<feature>_host.hip.h (the last
-// six beside their kernels), extraction, the file writers and the checkpoint calls in tsdf_extract_host.hip.h (the file formats
-// themselves in mesh_files.h, host-only), the group in tsdf_group.hip.h and include/tsdf_hip_diag.h in tsdf_diag.hip.h, all
-// included at the end (one translation unit).
+// batches, raycasting, tracking, merging, registration, extents, association and segmentation each in a
+// tsdf_<feature>_host.hip.h (the last seven beside their kernels), extraction, the file writers and the checkpoint calls in
+// tsdf_extract_host.hip.h (the file formats themselves in mesh_files.h, host-only), the group in tsdf_group.hip.h and
+// include/tsdf_hip_diag.h in tsdf_diag.hip.h, all included at the end (one translation unit).
 //
 // One handle = one z-slab of the voxel grid resident in HBM on one device + one HIP stream.
 // Host work per frame is the 4x4 pose composition (pose_math.h) and one kernel launch; the
@@ -42,6 +42,7 @@
 #include "tsdf_track.hip.h"
 #include "tsdf_batch_track.hip.h"
 #include "tsdf_fuse.hip.h"
+#include "tsdf_align.hip.h"
 #include "tsdf_extent.hip.h"
 #include "tsdf_associate.hip.h"
 #include "tsdf_segment.hip.h"
@@ -194,6 +195,12 @@ struct tsdf_volume {
     DevPtr<unsigned long long> d_fuse;
     HostPtr<unsigned long long> h_fuse;
     Event fuse_src_ready, fuse_done;
+    // registration (tsdf_align_* with this handle as the destination), allocated on first use, all or none: the partial rows of
+    // a pass and the pose state in one block of HBM, the state's pinned copy, and the two events of the merge's order; no size
+    // of either volume enters it, so one handle aligns against sources of any size in turn
+    DevPtr<char> d_align;
+    HostPtr<tsdfk::TrackState> h_align;
+    Event align_src_ready, align_done;
     // extent (tsdf_volume_extent), allocated on first use, both or neither: the record and behind it one partial record per
     // workgroup of the launch in HBM (the slab's dims fix their number); the record's pinned host copy
     DevPtr<unsigned long long> d_extent;
@@ -1653,6 +1660,7 @@ int tsdf_download_colour(tsdf_volume *v, uint32_t *colour_host)
 #include "tsdf_raycast_host.hip.h"
 #include "tsdf_track_host.hip.h"
 #include "tsdf_fuse_host.hip.h"
+#include "tsdf_align_host.hip.h"
 #include "tsdf_extent_host.hip.h"
 #include "tsdf_associate_host.hip.h"
 #include "tsdf_batch_track_host.hip.h"

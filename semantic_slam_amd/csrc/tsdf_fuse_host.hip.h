@@ -14,34 +14,45 @@ int fuse_handle_ok(const char *who, const char *side, const tsdf_volume *v)
     return TSDF_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int tsdf_fuse_params_default(const tsdf_config *dst_cfg, tsdf_fuse_params *out)
+// What every call that takes a destination and a source refuses about the two handles.
+int fuse_pair_ok(const char *who, const tsdf_volume *dst, const tsdf_volume *src)
 {
-    if (!dst_cfg || !out) return fail(TSDF_ERR_INVALID, "tsdf_fuse_params_default: NULL argument");
-    out->weight_thresh = 0.9f;
-    out->agree_tol = 0.4f;   // two voxels of the default band of five: a choice
-    out->write = 1;
-    return TSDF_OK;
-}
-
-int tsdf_fuse_volume(tsdf_volume *dst, tsdf_volume *src, const tsdf_fuse_params *p, tsdf_fuse_counts *counts)
-{
-    const char *who = "tsdf_fuse_volume";
-    if (!dst || !src || !p) return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
     if (dst == src) return fail(TSDF_ERR_INVALID, "%s: dst and src are the same handle", who);
     int rc = fuse_handle_ok(who, "dst", dst);
     if (rc == TSDF_OK) rc = fuse_handle_ok(who, "src", src);
     if (rc) return rc;
     if (dst->cfg.device != src->cfg.device)
         return fail(TSDF_ERR_INVALID, "%s: dst is on device %d, src on device %d", who, dst->cfg.device, src->cfg.device);
+    return TSDF_OK;
+}
+
+// What is queued next on dst's stream runs after everything queued on src's stream so far.
+int fuse_after_src(tsdf_volume *dst, tsdf_volume *src, hipEvent_t src_ready)
+{
+    if (src->stream == dst->stream) return TSDF_OK;
+    HIP_TRY(hipEventRecord(src_ready, src->stream));
+    HIP_TRY(hipStreamWaitEvent(dst->stream, src_ready, 0));
+    return TSDF_OK;
+}
+
+// A later write to src must not overtake the reads queued on dst's stream so far.
+int fuse_src_after(tsdf_volume *dst, tsdf_volume *src, hipEvent_t done)
+{
+    if (src->stream == dst->stream) return TSDF_OK;
+    HIP_TRY(hipEventRecord(done, dst->stream));
+    HIP_TRY(hipStreamWaitEvent(src->stream, done, 0));
+    return TSDF_OK;
+}
+
+// The body of tsdf_fuse_volume and tsdf_fuse_volume_at: the merge with the first three rows of M as the pose.
+int fuse_volume_with(const char *who, tsdf_volume *dst, tsdf_volume *src, const tsdf_fuse_params *p, const float M[16],
+                     tsdf_fuse_counts *counts)
+{
     if (!std::isfinite(p->weight_thresh)) return fail(TSDF_ERR_INVALID, "%s: weight_thresh is not finite", who);
     if (!std::isfinite(p->agree_tol) || !(p->agree_tol > 0.0f))
         return fail(TSDF_ERR_INVALID, "%s: agree_tol must be finite and > 0 (%g)", who, (double)p->agree_tol);
     if (p->write != 0 && p->write != 1) return fail(TSDF_ERR_INVALID, "%s: write must be 0 or 1 (%d)", who, p->write);
-    rc = bind_device(dst);               // the collected frames of both, through their batches where they have one
+    int rc = bind_device(dst);           // the collected frames of both, through their batches where they have one
     if (rc == TSDF_OK) rc = bind_device(src);
     if (rc) return rc;
     if (!dst->d_fuse) {                  // all four or none
@@ -56,8 +67,6 @@ int tsdf_fuse_volume(tsdf_volume *dst, tsdf_volume *src, const tsdf_fuse_params 
         dst->fuse_src_ready = std::move(ready); dst->fuse_done = std::move(done);
     }
     const tsdf_config &cd = dst->cfg, &cs = src->cfg;
-    float M[16];
-    tsdf_host::multiply_matrix(src->base2world_inv, cd.base2world, M);
     tsdfk::FuseParams k;
     k.dt = dst->d_tsdf; k.dw = dst->d_weight;
     k.st = src->d_tsdf; k.sw = src->d_weight;
@@ -74,10 +83,8 @@ int tsdf_fuse_volume(tsdf_volume *dst, tsdf_volume *src, const tsdf_fuse_params 
     k.write = p->write;
     k.counts = dst->d_fuse;
     HIP_TRY(hipMemsetAsync(dst->d_fuse, 0, 4 * sizeof(unsigned long long), dst->stream));
-    if (src->stream != dst->stream) {    // after everything queued on src's stream so far
-        HIP_TRY(hipEventRecord(dst->fuse_src_ready, src->stream));
-        HIP_TRY(hipStreamWaitEvent(dst->stream, dst->fuse_src_ready, 0));
-    }
+    rc = fuse_after_src(dst, src, dst->fuse_src_ready);
+    if (rc) return rc;
     const int quads = (cd.dim_x + 3) / 4;
     const dim3 grid((quads + 7) / 8, (cd.dim_y + 7) / 8, (cd.dim_z + 4 * tsdfk::kFuseZRun - 1) / (4 * tsdfk::kFuseZRun));
     if (cd.dim_x % 4 == 0)
@@ -85,10 +92,8 @@ int tsdf_fuse_volume(tsdf_volume *dst, tsdf_volume *src, const tsdf_fuse_params 
     else
         hipLaunchKernelGGL(tsdfk::fuse_volume<false>, grid, dim3(256), 0, dst->stream, k);
     HIP_TRY(hipGetLastError());
-    if (src->stream != dst->stream) {    // a later write to src must not overtake the read
-        HIP_TRY(hipEventRecord(dst->fuse_done, dst->stream));
-        HIP_TRY(hipStreamWaitEvent(src->stream, dst->fuse_done, 0));
-    }
+    rc = fuse_src_after(dst, src, dst->fuse_done);
+    if (rc) return rc;
     if (p->write) {                      // later fused / classified Integrate launches must not trust stale summary words
         rc = rebuild_summary(dst);
         if (rc) return rc;
@@ -102,6 +107,52 @@ int tsdf_fuse_volume(tsdf_volume *dst, tsdf_volume *src, const tsdf_fuse_params 
         counts->agree_band = dst->h_fuse.get()[3];
     }
     return TSDF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tsdf_fuse_params_default(const tsdf_config *dst_cfg, tsdf_fuse_params *out)
+{
+    if (!dst_cfg || !out) return fail(TSDF_ERR_INVALID, "tsdf_fuse_params_default: NULL argument");
+    out->weight_thresh = 0.9f;
+    out->agree_tol = 0.4f;   // two voxels of the default band of five: a choice
+    out->write = 1;
+    return TSDF_OK;
+}
+
+int tsdf_fuse_pose_default(const tsdf_config *dst_cfg, const tsdf_config *src_cfg, float dst2src[16])
+{
+    if (!dst_cfg || !src_cfg || !dst2src) return fail(TSDF_ERR_INVALID, "tsdf_fuse_pose_default: NULL argument");
+    float inv[16] = {};                  // a singular base2world_src: the all-zero inverse, as tsdf_create keeps it
+    tsdf_host::invert_matrix(src_cfg->base2world, inv);
+    tsdf_host::multiply_matrix(inv, dst_cfg->base2world, dst2src);
+    return TSDF_OK;
+}
+
+int tsdf_fuse_volume(tsdf_volume *dst, tsdf_volume *src, const tsdf_fuse_params *p, tsdf_fuse_counts *counts)
+{
+    const char *who = "tsdf_fuse_volume";
+    if (!dst || !src || !p) return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
+    const int rc = fuse_pair_ok(who, dst, src);
+    if (rc) return rc;
+    float M[16];
+    tsdf_host::multiply_matrix(src->base2world_inv, dst->cfg.base2world, M);
+    return fuse_volume_with(who, dst, src, p, M, counts);
+}
+
+int tsdf_fuse_volume_at(tsdf_volume *dst, tsdf_volume *src, const tsdf_fuse_params *p, const float dst2src[16],
+                        tsdf_fuse_counts *counts)
+{
+    const char *who = "tsdf_fuse_volume_at";
+    if (!dst || !src || !p) return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
+    if (!dst2src) return fail(TSDF_ERR_INVALID, "%s: NULL dst2src", who);
+    const int rc = fuse_pair_ok(who, dst, src);
+    if (rc) return rc;
+    for (int i = 0; i < 12; ++i)
+        if (!std::isfinite(dst2src[i])) return fail(TSDF_ERR_INVALID, "%s: dst2src[%d] is not finite", who, i);
+    return fuse_volume_with(who, dst, src, p, dst2src, counts);
 }
 
 }  // extern "C"
