@@ -431,7 +431,8 @@ int tsdf_track_system(tsdf_volume *vol, const tsdf_track_params *p, const float 
  *   sampled      all of them                       both_band    of both, |dst tsdf| < 1 and |sample| < 1 (near a surface in both)
  *   both         of those, dst weight > thresh     agree_band   of both_band, |dst tsdf - sample| <= agree_tol
  * Whether two volumes show the same object is the caller's decision from agree_band / both_band; the library makes none.
- * Deviation: labels and colours of dst are neither read nor written.  src is only read.
+ * Deviation: labels and colours of dst are neither read nor written.  src is only read.  tsdf_fuse_volume_carry (below) is the
+ * same merge that also carries them.
  * Results are specified bit for bit (tests/fuse_spec.py), with one exception: where dst already held a NaN, an infinity or a
  * weight that is not positive the update can yield a NaN, and which NaN (sign, payload) is the hardware's choice; such a voxel
  * is specified as "a NaN".  A valid sample is always finite, so a dst of finite values and weights >= 0 never gets one.
@@ -496,6 +497,43 @@ int tsdf_align_system(tsdf_volume *dst, tsdf_volume *src, const tsdf_align_param
                       int32_t level, double system_out[29]);   /* one pass at the given pose, tsdf_track_system's layout */
 int tsdf_fuse_volume_at(tsdf_volume *dst, tsdf_volume *src, const tsdf_fuse_params *p, const float dst2src[16],
                         tsdf_fuse_counts *counts /* may be NULL */);
+
+/*
+ * The merge that carries colour and labels, and the uploads of both.  tsdf_fuse_volume and tsdf_fuse_volume_at move the TSDF
+ * and the weights only: a re-gridded object would come out black and unlabelled, and a merged duplicate would lose the
+ * source's votes.  tsdf_fuse_volume_carry does everything those two do -- the TSDF, the weights and the four counts equal
+ * tsdf_fuse_volume (dst2src NULL) or tsdf_fuse_volume_at bit for bit, and with carry == 0 the call is that call -- and the
+ * destination voxels the merge updates (counts->sampled of them) also take what `carry` names.  The rule is stated exactly in
+ * csrc/tsdf_fuse_carry.hip.h and restated in tests/fuse_carry_spec.py.
+ *   TSDF_FUSE_CARRY_COLOUR   per 8-bit channel the source's colour, interpolated over the same 8 corners with the same
+ *                            fractions, is blended in with the merge's own weights: round((c_dst * w_dst + c_src * w_src) /
+ *                            (w_dst + w_src)) clamped to 0..255, with w_dst dst's weight BEFORE the merge and w_src the
+ *                            sample's; a voxel with w_dst == 0 takes the interpolated colour itself.  Only with write = 1.
+ *   TSDF_FUSE_CARRY_LABELS   the nearest source voxel (per axis the upper corner from a fraction of 0.5) is one observation of
+ *                            its label L with score Fp, folded in by tsdf_integrate_labels_device's rule and dst's
+ *                            prob_threshold: a source label 0 changes nothing; an unlabelled dst voxel takes (L, Fp, Bp);
+ *                            an equal label adds Fp to Fp and Bp to Bp; another label adds the source's Fp to dst's Bp and,
+ *                            if Fp / (Fp + Bp) then falls below the threshold, dst takes (L, Fp, Bp).
+ * carry_counts, over the updated voxels whose source label is not 0: label_adopted, label_agreed, label_opposed and, of the
+ * opposed, label_flipped.  Taken with write = 0 too (not one bit of dst is written then); all zero without the labels bit.
+ * tsdf_upload_labels / tsdf_upload_colour mirror tsdf_download_labels / tsdf_download_colour: tsdf_slab_voxels() elements per
+ * array, the collected frames applied first, as tsdf_upload does; all pointers are required.
+ * tsdf_fuse_volume_carry takes the handles tsdf_fuse_volume takes and applies the collected frames of both first.  Queued as
+ * tsdf_fuse_volume queues its kernel; returns when the counts are on the host.  src is only read.  Refused with
+ * TSDF_ERR_INVALID: everything tsdf_fuse_volume_at refuses, except that a NULL dst2src means the M tsdf_fuse_volume composes;
+ * carry with bits outside 3; colour asked for while colour is not enabled on dst or on src, labels likewise (the message
+ * names the side).  The uploads refuse a NULL argument and an attribute that is not enabled.
+ * Out of scope: a z-slab or tsdf_group handle on either side; labels and colour in tsdf_save_state; a trilinear or majority
+ * label vote; counts of colour agreement.
+ */
+#define TSDF_FUSE_CARRY_COLOUR 1u
+#define TSDF_FUSE_CARRY_LABELS 2u
+typedef struct tsdf_fuse_carry_counts { uint64_t label_adopted, label_agreed, label_opposed, label_flipped; } tsdf_fuse_carry_counts;
+int tsdf_fuse_volume_carry(tsdf_volume *dst, tsdf_volume *src, const tsdf_fuse_params *p,
+                           const float dst2src[16] /* NULL: the M tsdf_fuse_volume composes */, uint32_t carry,
+                           tsdf_fuse_counts *counts /* may be NULL */, tsdf_fuse_carry_counts *carry_counts /* may be NULL */);
+int tsdf_upload_labels(tsdf_volume *vol, const uint16_t *label_host, const float *fp_host, const float *bp_host);
+int tsdf_upload_colour(tsdf_volume *vol, const uint32_t *colour_host);
 
 /*
  * Extent: what a fused volume holds -- how many voxels were observed, how many lie near a surface, where those are (sums,

@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "tsdf_batch_track", "tsdf_batch_track_system", "tsdf_track_member_systems",
     "tsdf_fuse_params_default", "tsdf_fuse_volume",
     "tsdf_align_params_default", "tsdf_fuse_pose_default", "tsdf_align_volume", "tsdf_align_system", "tsdf_fuse_volume_at",
+    "tsdf_fuse_volume_carry", "tsdf_upload_labels", "tsdf_upload_colour",
     "tsdf_extent_params_default", "tsdf_volume_extent", "tsdf_batch_extents", "tsdf_group_extent", "tsdf_extent_combine",
     "tsdf_extent_metric", "tsdf_extent_regrid",
     "tsdf_associate_params_default", "tsdf_associate_count", "tsdf_associate_assign", "tsdf_batch_associate",
@@ -120,6 +121,15 @@ class FuseParams(C.Structure):
 class FuseCounts(C.Structure):
     """Mirror of `struct tsdf_fuse_counts` (include/tsdf_hip.h)."""
     _fields_ = [("sampled", C.c_uint64), ("both", C.c_uint64), ("both_band", C.c_uint64), ("agree_band", C.c_uint64)]
+
+
+FUSE_CARRY_COLOUR, FUSE_CARRY_LABELS = 1, 2      # TSDF_FUSE_CARRY_* (include/tsdf_hip.h)
+
+
+class FuseCarryCounts(C.Structure):
+    """Mirror of `struct tsdf_fuse_carry_counts` (include/tsdf_hip.h)."""
+    _fields_ = [("label_adopted", C.c_uint64), ("label_agreed", C.c_uint64), ("label_opposed", C.c_uint64),
+                ("label_flipped", C.c_uint64)]
 
 
 class AlignParams(C.Structure):
@@ -303,6 +313,11 @@ def load():
     L.tsdf_align_volume.argtypes = [vp, vp, C.POINTER(AlignParams), vp, C.POINTER(AlignResult)]
     L.tsdf_align_system.argtypes = [vp, vp, C.POINTER(AlignParams), vp, C.c_int32, vp]
     L.tsdf_fuse_volume_at.argtypes = [vp, vp, C.POINTER(FuseParams), vp, C.POINTER(FuseCounts)]
+    if hasattr(L, "tsdf_fuse_volume_carry"):    # (an earlier build loaded through TSDF_HIP_LIB for an A/B has none)
+        L.tsdf_fuse_volume_carry.argtypes = [vp, vp, C.POINTER(FuseParams), vp, C.c_uint32, C.POINTER(FuseCounts),
+                                             C.POINTER(FuseCarryCounts)]
+        L.tsdf_upload_labels.argtypes = [vp, vp, vp, vp]
+        L.tsdf_upload_colour.argtypes = [vp, vp]
     L.tsdf_extent_params_default.argtypes = [C.POINTER(TsdfConfig), C.POINTER(ExtentParams)]
     L.tsdf_volume_extent.argtypes = [vp, C.POINTER(ExtentParams), C.POINTER(Extent)]
     L.tsdf_batch_extents.argtypes = [vp, C.POINTER(ExtentParams), C.POINTER(Extent)]
@@ -928,6 +943,14 @@ class Volume:
         check(self.lib.tsdf_download_labels(self._h, lab.ctypes.data, fp.ctypes.data, bp.ctypes.data), "tsdf_download_labels")
         return lab, fp, bp
 
+    def upload_labels(self, label, fp, bp):
+        n = self.n_voxels
+        lab = np.ascontiguousarray(label, np.uint16).ravel()
+        if lab.size != n:
+            raise ValueError(f"expected {n} labels, got {lab.size}")
+        f, b = _f32(fp, n), _f32(bp, n)
+        check(self.lib.tsdf_upload_labels(self._h, lab.ctypes.data, f.ctypes.data, b.ctypes.data), "tsdf_upload_labels")
+
     # -- per-voxel colour fusion ----------------------------------------------------------------
     def colour_enable(self):
         check(self.lib.tsdf_colour_enable(self._h), "tsdf_colour_enable")
@@ -949,6 +972,12 @@ class Volume:
         out = np.empty(self.n_voxels, np.uint32)
         check(self.lib.tsdf_download_colour(self._h, out.ctypes.data), "tsdf_download_colour")
         return out
+
+    def upload_colour(self, colour):
+        c = np.ascontiguousarray(colour, np.uint32).ravel()
+        if c.size != self.n_voxels:
+            raise ValueError(f"expected {self.n_voxels} colours, got {c.size}")
+        check(self.lib.tsdf_upload_colour(self._h, c.ctypes.data), "tsdf_upload_colour")
 
     # -- raycasting -------------------------------------------------------------------------
     def raycast(self, cam2world, params=None, normals=True, labels=False, colour=False):
@@ -1005,13 +1034,25 @@ class Volume:
         return A, out[21:27].copy(), float(out[27]), int(out[28])
 
     # -- merging ----------------------------------------------------------------------------
-    def fuse_from(self, src, params=None, dst2src=None):
+    def fuse_from(self, src, params=None, dst2src=None, carry=0):
         """Merge the volume `src` into this one by trilinear resampling (csrc/tsdf_fuse.hip.h): every voxel of this grid
         samples src at its own position.  params: a FuseParams, default fuse_params_default(cfg); write = 0 compares only.
         dst2src: the pose to sample through (16 float32, this grid's base frame to src's; tsdf_fuse_volume_at) in place of
-        the one the two base2world give.  Returns the counts as a dict: sampled, both, both_band, agree_band."""
+        the one the two base2world give.  Returns the counts as a dict: sampled, both, both_band, agree_band.
+        carry: FUSE_CARRY_COLOUR | FUSE_CARRY_LABELS -- the updated voxels also take src's colour and / or label evidence
+        (tsdf_fuse_volume_carry, csrc/tsdf_fuse_carry.hip.h); the dict then also holds label_adopted, label_agreed,
+        label_opposed and label_flipped."""
         p = fuse_params_default(self.cfg) if params is None else params
         c = FuseCounts()
+        if carry:
+            m = None if dst2src is None else _f32(dst2src, 16)
+            cc = FuseCarryCounts()
+            check(self.lib.tsdf_fuse_volume_carry(self._h, src._h, C.byref(p), None if m is None else m.ctypes.data, carry,
+                                                  C.byref(c), C.byref(cc)), "tsdf_fuse_volume_carry")
+            return {"sampled": int(c.sampled), "both": int(c.both), "both_band": int(c.both_band),
+                    "agree_band": int(c.agree_band), "label_adopted": int(cc.label_adopted),
+                    "label_agreed": int(cc.label_agreed), "label_opposed": int(cc.label_opposed),
+                    "label_flipped": int(cc.label_flipped)}
         if dst2src is None:
             check(self.lib.tsdf_fuse_volume(self._h, src._h, C.byref(p), C.byref(c)), "tsdf_fuse_volume")
         else:

@@ -42,6 +42,7 @@
 #include "tsdf_track.hip.h"
 #include "tsdf_batch_track.hip.h"
 #include "tsdf_fuse.hip.h"
+#include "tsdf_fuse_carry.hip.h"
 #include "tsdf_align.hip.h"
 #include "tsdf_extent.hip.h"
 #include "tsdf_associate.hip.h"
@@ -190,8 +191,8 @@ struct tsdf_volume {
     // rows of an association pass and the pose state, in one block; the state's pinned host copy
     DevBuf<char> d_track;
     HostPtr<tsdfk::TrackState> h_track;
-    // merging (tsdf_fuse_volume with this handle as the destination), allocated on first use, all or none: the four counts in
-    // HBM and pinned; src_ready is recorded on the source's stream before the kernel, done on this handle's stream after it
+    // merging (tsdf_fuse_volume* with this handle as the destination), allocated on first use, all or none: the eight counts
+    // (four of the merge, four of the labels carried: tsdf_fuse_volume_carry) in HBM and pinned; src_ready is recorded on the source's stream before the kernel, done on this handle's stream after it
     DevPtr<unsigned long long> d_fuse;
     HostPtr<unsigned long long> h_fuse;
     Event fuse_src_ready, fuse_done;
@@ -1573,6 +1574,21 @@ int tsdf_download_labels(tsdf_volume *v, uint16_t *label_host, float *fp_host, f
     return TSDF_OK;
 }
 
+int tsdf_upload_labels(tsdf_volume *v, const uint16_t *label_host, const float *fp_host, const float *bp_host)
+{
+    if (!v || !label_host || !fp_host || !bp_host) return fail(TSDF_ERR_INVALID, "tsdf_upload_labels: NULL argument");
+    if (!v->d_label) return fail(TSDF_ERR_INVALID, "tsdf_upload_labels: labels not enabled");
+    int rc = bind_device(v);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(v->stream));
+    const size_t n = (size_t)v->geo.n_vox;
+    if (n == 0) return TSDF_OK;
+    HIP_TRY(hipMemcpy(v->d_label, label_host, n * sizeof(uint16_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(v->d_fp, fp_host, n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(v->d_bp, bp_host, n * sizeof(float), hipMemcpyHostToDevice));
+    return TSDF_OK;
+}
+
 int tsdf_compose_labels(tsdf_volume *v, const uint8_t *masks_dev, const uint16_t *labels_host, const float *scores_host,
                         int32_t k, uint16_t *label_im_dev, float *score_im_dev)
 {
@@ -1651,6 +1667,17 @@ int tsdf_download_colour(tsdf_volume *v, uint32_t *colour_host)
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(v->stream));
     if (v->geo.n_vox > 0) HIP_TRY(hipMemcpy(colour_host, v->d_colour, (size_t)v->geo.n_vox * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return TSDF_OK;
+}
+
+int tsdf_upload_colour(tsdf_volume *v, const uint32_t *colour_host)
+{
+    if (!v || !colour_host) return fail(TSDF_ERR_INVALID, "tsdf_upload_colour: NULL argument");
+    if (!v->d_colour) return fail(TSDF_ERR_INVALID, "tsdf_upload_colour: colour not enabled");
+    int rc = bind_device(v);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(v->stream));
+    if (v->geo.n_vox > 0) HIP_TRY(hipMemcpy(v->d_colour, colour_host, (size_t)v->geo.n_vox * sizeof(uint32_t), hipMemcpyHostToDevice));
     return TSDF_OK;
 }
 

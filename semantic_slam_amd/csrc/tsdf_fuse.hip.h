@@ -37,8 +37,8 @@
 //            differs between gfx950 and a host CPU; such a result is specified as "a NaN", every other result by its bits.
 //
 // DEVIATIONS.  Not a reference function: the reference never moves an object's TSDF (ref: src/Object.cpp:37-49 places the
-// grid once, from the first masked frame).  Labels and colours of the destination are neither read nor written: label
-// evidence (Fp, Bp) and the colour mean have no weight the sample could be folded in with.  The source is only read.
+// grid once, from the first masked frame).  Labels and colours of the destination are neither read nor written by this
+// kernel; tsdf_fuse_carry.hip.h carries them, in a kernel queued ahead of this one.  The source is only read.
 //
 // MAPPING.  One lane per four x-adjacent destination voxels; a wavefront covers 8 such quads by 8 rows of one slice (32 x 8
 // voxels: the 64 lanes' gathers fall into a few neighbouring source rows and meet in L1 / L2) and walks kFuseZRun slices,
@@ -72,12 +72,28 @@ struct FuseParams {
     unsigned long long *counts;  // sampled, both, both_band, agree_band
 };
 
+// The source cell of a position already known to lie inside the source box: lower corner j, upper corner k, fractions f.
+// tsdf_fuse_carry.hip.h gathers colours and labels from the same cell.
+struct FuseCell {
+    int j0, j1, j2, k0, k1, k2;
+    float f0, f1, f2;
+};
+
+__device__ __forceinline__ FuseCell fuse_cell(float g0, float g1, float g2)
+{
+    FuseCell c;
+    c.j0 = (int)floorf(g0); c.j1 = (int)floorf(g1); c.j2 = (int)floorf(g2);
+    c.f0 = g0 - (float)c.j0; c.f1 = g1 - (float)c.j1; c.f2 = g2 - (float)c.j2;
+    c.k0 = c.f0 > 0.0f ? c.j0 + 1 : c.j0; c.k1 = c.f1 > 0.0f ? c.j1 + 1 : c.j1; c.k2 = c.f2 > 0.0f ? c.j2 + 1 : c.j2;
+    return c;
+}
+
 // F and w_s at a position already known to lie inside the source box; true = the sample is valid.
 __device__ __forceinline__ bool fuse_sample(const FuseParams &P, float g0, float g1, float g2, float &F, float &ws)
 {
-    const int j0 = (int)floorf(g0), j1 = (int)floorf(g1), j2 = (int)floorf(g2);
-    const float f0 = g0 - (float)j0, f1 = g1 - (float)j1, f2 = g2 - (float)j2;
-    const int k0 = f0 > 0.0f ? j0 + 1 : j0, k1 = f1 > 0.0f ? j1 + 1 : j1, k2 = f2 > 0.0f ? j2 + 1 : j2;
+    const FuseCell cell = fuse_cell(g0, g1, g2);
+    const int j0 = cell.j0, j1 = cell.j1, j2 = cell.j2, k0 = cell.k0, k1 = cell.k1, k2 = cell.k2;
+    const float f0 = cell.f0, f1 = cell.f1, f2 = cell.f2;
     const int64_t sy = P.sdim[0], sz = (int64_t)P.sdim[0] * P.sdim[1];
     const int64_t r00 = j2 * sz + j1 * sy, r10 = j2 * sz + k1 * sy, r01 = k2 * sz + j1 * sy, r11 = k2 * sz + k1 * sy;
     const float *t = P.st, *w = P.sw;

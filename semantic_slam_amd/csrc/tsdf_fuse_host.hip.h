@@ -1,5 +1,5 @@
 // tsdf_fuse_host.hip.h -- host side of merging and re-gridding (include/tsdf_hip.h: tsdf_fuse_*), included at the end of
-// tsdf_capi.hip; tsdf_fuse.hip.h states the rule.
+// tsdf_capi.hip; tsdf_fuse.hip.h states the rule, tsdf_fuse_carry.hip.h that of the colours and labels carried along.
 #pragma once
 
 namespace {
@@ -44,9 +44,13 @@ int fuse_src_after(tsdf_volume *dst, tsdf_volume *src, hipEvent_t done)
     return TSDF_OK;
 }
 
-// The body of tsdf_fuse_volume and tsdf_fuse_volume_at: the merge with the first three rows of M as the pose.
+constexpr int kFuseWords = 8;   // the merge's four counts, then the four of the labels carried
+
+// The body of tsdf_fuse_volume, tsdf_fuse_volume_at and tsdf_fuse_volume_carry: the merge with the first three rows of M as the
+// pose.  carry (TSDF_FUSE_CARRY_*; the caller has checked that both handles hold what it names): the attributes' kernel is
+// queued ahead of the merge's, so it reads the weights the merge is about to replace.
 int fuse_volume_with(const char *who, tsdf_volume *dst, tsdf_volume *src, const tsdf_fuse_params *p, const float M[16],
-                     tsdf_fuse_counts *counts)
+                     tsdf_fuse_counts *counts, uint32_t carry = 0, tsdf_fuse_carry_counts *carry_counts = nullptr)
 {
     if (!std::isfinite(p->weight_thresh)) return fail(TSDF_ERR_INVALID, "%s: weight_thresh is not finite", who);
     if (!std::isfinite(p->agree_tol) || !(p->agree_tol > 0.0f))
@@ -59,8 +63,8 @@ int fuse_volume_with(const char *who, tsdf_volume *dst, tsdf_volume *src, const 
         DevPtr<unsigned long long> d;
         HostPtr<unsigned long long> h;
         Event ready, done;
-        HIP_TRY(dev_alloc(d, 4 * sizeof(unsigned long long)));
-        HIP_TRY(host_alloc(h, 4 * sizeof(unsigned long long), hipHostMallocDefault));
+        HIP_TRY(dev_alloc(d, kFuseWords * sizeof(unsigned long long)));
+        HIP_TRY(host_alloc(h, kFuseWords * sizeof(unsigned long long), hipHostMallocDefault));
         HIP_TRY(event_create(ready));
         HIP_TRY(event_create(done));
         dst->d_fuse = std::move(d); dst->h_fuse = std::move(h);
@@ -82,11 +86,29 @@ int fuse_volume_with(const char *who, tsdf_volume *dst, tsdf_volume *src, const 
     k.wthr = p->weight_thresh; k.tol = p->agree_tol;
     k.write = p->write;
     k.counts = dst->d_fuse;
-    HIP_TRY(hipMemsetAsync(dst->d_fuse, 0, 4 * sizeof(unsigned long long), dst->stream));
+    HIP_TRY(hipMemsetAsync(dst->d_fuse, 0, kFuseWords * sizeof(unsigned long long), dst->stream));
     rc = fuse_after_src(dst, src, dst->fuse_src_ready);
     if (rc) return rc;
     const int quads = (cd.dim_x + 3) / 4;
     const dim3 grid((quads + 7) / 8, (cd.dim_y + 7) / 8, (cd.dim_z + 4 * tsdfk::kFuseZRun - 1) / (4 * tsdfk::kFuseZRun));
+    const bool colour = (carry & TSDF_FUSE_CARRY_COLOUR) && p->write;   // colour has no counts: a dry run has nothing to do
+    const bool labels = (carry & TSDF_FUSE_CARRY_LABELS) != 0;
+    if (colour || labels) {              // (handles with either attribute have dim_x % 4 == 0: tsdf_*_enable)
+        tsdfk::FuseCarryParams c;
+        c.g = k;
+        c.dcol = dst->d_colour; c.scol = src->d_colour;
+        c.dlab = dst->d_label; c.dfp = dst->d_fp; c.dbp = dst->d_bp;
+        c.slab = src->d_label; c.sfp = src->d_fp; c.sbp = src->d_bp;
+        c.prob_thd = dst->prob_thd;
+        c.counts = dst->d_fuse + 4;
+        if (colour && labels)
+            hipLaunchKernelGGL((tsdfk::fuse_carry<true, true>), grid, dim3(256), 0, dst->stream, c);
+        else if (colour)
+            hipLaunchKernelGGL((tsdfk::fuse_carry<true, false>), grid, dim3(256), 0, dst->stream, c);
+        else
+            hipLaunchKernelGGL((tsdfk::fuse_carry<false, true>), grid, dim3(256), 0, dst->stream, c);
+        HIP_TRY(hipGetLastError());
+    }
     if (cd.dim_x % 4 == 0)
         hipLaunchKernelGGL(tsdfk::fuse_volume<true>, grid, dim3(256), 0, dst->stream, k);
     else
@@ -98,13 +120,19 @@ int fuse_volume_with(const char *who, tsdf_volume *dst, tsdf_volume *src, const 
         rc = rebuild_summary(dst);
         if (rc) return rc;
     }
-    HIP_TRY(hipMemcpyAsync(dst->h_fuse.get(), dst->d_fuse, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, dst->stream));
+    HIP_TRY(hipMemcpyAsync(dst->h_fuse.get(), dst->d_fuse, kFuseWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, dst->stream));
     HIP_TRY(hipStreamSynchronize(dst->stream));
     if (counts) {
         counts->sampled = dst->h_fuse.get()[0];
         counts->both = dst->h_fuse.get()[1];
         counts->both_band = dst->h_fuse.get()[2];
         counts->agree_band = dst->h_fuse.get()[3];
+    }
+    if (carry_counts) {
+        carry_counts->label_adopted = dst->h_fuse.get()[4];
+        carry_counts->label_agreed = dst->h_fuse.get()[5];
+        carry_counts->label_opposed = dst->h_fuse.get()[6];
+        carry_counts->label_flipped = dst->h_fuse.get()[7];
     }
     return TSDF_OK;
 }
@@ -153,6 +181,33 @@ int tsdf_fuse_volume_at(tsdf_volume *dst, tsdf_volume *src, const tsdf_fuse_para
     for (int i = 0; i < 12; ++i)
         if (!std::isfinite(dst2src[i])) return fail(TSDF_ERR_INVALID, "%s: dst2src[%d] is not finite", who, i);
     return fuse_volume_with(who, dst, src, p, dst2src, counts);
+}
+
+int tsdf_fuse_volume_carry(tsdf_volume *dst, tsdf_volume *src, const tsdf_fuse_params *p, const float dst2src[16],
+                           uint32_t carry, tsdf_fuse_counts *counts, tsdf_fuse_carry_counts *carry_counts)
+{
+    const char *who = "tsdf_fuse_volume_carry";
+    if (!dst || !src || !p) return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
+    const int rc = fuse_pair_ok(who, dst, src);
+    if (rc) return rc;
+    if (carry & ~(TSDF_FUSE_CARRY_COLOUR | TSDF_FUSE_CARRY_LABELS))
+        return fail(TSDF_ERR_INVALID, "%s: carry has bits outside TSDF_FUSE_CARRY_COLOUR | TSDF_FUSE_CARRY_LABELS (%u)", who, carry);
+    if (carry & TSDF_FUSE_CARRY_COLOUR) {
+        if (!dst->d_colour) return fail(TSDF_ERR_INVALID, "%s: colour is not enabled on dst (tsdf_colour_enable)", who);
+        if (!src->d_colour) return fail(TSDF_ERR_INVALID, "%s: colour is not enabled on src (tsdf_colour_enable)", who);
+    }
+    if (carry & TSDF_FUSE_CARRY_LABELS) {
+        if (!dst->d_label) return fail(TSDF_ERR_INVALID, "%s: labels are not enabled on dst (tsdf_labels_enable)", who);
+        if (!src->d_label) return fail(TSDF_ERR_INVALID, "%s: labels are not enabled on src (tsdf_labels_enable)", who);
+    }
+    float M[16];
+    if (dst2src) {
+        for (int i = 0; i < 12; ++i)
+            if (!std::isfinite(dst2src[i])) return fail(TSDF_ERR_INVALID, "%s: dst2src[%d] is not finite", who, i);
+    } else {
+        tsdf_host::multiply_matrix(src->base2world_inv, dst->cfg.base2world, M);
+    }
+    return fuse_volume_with(who, dst, src, p, dst2src ? dst2src : M, counts, carry, carry_counts);
 }
 
 }  // extern "C"
