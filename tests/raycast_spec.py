@@ -7,11 +7,15 @@ bit for bit.  Vectorised over rays: the march advances all rays that are still a
 
 tsdf / weight: flat x-fastest float32 arrays of the whole grid; pixels: None (every pixel, row-major) or an int array [n, 2] of
 (u, v).  Returns a dict of "depth" [n], "normal" [n, 3], "hit" [n] bool, "samples" [n] (samples taken per ray), and "label" /
-"colour" [n] when those arrays are given.
+"colour" [n] when those arrays are given.  With report=True it also says how each ray ended and what its set-up was: "end" [n]
+(an index into END), "go" [3], "gd" [n, 3], "gd_zero" [n, 3] (gd_i == 0), "touch" [n] (t_enter == t_exit on a ray that passed the
+set-up), "t_enter" / "t_exit" [n], "g_hit" [n, 3] (g* of the rule), and "trace": the march's samples as "t", "F" [k, n] float32 and "valid" [k, n] bool (rows past a ray's last sample
+hold NaN / False).  The report reads the arithmetic; it takes no part in it.
 """
 import numpy as np
 
 f32 = np.float32
+END = ("setup_miss", "hit", "exit", "stall", "cap")
 
 
 def max_steps(dims):
@@ -22,7 +26,8 @@ def pose_parts(cam2base, origin, vs):
     """R [3, 3], go [3] of the rule (go = (T - origin) / vs, float32)."""
     c = np.asarray(cam2base, f32).reshape(4, 4)
     R = np.ascontiguousarray(c[:3, :3])
-    go = (c[:3, 3] - np.asarray(origin, f32)) / f32(vs)
+    with np.errstate(invalid="ignore", over="ignore"):                        # a go that is not finite is a miss, by the rule
+        go = (c[:3, 3] - np.asarray(origin, f32)) / f32(vs)
     return R, go.astype(f32)
 
 
@@ -58,7 +63,7 @@ def sample(tsdf, weight, dims, wthr, g):
 
 
 def render(tsdf, weight, dims, origin, vs, trunc, K, hw, near, far, weight_thresh, cam2base, pixels=None, label=None,
-           colour=None):
+           colour=None, report=False):
     tsdf = np.ascontiguousarray(tsdf, f32).ravel()
     weight = np.ascontiguousarray(weight, f32).ravel()
     dims = [int(d) for d in dims]
@@ -106,6 +111,8 @@ def render(tsdf, weight, dims, origin, vs, trunc, K, hw, near, far, weight_thres
     hit = np.zeros(n, bool)
     ts = np.zeros(n, f32)
     samples = np.zeros(n, np.int64)
+    end = np.where(ok, END.index("cap"), END.index("setup_miss"))      # a ray still active after the last sample met the cap
+    trace = {"t": [], "F": [], "valid": []}
     for _ in range(max_steps(dims)):
         idx = np.nonzero(active)[0]
         if idx.size == 0:
@@ -115,12 +122,18 @@ def render(tsdf, weight, dims, origin, vs, trunc, K, hw, near, far, weight_thres
             g = np.stack([go[i] + tt * gd[i, idx] for i in range(3)])
         valid, F = sample(tsdf, weight, dims, wthr, g)
         samples[idx] += 1
+        if report:
+            for key, val, fill in (("t", tt, np.nan), ("F", F, np.nan), ("valid", valid, False)):
+                row = np.full(n, fill, val.dtype)
+                row[idx] = val
+                trace[key].append(row)
         h = valid & prev_valid[idx] & (F_prev[idx] > f32(0)) & (F <= f32(0))
         hi_idx = idx[h]
         fp, tp = F_prev[hi_idx], t_prev[hi_idx]
         ts[hi_idx] = tp + (tt[h] - tp) * (fp / (fp - F[h]))
         hit[hi_idx] = True
         active[hi_idx] = False
+        end[hi_idx] = END.index("hit")
         go_on = ~h
         idx, tt, valid, F = idx[go_on], tt[go_on], valid[go_on], F[go_on]
         with np.errstate(invalid="ignore", over="ignore"):
@@ -128,6 +141,7 @@ def render(tsdf, weight, dims, origin, vs, trunc, K, hw, near, far, weight_thres
             tn = tt + step * r[idx]
         stall = ~(tn > tt)
         active[idx[stall]] = False
+        end[idx[stall]] = END.index("stall")
         keep = ~stall
         idx, tt, valid, F, tn = idx[keep], tt[keep], valid[keep], F[keep], tn[keep]
         t_prev[idx] = tt
@@ -135,10 +149,17 @@ def render(tsdf, weight, dims, origin, vs, trunc, K, hw, near, far, weight_thres
         prev_valid[idx] = valid
         t[idx] = tn
         active[idx[~(tn <= t_exit[idx])]] = False
+        end[idx[~(tn <= t_exit[idx])]] = END.index("exit")
 
     out = {"hit": hit, "samples": samples, "depth": np.where(hit, ts, f32(0)).astype(f32)}
     with np.errstate(invalid="ignore", over="ignore"):
         gs = np.stack([go[i] + ts * gd[i] for i in range(3)])
+    if report:
+        with np.errstate(invalid="ignore"):
+            out.update(end=end, go=go, gd=gd.T, gd_zero=(gd == f32(0)).T, touch=ok & (t_enter == t_exit), t_enter=t_enter,
+                       t_exit=t_exit, g_hit=gs.T,
+                       trace={k: np.stack(v) if v else np.zeros((0, n), bool if k == "valid" else f32)
+                              for k, v in trace.items()})
     normal = np.zeros((n, 3), f32)
     hidx = np.nonzero(hit)[0]
     if hidx.size:
@@ -154,7 +175,7 @@ def render(tsdf, weight, dims, origin, vs, trunc, K, hw, near, far, weight_thres
             okn &= vp & vq
             with np.errstate(invalid="ignore", over="ignore"):
                 nn.append(Fp - Fq)
-        with np.errstate(invalid="ignore", over="ignore"):
+        with np.errstate(invalid="ignore", over="ignore", divide="ignore"):   # len == 0: m / len is computed and dropped
             m = [(R[0, j] * nn[0] + R[1, j] * nn[1]) + R[2, j] * nn[2] for j in range(3)]
             ln = np.sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2])
             okn &= np.isfinite(ln) & (ln > f32(0))
@@ -177,11 +198,12 @@ def render(tsdf, weight, dims, origin, vs, trunc, K, hw, near, far, weight_thres
     return out
 
 
-def render_batch(members, K, hw, near, far, weight_thresh, pixels=None):
+def render_batch(members, K, hw, near, far, weight_thresh, pixels=None, report=False):
     """members: list of dicts with the render() arguments tsdf, weight, dims, origin, vs, trunc, cam2base.  Per pixel the
-    nearest hit wins, ties to the lower index.  Returns depth, normal, member (-1 = miss)."""
+    nearest hit wins, ties to the lower index.  Returns depth, normal, member (-1 = miss); with report=True also "members",
+    each member's own render(report=True)."""
     outs = [render(m["tsdf"], m["weight"], m["dims"], m["origin"], m["vs"], m["trunc"], K, hw, near, far, weight_thresh,
-                   m["cam2base"], pixels=pixels) for m in members]
+                   m["cam2base"], pixels=pixels, report=report) for m in members]
     d = np.stack([np.where(o["hit"], o["depth"], np.inf) for o in outs])
     who = np.argmin(d, axis=0)
     anyhit = np.isfinite(d.min(axis=0))
@@ -189,4 +211,7 @@ def render_batch(members, K, hw, near, far, weight_thresh, pixels=None):
     depth = np.where(anyhit, d[who, np.arange(n)], 0).astype(f32)
     normal = np.stack([o["normal"] for o in outs])[who, np.arange(n)]
     normal = np.where(anyhit[:, None], normal, f32(0)).astype(f32)
-    return {"depth": depth, "normal": normal, "member": np.where(anyhit, who, -1).astype(np.int32)}
+    out = {"depth": depth, "normal": normal, "member": np.where(anyhit, who, -1).astype(np.int32)}
+    if report:
+        out["members"] = outs
+    return out
