@@ -12,7 +12,11 @@
 // The reference's C++ signature carries no camera pose although its Python side needs one
 // (ref: include/TSDFfusion.hpp:49 vs src/TSDFfusion.py.in:31).  Here: SetPose() before the
 // 2-argument Integrate (which uses the last pose set, identity at first), or the 3-argument
-// overload.  Colour is fused beside the distance as tsdf-fusion-python does it (per channel the
+// overload.  Or let the class estimate the pose from the two images the call receives:
+// after EstimatePose(true) every pose-less Integrate but the first tracks its frame against the
+// fused model from the last pose (tsdf_track_rgbd: point-to-plane ICP plus, with a colour image,
+// the intensity residual against the fused colours; csrc/tsdf_photo.hip.h), integrates it at the
+// estimate, and skips a frame whose track is lost.  Pose() and LastTrackStatus() report it.  Colour is fused beside the distance as tsdf-fusion-python does it (per channel the
 // weighted running mean, rounded and clamped; csrc/tsdf_colour.hip.h) and SaveMesh writes it per
 // vertex.  The voxel update is the reference's own GpuIntegrate rule (ref: src/tsdf.cu:15-60); parity
 // with tsdf-fusion-python's arithmetic is unpinned because that package is absent.
@@ -56,6 +60,19 @@ class TSDFfusion
 		/** Pose used by the pose-less Integrate calls (row-major 4x4 camera-to-world). */
 		void SetPose(const float cam2world[16]);
 
+		/** Off (the default): the pose-less Integrate calls use the pose as set.  On: once a frame has been
+		    integrated, they track the incoming frame from the last pose (with rgb when given, depth only
+		    otherwise), store the estimate as the current pose and integrate there; a lost track integrates
+		    nothing and keeps the pose.  The first frame uses the pose as set. */
+		void EstimatePose(bool on);
+
+		/** The pose the last pose-less Integrate used (the pose as set before any). */
+		const float *Pose() const { return pose_; }
+
+		/** -1 when the last pose-less Integrate tracked nothing, else tsdf_track_result's status: 0 converged,
+		    1 iterations exhausted, 2 lost (the frame was not integrated). */
+		int LastTrackStatus() const { return last_status_; }
+
 		/** Surface points to a .ply (the reference's SaveMesh needs the absent Python package;
 		    ref: src/TSDFfusion.py.in:48-53).  Point cloud in the format of ref: src/tsdf.cu:185-212. */
 		void SavePointCloud(const std::string &file_name);
@@ -71,8 +88,12 @@ class TSDFfusion
 		TSDFfusion(const TSDFfusion &);
 		TSDFfusion &operator=(const TSDFfusion &);
 		void initialise();
+		void integratePoseless(const unsigned char *rgb, const float *depth, int height, int width);
 		tsdf_volume *vol_;
 		float pose_[16];
+		bool estimate_;
+		int integrated_;     // frames integrated so far, by any overload
+		int last_status_;
 };
 
 #endif // TSDF_HIP_DROPIN_TSDFFUSION_HPP

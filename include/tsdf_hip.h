@@ -416,6 +416,55 @@ int tsdf_track_system(tsdf_volume *vol, const tsdf_track_params *p, const float 
                       const float ref_cam2world[16], const float cam2world[16], int32_t level, double system_out[29]);
 
 /*
+ * Photometric tracking: tsdf_track's geometric system plus an intensity residual of the live RGB image against the colour
+ * fused into the volume (tsdf_colour_enable), so that a scene whose geometry leaves directions free -- a camera facing a wall
+ * -- is still constrained by its texture.  The rule is stated exactly in csrc/tsdf_photo.hip.h and restated in
+ * tests/photo_spec.py: per level, A = A_geo + photo_weight^2 * A_photo and b likewise, then tsdf_track's solve and step.
+ *   photo_weight       finite, >= 0: metres of point-to-plane residual one unit of intensity ([0, 1]) counts for; 0 = geometric only
+ *   intensity_thresh   finite, > 0: a photometric pair whose |residual| exceeds this is rejected
+ * tsdf_photo_params_default: photo_weight 0.1, intensity_thresh 0.25.  Host arithmetic only: needs no device.
+ * A track is lost as tsdf_track's is, by the GEOMETRIC pair count or a failed pivot of the combined system.
+ */
+typedef struct tsdf_photo_params {
+    float photo_weight;
+    float intensity_thresh;
+} tsdf_photo_params;
+
+typedef struct tsdf_track_rgbd_result {
+    tsdf_track_result geo;     /* as tsdf_track's: inliers and rmse are the geometric pairs' */
+    int32_t photo_pairs;       /* photometric pairs of the last iteration run (0 without an rgb image or weight) */
+    float photo_rmse;          /* sqrt(sum r^2 / photo_pairs) of that iteration, intensity units */
+} tsdf_track_rgbd_result;
+
+int tsdf_photo_params_default(const tsdf_config *cfg, tsdf_photo_params *out);
+/*
+ * The images are host memory: depth_host ray.im_height x ray.im_width floats (metres), rgb_host as many R, G, B byte triples
+ * or NULL, mask_host as many {0, 255} bytes or NULL; each is copied once.  Applies the handle's collected frames first, reads
+ * the volume only, and returns when the result is on the host.  With rgb_host NULL or photo_weight 0 it is the geometric
+ * track: `geo` is tsdf_track's result on the same frame bit for bit and photo_pairs is 0.  An rgb image needs a handle with
+ * colour enabled.  Lost is not an error: TSDF_OK with status 2.  Whole-grid handles only.
+ */
+int tsdf_track_rgbd(tsdf_volume *vol, const tsdf_track_params *p, const tsdf_photo_params *pp, const float *depth_host,
+                    const uint8_t *rgb_host, const uint8_t *mask_host, const float guess_cam2world[16],
+                    tsdf_track_rgbd_result *out);
+/*
+ * Both linear systems of one iteration of level `level`, each in tsdf_track_system's layout, unweighted and not added:
+ * geo_out equals tsdf_track_system's output, photo_out is the photometric one.  rgb_host is required.  Returns when both are
+ * on the host.
+ */
+int tsdf_track_rgbd_system(tsdf_volume *vol, const tsdf_track_params *p, const tsdf_photo_params *pp, const float *depth_host,
+                           const uint8_t *rgb_host, const uint8_t *mask_host, const float ref_cam2world[16],
+                           const float cam2world[16], int32_t level, double geo_out[29], double photo_out[29]);
+/*
+ * The model intensity image of pyramid level `level` (0..2) seen from cam2world: (im_height >> level) x (im_width >> level)
+ * floats in [0, 1], -1 where the model has none.  Trilinear in the fused colours' luminance at the depth render's hit point, so
+ * unlike tsdf_raycast's colour output it has a usable image gradient.  For callers who bring residuals of their own.  Returns
+ * when the image is on the host.
+ */
+int tsdf_render_intensity(tsdf_volume *vol, const tsdf_raycast_params *p, const float cam2world[16], int32_t level,
+                          float *intensity_host);
+
+/*
  * Merging and re-gridding: every voxel of dst samples src at its own position (trilinear, through both handles' base2world,
  * origin and voxel size) and folds the sample in as one observation whose weight is the smallest of the 8 corner weights.  Two
  * uses: a duplicate object (tsdf_batch_associate answered -1 for a partial view, so one physical object lives in two volumes)

@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "tsdf_colour_enable", "tsdf_integrate_colour_device", "tsdf_integrate_rgbd", "tsdf_download_colour",
     "tsdf_raycast_params_default", "tsdf_raycast_device", "tsdf_raycast", "tsdf_batch_raycast_device",
     "tsdf_track_params_default", "tsdf_track", "tsdf_track_system",
+    "tsdf_photo_params_default", "tsdf_track_rgbd", "tsdf_track_rgbd_system", "tsdf_render_intensity",
     "tsdf_batch_track", "tsdf_batch_track_system", "tsdf_track_member_systems",
     "tsdf_fuse_params_default", "tsdf_fuse_volume",
     "tsdf_align_params_default", "tsdf_fuse_pose_default", "tsdf_align_volume", "tsdf_align_system", "tsdf_fuse_volume_at",
@@ -111,6 +112,16 @@ class TrackResult(C.Structure):
         ("cam2world", C.c_float * 16), ("status", C.c_int32), ("iters_run", C.c_int32 * 3), ("inliers", C.c_int32),
         ("rmse", C.c_float),
     ]
+
+
+class PhotoParams(C.Structure):
+    """Mirror of `struct tsdf_photo_params` (include/tsdf_hip.h)."""
+    _fields_ = [("photo_weight", C.c_float), ("intensity_thresh", C.c_float)]
+
+
+class TrackRgbdResult(C.Structure):
+    """Mirror of `struct tsdf_track_rgbd_result` (include/tsdf_hip.h)."""
+    _fields_ = [("geo", TrackResult), ("photo_pairs", C.c_int32), ("photo_rmse", C.c_float)]
 
 
 class FuseParams(C.Structure):
@@ -302,6 +313,10 @@ def load():
     L.tsdf_track_params_default.argtypes = [C.POINTER(TsdfConfig), C.POINTER(TrackParams)]
     L.tsdf_track.argtypes = [vp, C.POINTER(TrackParams), vp, vp, vp, C.POINTER(TrackResult)]
     L.tsdf_track_system.argtypes = [vp, C.POINTER(TrackParams), vp, vp, vp, vp, C.c_int32, vp]
+    L.tsdf_photo_params_default.argtypes = [C.POINTER(TsdfConfig), C.POINTER(PhotoParams)]
+    L.tsdf_track_rgbd.argtypes = [vp, C.POINTER(TrackParams), C.POINTER(PhotoParams), vp, vp, vp, vp, C.POINTER(TrackRgbdResult)]
+    L.tsdf_track_rgbd_system.argtypes = [vp, C.POINTER(TrackParams), C.POINTER(PhotoParams), vp, vp, vp, vp, vp, C.c_int32, vp, vp]
+    L.tsdf_render_intensity.argtypes = [vp, C.POINTER(RaycastParams), vp, C.c_int32, vp]
     L.tsdf_batch_track.argtypes = [vp, C.POINTER(TrackParams), vp, vp, vp, vp, C.POINTER(TrackResult), vp]
     L.tsdf_batch_track_system.argtypes = [vp, C.POINTER(TrackParams), vp, vp, vp, vp, C.c_int32, vp]
     L.tsdf_track_member_systems.argtypes = [C.c_int32, C.POINTER(TrackParams), vp, vp, vp, C.c_int32, vp, vp, vp, vp,
@@ -456,6 +471,13 @@ def track_params_default(cfg):
     {10, 5, 4}, 0.10 m, cos(20 deg), min_inliers 300, eps 1e-5 rad / 1e-5 m (no device)."""
     p = TrackParams()
     check(load().tsdf_track_params_default(C.byref(cfg), C.byref(p)), "tsdf_track_params_default")
+    return p
+
+
+def photo_params_default(cfg):
+    """Photometric tracking parameters (include/tsdf_hip.h): photo_weight 0.1, intensity_thresh 0.25 (no device)."""
+    p = PhotoParams()
+    check(load().tsdf_photo_params_default(C.byref(cfg), C.byref(p)), "tsdf_photo_params_default")
     return p
 
 
@@ -1032,6 +1054,58 @@ class Volume:
         A[np.triu_indices(6)] = out[:21]
         A = A + np.triu(A, 1).T
         return A, out[21:27].copy(), float(out[27]), int(out[28])
+
+    def _host_frame(self, p, depth, rgb, mask):
+        """The host images of a photometric call as contiguous arrays of params.ray's size (rgb and mask may be None)."""
+        hw = (p.ray.im_height, p.ray.im_width)
+        d = np.ascontiguousarray(depth, np.float32)
+        c = None if rgb is None else np.ascontiguousarray(rgb, np.uint8)
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        if d.shape != hw or (c is not None and c.shape != hw + (3,)) or (m is not None and m.shape != hw):
+            raise ValueError(f"expected images of {hw[0]} x {hw[1]} pixels")
+        return d, c, m
+
+    def track_rgbd(self, depth, rgb, guess_cam2world, params=None, photo=None, mask=None):
+        """Track a live RGB-D frame (host arrays: depth [H, W] float32, rgb [H, W, 3] uint8 or None, mask [H, W] uint8 or
+        None) against the model from guess_cam2world with the geometric and the photometric term (csrc/tsdf_photo.hip.h).
+        Returns (cam2world [4, 4] float32, stats as track's plus photo_pairs, photo_rmse).  photo: a PhotoParams, default
+        photo_params_default(cfg); rgb None or photo_weight 0 is the geometric track."""
+        p = track_params_default(self.cfg) if params is None else params
+        pp = photo_params_default(self.cfg) if photo is None else photo
+        d, c, m = self._host_frame(p, depth, rgb, mask)
+        guess = _f32(guess_cam2world, 16)
+        res = TrackRgbdResult()
+        check(self.lib.tsdf_track_rgbd(self._h, C.byref(p), C.byref(pp), d.ctypes.data, None if c is None else c.ctypes.data,
+                                       None if m is None else m.ctypes.data, guess.ctypes.data, C.byref(res)), "tsdf_track_rgbd")
+        g = res.geo
+        pose = np.array(g.cam2world, np.float32).reshape(4, 4)
+        stats = {"status": g.status, "status_name": TRACK_STATUS[g.status], "iters_run": list(g.iters_run),
+                 "inliers": g.inliers, "rmse": g.rmse, "photo_pairs": res.photo_pairs, "photo_rmse": res.photo_rmse}
+        return pose, stats
+
+    def track_rgbd_system(self, depth, rgb, ref_cam2world, cam2world, level=0, params=None, photo=None, mask=None):
+        """Both systems of one iteration at `level` (tsdf_track_rgbd_system): (geo [29], photo [29]) float64 in
+        tsdf_track_system's layout, unweighted."""
+        p = track_params_default(self.cfg) if params is None else params
+        pp = photo_params_default(self.cfg) if photo is None else photo
+        d, c, m = self._host_frame(p, depth, rgb, mask)
+        ref, cur = _f32(ref_cam2world, 16), _f32(cam2world, 16)
+        geo, pho = np.zeros(29, np.float64), np.zeros(29, np.float64)
+        check(self.lib.tsdf_track_rgbd_system(self._h, C.byref(p), C.byref(pp), d.ctypes.data,
+                                              None if c is None else c.ctypes.data, None if m is None else m.ctypes.data,
+                                              ref.ctypes.data, cur.ctypes.data, level, geo.ctypes.data, pho.ctypes.data),
+              "tsdf_track_rgbd_system")
+        return geo, pho
+
+    def render_intensity(self, cam2world, level=0, params=None):
+        """The model intensity image of pyramid level `level` from cam2world (tsdf_render_intensity): float32
+        [H >> level, W >> level], -1 where the model has none.  params: a RaycastParams."""
+        p = raycast_params_default(self.cfg) if params is None else params
+        out = np.empty((p.im_height >> max(level, 0), p.im_width >> max(level, 0)), np.float32)
+        c2w = _f32(cam2world, 16)
+        check(self.lib.tsdf_render_intensity(self._h, C.byref(p), c2w.ctypes.data, level, out.ctypes.data),
+              "tsdf_render_intensity")
+        return out
 
     # -- merging ----------------------------------------------------------------------------
     def fuse_from(self, src, params=None, dst2src=None, carry=0):

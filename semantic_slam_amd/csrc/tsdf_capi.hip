@@ -41,6 +41,7 @@
 #include "tsdf_raycast.hip.h"
 #include "tsdf_track.hip.h"
 #include "tsdf_batch_track.hip.h"
+#include "tsdf_photo.hip.h"
 #include "tsdf_fuse.hip.h"
 #include "tsdf_fuse_carry.hip.h"
 #include "tsdf_align.hip.h"
@@ -191,6 +192,11 @@ struct tsdf_volume {
     // rows of an association pass and the pose state, in one block; the state's pinned host copy
     DevBuf<char> d_track;
     HostPtr<tsdfk::TrackState> h_track;
+    // photometric tracking (tsdf_track_rgbd*, tsdf_render_intensity), allocated on first use and grown with the image: the staged
+    // host frame (depth | rgb | mask), the live and model intensity pyramids, the photometric partial rows and state in one
+    // block; its pinned mirror (depth | rgb | mask | state), free again when a call returns
+    DevBuf<char> d_photo;
+    HostBuf<char> h_photo;
     // merging (tsdf_fuse_volume* with this handle as the destination), allocated on first use, all or none: the eight counts
     // (four of the merge, four of the labels carried: tsdf_fuse_volume_carry) in HBM and pinned; src_ready is recorded on the source's stream before the kernel, done on this handle's stream after it
     DevPtr<unsigned long long> d_fuse;
@@ -1686,6 +1692,7 @@ int tsdf_upload_colour(tsdf_volume *v, const uint32_t *colour_host)
 #include "tsdf_batch_host.hip.h"
 #include "tsdf_raycast_host.hip.h"
 #include "tsdf_track_host.hip.h"
+#include "tsdf_photo_host.hip.h"
 #include "tsdf_fuse_host.hip.h"
 #include "tsdf_align_host.hip.h"
 #include "tsdf_extent_host.hip.h"

@@ -142,7 +142,7 @@ TSDF::~TSDF()
 // ------------------------------------------------------------------------------------------------
 // TSDFfusion
 // ------------------------------------------------------------------------------------------------
-TSDFfusion::TSDFfusion() : vol_(NULL)
+TSDFfusion::TSDFfusion() : vol_(NULL), estimate_(false), integrated_(0), last_status_(-1)
 {
 	initialise();
 }
@@ -177,6 +177,8 @@ TSDFfusion::~TSDFfusion()
 
 void TSDFfusion::SetPose(const float cam2world[16]) { std::memcpy(pose_, cam2world, sizeof pose_); }
 
+void TSDFfusion::EstimatePose(bool on) { estimate_ = on; }
+
 void TSDFfusion::Integrate(const unsigned char *rgb, const float *depth, int height, int width, const float cam2world[16])
 {
 	tsdf_config cfg;
@@ -187,11 +189,34 @@ void TSDFfusion::Integrate(const unsigned char *rgb, const float *depth, int hei
 	const int rc = rgb ? tsdf_integrate_rgbd(vol_, depth, rgb, cam2world) : tsdf_integrate(vol_, depth, cam2world);
 	if (rc != TSDF_OK)
 		throw std::runtime_error(std::string("TSDFfusion::Integrate: ") + tsdf_last_error());
+	++integrated_;
+}
+
+// The pose-less calls: with EstimatePose on and a model to track against, the pose comes from the frame itself.
+void TSDFfusion::integratePoseless(const unsigned char *rgb, const float *depth, int height, int width)
+{
+	last_status_ = -1;
+	if (estimate_ && integrated_ > 0) {
+		tsdf_config cfg;
+		tsdf_get_config(vol_, &cfg);
+		if (height != cfg.im_height || width != cfg.im_width)
+			throw std::runtime_error("TSDFfusion::Integrate: depth image must be 480x640");
+		tsdf_track_params tp;
+		tsdf_photo_params pp;
+		tsdf_track_rgbd_result res;
+		if (tsdf_track_params_default(&cfg, &tp) != TSDF_OK || tsdf_photo_params_default(&cfg, &pp) != TSDF_OK ||
+		    tsdf_track_rgbd(vol_, &tp, &pp, depth, rgb, NULL, pose_, &res) != TSDF_OK)
+			throw std::runtime_error(std::string("TSDFfusion::Integrate: ") + tsdf_last_error());
+		last_status_ = res.geo.status;
+		if (res.geo.status == 2) return;      // lost: nothing is integrated, the pose stays
+		std::memcpy(pose_, res.geo.cam2world, sizeof pose_);
+	}
+	Integrate(rgb, depth, height, width, pose_);
 }
 
 void TSDFfusion::Integrate(const unsigned char *rgb, const float *depth, int height, int width)
 {
-	Integrate(rgb, depth, height, width, pose_);
+	integratePoseless(rgb, depth, height, width);
 }
 
 #ifdef TSDFFUSION_HAVE_OPENCV
@@ -201,7 +226,7 @@ void TSDFfusion::Integrate(cv::Mat imRGB, cv::Mat imD)
 		throw std::runtime_error("TSDFfusion::Integrate: depth must be continuous CV_32F metres");
 	if (!imRGB.empty() && (imRGB.type() != CV_8UC3 || !imRGB.isContinuous() || imRGB.rows != imD.rows || imRGB.cols != imD.cols))
 		throw std::runtime_error("TSDFfusion::Integrate: colour must be continuous CV_8UC3 of the depth image's size");
-	Integrate(imRGB.empty() ? NULL : imRGB.data, (const float *)imD.data, imD.rows, imD.cols, pose_);
+	integratePoseless(imRGB.empty() ? NULL : imRGB.data, (const float *)imD.data, imD.rows, imD.cols);
 }
 
 void TSDFfusion::Integrate(cv::Mat imRGB, cv::Mat imD, cv::Mat cam2world)
@@ -210,7 +235,11 @@ void TSDFfusion::Integrate(cv::Mat imRGB, cv::Mat imD, cv::Mat cam2world)
 	cam2world.convertTo(p, CV_32F);
 	p = p.clone();
 	SetPose((const float *)p.data);
-	Integrate(imRGB, imD);
+	if (imD.type() != CV_32F || !imD.isContinuous())
+		throw std::runtime_error("TSDFfusion::Integrate: depth must be continuous CV_32F metres");
+	if (!imRGB.empty() && (imRGB.type() != CV_8UC3 || !imRGB.isContinuous() || imRGB.rows != imD.rows || imRGB.cols != imD.cols))
+		throw std::runtime_error("TSDFfusion::Integrate: colour must be continuous CV_8UC3 of the depth image's size");
+	Integrate(imRGB.empty() ? NULL : imRGB.data, (const float *)imD.data, imD.rows, imD.cols, pose_);      // the pose as given
 }
 #endif
 
