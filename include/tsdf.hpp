@@ -14,6 +14,8 @@
 //     TSDF(const tsdf_config&)   run-time grid size / voxel size / intrinsics / z-slab / device
 //     TSDF(const tsdf_config&, devices)   the same grid cut into z-slabs over several GPUs of the node, in this
 //                                process (tsdf_group_*): Integrate fans the frame out, the destructor gathers
+//     IntegrateRange(), IntegrateScan()   Integrate for the reference's second sensor (mSensor == 1): an image of lidar
+//                                ranges, or the Velodyne scan itself, made into z-depth on the device
 //     Download(), Sync()         read results back without destroying the object
 //     SetSaveOnDestroy(false)    skip the two files the destructor writes
 //     TSDF::ThrowOnError(true)   throw std::runtime_error instead of print + exit(1)
@@ -56,6 +58,21 @@ class TSDF
 	*/
 	void Integrate(float *depth_im, std::vector<float> cam2world_vec);
 
+	/** Integrate one image of lidar RANGES, distances along the ray (not in the reference, whose lidar call site hands its
+	range image to Integrate as it is: ref: examples/label_instance_lidar.cpp:76-77,126, src/Object.cpp:160-164 and the FIXME
+	at :41).  Each range is divided by its ray's length under the object's intrinsics (ref: src/Object.cpp:613-620), on the
+	device, and the z-depth image is integrated as Integrate would.
+	@param range_im pointer to h*w floats, metres along the ray, 0 = no return; borrowed for the call only
+	*/
+	void IntegrateRange(float *range_im, std::vector<float> cam2world_vec);
+
+	/** Integrate one Velodyne scan (ref: src/Utility.cpp:374-419 makes the range image of it on the CPU).
+	@param xyzi n points of 4 floats (x, y, z, intensity) in the scanner's frame, the KITTI .bin layout; borrowed for the call
+	@param n number of points
+	@param velo2img 12 floats, row-major 3x4: scanner frame to pixels times depth (tsdf_scan_projection composes it)
+	*/
+	void IntegrateScan(const float *xyzi, size_t n, const float velo2img[12], std::vector<float> cam2world_vec);
+
 	/// pointer to a TSDF voxel grid (host mirror; refreshed by Download() and by the destructor)
 	float * voxel_grid_TSDF;
 
@@ -85,5 +102,8 @@ class TSDF
 	tsdf_group *grp_;
 	std::vector<int> devices_;
 	bool save_on_destroy_;
+	tsdf_scanner *scan_;               // a multi-device object's: scans become z-depth on devices_[0], then fan out
+	std::vector<float> scan_depth_;
+	float *scan_image();               // scan_ and scan_depth_ at their first use
 };
 #endif // TSDF_HIP_DROPIN_TSDF_HPP

@@ -897,6 +897,59 @@ int tsdf_segment_frame(tsdf_segmenter *seg, const tsdf_segment_params *p, const 
                        int32_t *cluster_dev /* may be NULL */, int32_t *n_clusters);
 
 /*
+ * Lidar scans.  The reference's second sensor (mSensor == 1) feeds its object loop an image of RANGES, distances along the
+ * ray, made from a Velodyne scan (ref: examples/label_instance_lidar.cpp:76-77,126; src/Utility.cpp:40-57,374-419), and every
+ * consumer that turns such a pixel into a point divides by the ray's length (ref: src/Object.cpp:613-620, src/DoN.cpp:89-96).
+ * Everything else in this header takes z-depth; the calls below make z-depth out of a scan or out of a range image, on the
+ * device, so that the whole of it serves the second sensor as well.  The rule is stated exactly in csrc/tsdf_scan.hip.h and
+ * restated in tests/scan_spec.py; every pointer here is host memory, borrowed for the call only.
+ *   points_host   n_points x 4 floats in the KITTI .bin layout (x, y, z, intensity; the intensity is ignored), in scan order:
+ *                 where several points fall into one pixel the one with the highest index stays, as in the reference's loop.
+ *                 0 <= n_points <= 4294967295 (2^32 - 1: a point's index + 1 is the upper word of its pixel's 64-bit key);
+ *                 n_points == 0 is valid (points_host may then be NULL) and gives all-zero images
+ *   velo2img      3 x 4 row-major, scanner frame to pixels times depth; finite.  A point is kept when (velo2img * point)[0]
+ *                 >= 2 (ref: src/Utility.cpp:53, the reference's guard as it stands) and its pixel (u, v), truncated, has
+ *                 1 <= u < width and 1 <= v < height: row 0 and column 0 are never written (ref: :405)
+ *   cam_K         the camera of the range image, finite with fx, fy != 0:
+ *                 depth = range / sqrtf(((u - cx) / fx)^2 + ((v - cy) / fy)^2 + 1) where 0 < range <= FLT_MAX, else 0
+ * tsdf_scan_projection composes velo2img = P_rect * [R_rect 0; 0 1] * [R_velo t_velo; 0 1] (ref: src/Utility.cpp:42-49) in
+ * tsdf_multiply_matrix's fp32 operation order; host arithmetic only, needs no device.  The library embeds no calibration.
+ */
+int tsdf_scan_projection(const float P_rect[12], const float R_rect[9], const float R_velo[9], const float t_velo[3],
+                         float velo2img_out[12]);
+/*
+ * A tsdf_scanner projects scans into images of one size on one device; it owns the key image, the points' staging and the
+ * output images (allocated at the first call that needs them).  One scanner may be driven from one thread at a time.
+ *   tsdf_scan_project         the scan's range image into range_host, its z-depth image into depth_host (both im_height x
+ *                             im_width floats, 0 where no point fell) and the number of written pixels into *n_pixels.  Each
+ *                             of the three may be NULL, not all of them; cam_K may be NULL when depth_host is.  Returns with
+ *                             the images on the host.  Successive scans through one scanner do not see each other.
+ *   tsdf_scan_range_to_depth  the conversion alone, for a caller who holds a range image already; returns with depth_host
+ *                             written.  range_host and depth_host may be the same buffer.
+ * depth_host is what tsdf_integrate, tsdf_group_integrate and -- uploaded -- tsdf_object_origin, the batch, segmentation and
+ * tracking calls take as their depth frame, unchanged.
+ */
+typedef struct tsdf_scanner tsdf_scanner;
+int tsdf_scanner_create(int32_t device, int32_t im_height, int32_t im_width, tsdf_scanner **out);
+int tsdf_scanner_destroy(tsdf_scanner *scanner);
+int tsdf_scan_project(tsdf_scanner *scanner, const float velo2img[12], const float cam_K[9], const float *points_host,
+                      int64_t n_points, float *range_host, float *depth_host, int64_t *n_pixels);
+int tsdf_scan_range_to_depth(tsdf_scanner *scanner, const float cam_K[9], const float *range_host, float *depth_host);
+/*
+ * TSDF::Integrate for the second sensor: tsdf_integrate's call shape and behaviour, deferral included (the frames of these
+ * calls are collected with tsdf_integrate's and applied with them, in call order), for an image of ranges or for the scan
+ * itself.  The image size and cam_K are the handle's (a handle whose cam_K is not finite or has fx or fy == 0 is refused).
+ *   tsdf_integrate_range   range_host: im_height x im_width floats; copied as it is and converted to z-depth on the device
+ *                          on its way into the frame's slot, as tsdf_integrate_u16 converts a 16-bit frame
+ *   tsdf_integrate_scan    points in, fused: projected on the device straight into the frame's slot; the image never
+ *                          leaves the device.  The handle's scan memory is allocated at the first such call
+ * Equal, bit for bit, to tsdf_integrate of tsdf_scan_range_to_depth's, respectively tsdf_scan_project's, depth_host.
+ */
+int tsdf_integrate_range(tsdf_volume *vol, const float *range_host, const float cam2world[16]);
+int tsdf_integrate_scan(tsdf_volume *vol, const float velo2img[12], const float *points_host, int64_t n_points,
+                        const float cam2world[16]);
+
+/*
  * One grid over several devices in ONE process.  The reference's host is a C++ program that owns its TSDFs directly
  * (ref: include/tsdf.hpp:22-43; src/Engine.cpp:170-172 drives distinct TSDFs from one loop), so a C++ caller must be
  * able to span the node without a process per GPU.  tsdf_group_create cuts the grid of *cfg (its z_begin / z_end /

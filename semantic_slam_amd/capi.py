@@ -41,6 +41,8 @@ ABI_SYMBOLS = [
     "tsdf_associate_params_default", "tsdf_associate_count", "tsdf_associate_assign", "tsdf_batch_associate",
     "tsdf_segment_params_default", "tsdf_segmenter_create", "tsdf_segmenter_destroy", "tsdf_segmenter_set_stream",
     "tsdf_segment_depth_device", "tsdf_segment_refine_masks_device", "tsdf_segment_frame",
+    "tsdf_scan_projection", "tsdf_scanner_create", "tsdf_scanner_destroy", "tsdf_scan_project", "tsdf_scan_range_to_depth",
+    "tsdf_integrate_range", "tsdf_integrate_scan",
     "tsdf_object_origin", "tsdf_batch_create", "tsdf_batch_destroy", "tsdf_batch_size", "tsdf_batch_volume",
     "tsdf_batch_integrate_device", "tsdf_batch_sync",
     "tsdf_group_create", "tsdf_group_destroy", "tsdf_group_size", "tsdf_group_voxels", "tsdf_group_volume",
@@ -353,6 +355,13 @@ def load():
     L.tsdf_segment_depth_device.argtypes = [vp, C.POINTER(SegmentParams), vp, vp, vp, C.POINTER(C.c_int32)]
     L.tsdf_segment_refine_masks_device.argtypes = [vp, C.POINTER(SegmentParams), vp, C.c_int32, vp, C.c_int32, vp, vp]
     L.tsdf_segment_frame.argtypes = [vp, C.POINTER(SegmentParams), vp, vp, C.c_int32, vp, vp, C.POINTER(C.c_int32)]
+    L.tsdf_scan_projection.argtypes = [vp, vp, vp, vp, vp]
+    L.tsdf_scanner_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
+    L.tsdf_scanner_destroy.argtypes = [vp]
+    L.tsdf_scan_project.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, i64p]
+    L.tsdf_scan_range_to_depth.argtypes = [vp, vp, vp, vp]
+    L.tsdf_integrate_range.argtypes = [vp, vp, vp]
+    L.tsdf_integrate_scan.argtypes = [vp, vp, vp, C.c_int64, vp]
     L.tsdf_object_origin.argtypes = [C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp]
     L.tsdf_batch_create.argtypes = [C.POINTER(TsdfConfig), C.c_int32, C.POINTER(vp)]
     L.tsdf_batch_destroy.argtypes = [vp]
@@ -665,6 +674,75 @@ class Segmenter:
         return n.value
 
 
+def scan_projection(P_rect, R_rect, R_velo, t_velo):
+    """velo2img [3, 4] = P_rect * [R_rect 0; 0 1] * [R_velo t_velo; 0 1] in the library's fp32 operation order (no device)."""
+    out = np.zeros(12, np.float32)
+    P, Rr, Rv, t = _f32(P_rect, 12), _f32(R_rect, 9), _f32(R_velo, 9), _f32(t_velo, 3)
+    check(load().tsdf_scan_projection(P.ctypes.data, Rr.ctypes.data, Rv.ctypes.data, t.ctypes.data, out.ctypes.data),
+          "tsdf_scan_projection")
+    return out.reshape(3, 4)
+
+
+def _scan_points(points):
+    """A scan as contiguous float32 [n, 4] (the KITTI .bin layout)."""
+    pts = np.ascontiguousarray(points, dtype=np.float32)
+    if pts.ndim != 2 or pts.shape[1] != 4:
+        raise ValueError(f"expected points of shape [n, 4], got {pts.shape}")
+    return pts
+
+
+class Scanner:
+    """A tsdf_scanner: lidar scans into range and z-depth images of one size on one device.  Every array is host memory;
+    every call returns with its outputs written."""
+
+    def __init__(self, im_height, im_width, device=0):
+        self.lib = load()
+        self.h, self.w = int(im_height), int(im_width)
+        self._h = C.c_void_p()
+        check(self.lib.tsdf_scanner_create(device, self.h, self.w, C.byref(self._h)), "tsdf_scanner_create")
+
+    def close(self):
+        if self._h:
+            self.lib.tsdf_scanner_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def project(self, points, velo2img, K=None, want_range=True, want_depth=True, want_count=True):
+        """(range [h, w] or None, depth [h, w] or None, written pixels or None) of a scan [n, 4]; K is needed for the depth."""
+        pts = _scan_points(points)
+        m = _f32(velo2img, 12)
+        k = None if K is None else _f32(K, 9)
+        rng = np.empty((self.h, self.w), np.float32) if want_range else None
+        dep = np.empty((self.h, self.w), np.float32) if want_depth else None
+        n = C.c_int64(-1)
+        check(self.lib.tsdf_scan_project(self._h, m.ctypes.data, None if k is None else k.ctypes.data,
+                                         pts.ctypes.data if len(pts) else None, len(pts),
+                                         None if rng is None else rng.ctypes.data, None if dep is None else dep.ctypes.data,
+                                         C.byref(n) if want_count else None), "tsdf_scan_project")
+        return rng, dep, (int(n.value) if want_count else None)
+
+    def range_to_depth(self, range_im, K):
+        """The z-depth image of a range image [h, w] under the camera K."""
+        r = np.ascontiguousarray(range_im, dtype=np.float32)
+        if r.shape != (self.h, self.w):
+            raise ValueError(f"the range image is {r.shape}, the scanner's {(self.h, self.w)}")
+        k = _f32(K, 9)
+        out = np.empty((self.h, self.w), np.float32)
+        check(self.lib.tsdf_scan_range_to_depth(self._h, k.ctypes.data, r.ctypes.data, out.ctypes.data), "tsdf_scan_range_to_depth")
+        return out
+
+
 def selftest_round(device=0):
     """Returns (mismatches, first_bad[4]) of the exhaustive pixel-rounding self-test."""
     cnt = C.c_uint64()
@@ -794,6 +872,19 @@ class Volume:
     def set_deferral(self, n_frames):
         """Host frames collected per launch by integrate() (0 / 1: every call launches; default 32)."""
         check(self.lib.tsdf_set_deferral(self._h, n_frames), "tsdf_set_deferral")
+
+    def integrate_range(self, range_host, cam2world):
+        """integrate() for a lidar range image (distance along the ray): converted to z-depth on the device."""
+        r = _f32(range_host, self.cfg.im_height * self.cfg.im_width)
+        p = _f32(cam2world, 16)
+        check(self.lib.tsdf_integrate_range(self._h, r.ctypes.data, p.ctypes.data), "tsdf_integrate_range")
+
+    def integrate_scan(self, points, velo2img, cam2world):
+        """integrate() for a lidar scan [n, 4] (x, y, z, intensity): projected on the device, the image never leaves it."""
+        pts = _scan_points(points)
+        m, p = _f32(velo2img, 12), _f32(cam2world, 16)
+        check(self.lib.tsdf_integrate_scan(self._h, m.ctypes.data, pts.ctypes.data if len(pts) else None, len(pts), p.ctypes.data),
+              "tsdf_integrate_scan")
 
     def integrate_u16(self, raw_u16, cam2world, depth_factor=5000.0, row_step=1, col_step=1):
         """Raw 16-bit frame: half-size H2D copy, conversion (and optional subsampling) on the device."""

@@ -1,6 +1,6 @@
 // tsdf_capi.hip -- implementation of include/tsdf_hip.h (libtsdf_hip.so).  Handles, integration, labels and colour are here;
-// batches, raycasting, tracking, merging, registration, extents, association and segmentation each in a
-// tsdf_<feature>_host.hip.h (the last seven beside their kernels), extraction, the file writers and the checkpoint calls in
+// batches, raycasting, tracking, merging, registration, extents, association, segmentation and lidar scans each in a
+// tsdf_<feature>_host.hip.h (the last eight beside their kernels), extraction, the file writers and the checkpoint calls in
 // tsdf_extract_host.hip.h (the file formats themselves in mesh_files.h, host-only), the group in tsdf_group.hip.h and
 // include/tsdf_hip_diag.h in tsdf_diag.hip.h, all included at the end (one translation unit).
 //
@@ -48,6 +48,7 @@
 #include "tsdf_extent.hip.h"
 #include "tsdf_associate.hip.h"
 #include "tsdf_segment.hip.h"
+#include "tsdf_scan.hip.h"
 #ifdef TSDF_EXPERIMENTS
 #include "tsdf_experiments.hip.h"
 #endif
@@ -107,6 +108,20 @@ constexpr size_t kClaimBlockBytes = (tsdfk::kCounterBytes + sizeof(tsdfk::ClassP
 constexpr int kWedgeMode = TSDF_WEDGE_MODE;
 
 }  // namespace
+
+// What projecting a lidar scan needs on a device (tsdf_scan_host.hip.h), held by a tsdf_scanner and by every handle that has
+// been given a scan; allocated on first use.  keys: one 64-bit key per pixel, all zero between calls (scan_resolve leaves
+// them so; keys_clean is false from the splat's launch until the resolve's, so a call that failed in between costs the next
+// one a clear).  The points' pinned block and its copy in HBM grow with the scan; pts_read, recorded behind the kernel that
+// read them, is what the next call waits for before it refills or regrows either.
+struct ScanStage {
+    DevBuf<unsigned long long> d_keys;
+    bool keys_clean = false;
+    DevBuf<float4> d_pts;
+    HostBuf<float4> h_pts;
+    Event pts_read;
+    bool pts_in_use = false;
+};
 
 struct tsdf_volume {
     tsdf_config cfg = {};
@@ -212,6 +227,8 @@ struct tsdf_volume {
     // workgroup of the launch in HBM (the slab's dims fix their number); the record's pinned host copy
     DevPtr<unsigned long long> d_extent;
     HostPtr<unsigned long long> h_extent;
+    // lidar scans (tsdf_integrate_scan), allocated on first use: a handle that never sees a scan allocates nothing
+    ScanStage scan;
 };
 
 using tsdf_host::kBatchSideStreams;
@@ -1699,6 +1716,7 @@ int tsdf_upload_colour(tsdf_volume *v, const uint32_t *colour_host)
 #include "tsdf_associate_host.hip.h"
 #include "tsdf_batch_track_host.hip.h"
 #include "tsdf_segment_host.hip.h"
+#include "tsdf_scan_host.hip.h"
 #include "tsdf_extract_host.hip.h"
 #include "tsdf_group.hip.h"
 #include "tsdf_diag.hip.h"

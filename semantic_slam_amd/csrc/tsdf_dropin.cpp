@@ -29,7 +29,7 @@ void TSDF::fail(const char *what, int line) const
 }
 
 TSDF::TSDF(int h, int w, int MOid, std::vector<float> base2world_, std::vector<float> origin)
-	: voxel_grid_TSDF(NULL), voxel_grid_weight(NULL), vol_(NULL), grp_(NULL), save_on_destroy_(true)
+	: voxel_grid_TSDF(NULL), voxel_grid_weight(NULL), vol_(NULL), grp_(NULL), save_on_destroy_(true), scan_(NULL)
 {
 	tsdf_config_default(&cfg_, h, w);  // 200^3 @ 4 mm, trunc 20 mm, TUM K (ref: include/tsdf.hpp:63-67,96)
 	cfg_.id = MOid;
@@ -39,14 +39,14 @@ TSDF::TSDF(int h, int w, int MOid, std::vector<float> base2world_, std::vector<f
 }
 
 TSDF::TSDF(const tsdf_config &cfg)
-	: voxel_grid_TSDF(NULL), voxel_grid_weight(NULL), cfg_(cfg), vol_(NULL), grp_(NULL), save_on_destroy_(true)
+	: voxel_grid_TSDF(NULL), voxel_grid_weight(NULL), cfg_(cfg), vol_(NULL), grp_(NULL), save_on_destroy_(true), scan_(NULL)
 {
 	init();
 }
 
 TSDF::TSDF(const tsdf_config &cfg, const std::vector<int> &devices)
 	: voxel_grid_TSDF(NULL), voxel_grid_weight(NULL), cfg_(cfg), vol_(NULL), grp_(NULL), devices_(devices),
-	  save_on_destroy_(true)
+	  save_on_destroy_(true), scan_(NULL)
 {
 	cfg_.z_begin = 0;
 	cfg_.z_end = cfg_.dim_z;
@@ -79,6 +79,40 @@ void TSDF::Integrate(float *depth_im, std::vector<float> cam2world_vec)
 	for (size_t i = 0; i < 16 && i < cam2world_vec.size(); ++i) cam2world[i] = cam2world_vec[i];  // ref: src/tsdf.cu:139
 	const int rc = grp_ ? tsdf_group_integrate(grp_, depth_im, cam2world) : tsdf_integrate(vol_, depth_im, cam2world);
 	if (rc != TSDF_OK) fail("tsdf_integrate", __LINE__);
+}
+
+// A multi-device object makes the z-depth image once, on its first device, and hands it to the group like any depth frame.
+float *TSDF::scan_image()
+{
+	if (!scan_ && tsdf_scanner_create(devices_[0], cfg_.im_height, cfg_.im_width, &scan_) != TSDF_OK) fail("tsdf_scanner_create", __LINE__);
+	scan_depth_.resize((size_t)cfg_.im_height * cfg_.im_width);
+	return scan_depth_.data();
+}
+
+void TSDF::IntegrateRange(float *range_im, std::vector<float> cam2world_vec)
+{
+	float cam2world[16] = {0};
+	for (size_t i = 0; i < 16 && i < cam2world_vec.size(); ++i) cam2world[i] = cam2world_vec[i];
+	if (!grp_) {
+		if (tsdf_integrate_range(vol_, range_im, cam2world) != TSDF_OK) fail("tsdf_integrate_range", __LINE__);
+		return;
+	}
+	float *depth = scan_image();
+	if (tsdf_scan_range_to_depth(scan_, cfg_.cam_K, range_im, depth) != TSDF_OK) fail("tsdf_scan_range_to_depth", __LINE__);
+	if (tsdf_group_integrate(grp_, depth, cam2world) != TSDF_OK) fail("tsdf_group_integrate", __LINE__);
+}
+
+void TSDF::IntegrateScan(const float *xyzi, size_t n, const float velo2img[12], std::vector<float> cam2world_vec)
+{
+	float cam2world[16] = {0};
+	for (size_t i = 0; i < 16 && i < cam2world_vec.size(); ++i) cam2world[i] = cam2world_vec[i];
+	if (!grp_) {
+		if (tsdf_integrate_scan(vol_, velo2img, xyzi, (int64_t)n, cam2world) != TSDF_OK) fail("tsdf_integrate_scan", __LINE__);
+		return;
+	}
+	float *depth = scan_image();
+	if (tsdf_scan_project(scan_, velo2img, cfg_.cam_K, xyzi, (int64_t)n, NULL, depth, NULL) != TSDF_OK) fail("tsdf_scan_project", __LINE__);
+	if (tsdf_group_integrate(grp_, depth, cam2world) != TSDF_OK) fail("tsdf_group_integrate", __LINE__);
 }
 
 void TSDF::Sync()
@@ -130,6 +164,8 @@ TSDF::~TSDF()
 			if ((grp_ ? tsdf_group_save_bin(grp_, name.c_str()) : tsdf_save_bin(vol_, name.c_str())) != TSDF_OK)
 				fail_in_destructor("tsdf_save_bin", __LINE__);
 		}
+		if (scan_) tsdf_scanner_destroy(scan_);
+		scan_ = NULL;
 		if (grp_) tsdf_group_destroy(grp_);
 		if (vol_) tsdf_destroy(vol_);
 		vol_ = NULL;

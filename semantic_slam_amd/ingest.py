@@ -81,6 +81,16 @@ def save_depth_png(path, raw_u16):
     Image.fromarray(a).save(path, format="PNG")
 
 
+def read_velodyne_bin(path):
+    """One KITTI velodyne scan as float32 [n, 4] (x, y, z, intensity), the file's order kept: what `tsdf_scan_project` and
+    `tsdf_integrate_scan` take.  The file is n records of four little-endian floats (ref: src/Utility.cpp:379-392, which
+    reads it the same way); a length that is no multiple of 16 bytes is refused rather than cut."""
+    raw = np.fromfile(path, dtype="<f4")
+    if raw.size % 4:
+        raise ValueError(f"{path}: {raw.size * 4} bytes is not a whole number of 16-byte points")
+    return np.ascontiguousarray(raw.reshape(-1, 4), dtype=np.float32)
+
+
 def iter_keyframes(bundle_path, associations_path, root):
     """The offline labeller's keyframe loop (ref: examples/label_instance_rgbd.cpp:78-110) as far as the TSDF needs it:
     yields (Twc [16] float32, raw depth uint16 [H, W], depth file name) per keyframe, poses from bundle.txt

@@ -304,6 +304,62 @@ class TrackScene:
 
 
 # --------------------------------------------------------------------------------------
+# a spinning lidar over the scenes above (the reference's second sensor, ref: examples/label_instance_lidar.cpp)
+# --------------------------------------------------------------------------------------
+# sensor axes (x forward, y left, z up) in camera axes (x right, y down, z forward), and a mount 8 cm above the camera and
+# 27 cm behind it: the shape of KITTI's velodyne-to-camera calibration, as round numbers
+VELO2CAM = np.array([[0.0, -1.0, 0.0, 0.0],
+                     [0.0, 0.0, -1.0, -0.08],
+                     [1.0, 0.0, 0.0, -0.27],
+                     [0.0, 0.0, 0.0, 1.0]])
+
+
+def _scene_ranges(scene, o, d):
+    """Distance along the unit rays d [n, 3] from o [3] (base frame) to the nearest surface of a SurfScene or a TrackScene;
+    inf where a ray meets none."""
+    spheres = scene.spheres if hasattr(scene, "spheres") else [(scene.center, scene.radius)]
+    t = np.full(len(d), np.inf)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for c, r in spheres:
+            oc = o - c
+            b = 2.0 * (d @ oc)
+            disc = b * b - 4.0 * (float(oc @ oc) - r * r)
+            ts = np.where(disc >= 0.0, (-b - np.sqrt(np.maximum(disc, 0.0))) / 2.0, np.inf)
+            t = np.minimum(t, np.where(ts > 0.0, ts, np.inf))
+        tw = (scene.wall_z - o[2]) / d[:, 2]
+        tw = np.where(np.isfinite(tw) & (tw > 0.0), tw, np.inf)
+        if not hasattr(scene, "spheres"):        # S-surf's wall is finite: 1.5x the volume's xy extent around the centre
+            hit = o[None, :] + np.where(np.isfinite(tw), tw, 0.0)[:, None] * d
+            ext = np.array(scene.dims[:2]) * scene.vs
+            tw = np.where(np.all(np.abs(hit[:, :2] - scene.center[:2]) <= 0.75 * ext, axis=-1), tw, np.inf)
+    return np.minimum(t, tw)
+
+
+def lidar_scan(scene, cam2base, velo2cam=VELO2CAM, n_beams=64, n_azimuth=1860, elev_deg=(2.0, -24.8), room=None):
+    """One revolution of an n_beams lidar mounted at velo2cam on the camera at cam2base, over a SurfScene or a TrackScene:
+    float32 [n, 4] (x, y, z, intensity) in the SENSOR frame, in firing order (azimuth by azimuth, beam by beam), the layout of
+    a KITTI velodyne .bin.  The defaults are the HDL-64E's: 64 beams from +2 to -24.8 degrees, 1860 firings a revolution.
+    room: None, or (x, y, z_up, z_down) half extents in metres of a box around the sensor whose inside the rays that miss
+    the scene hit -- ground and surroundings, so that every ray returns as in a real scan; without it they are dropped."""
+    az = -np.pi + 2.0 * np.pi * np.arange(n_azimuth) / n_azimuth
+    el = np.radians(np.linspace(elev_deg[0], elev_deg[1], n_beams))
+    a, e = np.meshgrid(az, el, indexing="ij")
+    d_s = np.stack([np.cos(e) * np.cos(a), np.cos(e) * np.sin(a), np.sin(e)], axis=-1).reshape(-1, 3)
+    T = np.asarray(cam2base, np.float64).reshape(4, 4) @ np.asarray(velo2cam, np.float64).reshape(4, 4)    # sensor to base
+    t = _scene_ranges(scene, T[:3, 3], d_s @ T[:3, :3].T)
+    if room is not None:
+        hi = np.array([room[0], room[1], room[2]], np.float64)
+        lo = -np.array([room[0], room[1], room[3]], np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t_exit = np.where(d_s > 0.0, hi / d_s, np.where(d_s < 0.0, lo / d_s, np.inf)).min(axis=-1)
+        t = np.minimum(t, t_exit)
+    keep = np.isfinite(t)
+    pts = t[keep, None] * d_s[keep]
+    intensity = 0.25 + 0.5 * np.abs(np.sin(7.0 * a.reshape(-1)[keep]))
+    return np.ascontiguousarray(np.concatenate([pts, intensity[:, None]], axis=1), dtype=np.float32)
+
+
+# --------------------------------------------------------------------------------------
 # S-objects: several object instances in front of a wall (instance association)
 # --------------------------------------------------------------------------------------
 OBJECTS = (("sphere", (-0.35, -0.15, 1.30), 0.12),
