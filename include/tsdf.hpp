@@ -16,6 +16,8 @@
 //                                process (tsdf_group_*): Integrate fans the frame out, the destructor gathers
 //     IntegrateRange(), IntegrateScan()   Integrate for the reference's second sensor (mSensor == 1): an image of lidar
 //                                ranges, or the Velodyne scan itself, made into z-depth on the device
+//     SetScanFill(), ClearScanFill()   fill the gaps between lidar beams in front of IntegrateRange / IntegrateScan
+//                                (csrc/tsdf_scan_fill.hip.h); off by default
 //     Download(), Sync()         read results back without destroying the object
 //     SetSaveOnDestroy(false)    skip the two files the destructor writes
 //     TSDF::ThrowOnError(true)   throw std::runtime_error instead of print + exit(1)
@@ -73,6 +75,16 @@ class TSDF
 	*/
 	void IntegrateScan(const float *xyzi, size_t n, const float velo2img[12], std::vector<float> cam2world_vec);
 
+	/** From here on IntegrateRange and IntegrateScan fill the gaps between beams in their z-depth image before it is
+	integrated (not in the reference, whose lidar call site fuses the sparse image): inverse depth is interpolated between
+	the nearest sources at most max_span_u pixels apart along rows, then at most max_span_v apart along columns, never
+	across a relative depth difference above jump_rel (tsdf_scan_fill_params in tsdf_hip.h; its defaults are 5, 8, 0.05f).
+	Parameters outside their range make the next IntegrateRange / IntegrateScan fail.  Integrate is not touched.
+	*/
+	void SetScanFill(int max_span_u, int max_span_v, float jump_rel);
+	/// back to the default: IntegrateRange and IntegrateScan integrate the sparse image as it is
+	void ClearScanFill() { fill_on_ = false; }
+
 	/// pointer to a TSDF voxel grid (host mirror; refreshed by Download() and by the destructor)
 	float * voxel_grid_TSDF;
 
@@ -105,5 +117,7 @@ class TSDF
 	tsdf_scanner *scan_;               // a multi-device object's: scans become z-depth on devices_[0], then fan out
 	std::vector<float> scan_depth_;
 	float *scan_image();               // scan_ and scan_depth_ at their first use
+	bool fill_on_;                     // SetScanFill: the lidar calls go through the library's filled forms
+	tsdf_scan_fill_params fill_;
 };
 #endif // TSDF_HIP_DROPIN_TSDF_HPP

@@ -948,6 +948,43 @@ int tsdf_scan_range_to_depth(tsdf_scanner *scanner, const float cam_K[9], const 
 int tsdf_integrate_range(tsdf_volume *vol, const float *range_host, const float cam2world[16]);
 int tsdf_integrate_scan(tsdf_volume *vol, const float velo2img[12], const float *points_host, int64_t n_points,
                         const float cam2world[16]);
+/*
+ * Filling the gaps between beams.  A 64-beam scan writes a few pixels in a hundred, in rows one beam apart; Integrate samples
+ * the nearest pixel and skips a voxel whose pixel is empty, so the sparse image fuses isolated rows of voxels.  The fill
+ * interpolates INVERSE depth between the nearest sources on either side of an empty pixel, along rows first (u pass) and
+ * then along columns (v pass, which also takes u-filled pixels as sources); it never extrapolates and never bridges a
+ * relative depth difference above jump_rel.  Off unless asked for: nothing above changes.  The rule is stated exactly in
+ * csrc/tsdf_scan_fill.hip.h and restated in tests/scan_fill_spec.py.
+ *   max_span_u, max_span_v   0 ... 16: the largest distance in pixels between two sources that the pass bridges; 0 or 1
+ *                            turns the pass off
+ *   jump_rel                 finite, >= 0: a pair a, b is bridged only if |a - b| <= jump_rel * min(a, b)
+ * tsdf_scan_fill_params_default gives 5, 8, 0.05f: the gap widths of a 64-beam revolution in a 1242 x 375 image (one beam
+ * spacing is closed, two are not) and a conservative jump; choices, not measurements.  Host only, needs no device.
+ *   tsdf_scan_fill_depth         any sparse z-depth image of the scanner's size in; the filled image into filled_host, the
+ *                                kind image (0 empty, 1 measured, 2 filled by the u pass, 3 by the v pass) into kind_host,
+ *                                the number of filled pixels into *n_filled.  Each of the three may be NULL, not all of
+ *                                them.  filled_host may be depth_host.  An unfilled pixel keeps its input bits
+ *   tsdf_scan_project_filled     tsdf_scan_project's depth image through tsdf_scan_fill_depth, without the image visiting
+ *                                the host in between; the same three outputs
+ *   tsdf_integrate_range_filled, tsdf_integrate_scan_filled
+ *                                tsdf_integrate_range and tsdf_integrate_scan, deferral included, with the fill between
+ *                                the z-depth image and the frame's slot.  Equal, bit for bit, to tsdf_integrate of the
+ *                                image tsdf_scan_fill_depth, respectively tsdf_scan_project_filled, returns
+ */
+typedef struct tsdf_scan_fill_params {
+    int32_t max_span_u, max_span_v;
+    float jump_rel;
+} tsdf_scan_fill_params;
+int tsdf_scan_fill_params_default(tsdf_scan_fill_params *out);
+int tsdf_scan_fill_depth(tsdf_scanner *scanner, const tsdf_scan_fill_params *params, const float *depth_host,
+                         float *filled_host, uint8_t *kind_host, int64_t *n_filled);
+int tsdf_scan_project_filled(tsdf_scanner *scanner, const float velo2img[12], const float cam_K[9],
+                             const tsdf_scan_fill_params *params, const float *points_host, int64_t n_points,
+                             float *depth_host, uint8_t *kind_host, int64_t *n_filled);
+int tsdf_integrate_range_filled(tsdf_volume *vol, const tsdf_scan_fill_params *params, const float *range_host,
+                                const float cam2world[16]);
+int tsdf_integrate_scan_filled(tsdf_volume *vol, const float velo2img[12], const tsdf_scan_fill_params *params,
+                               const float *points_host, int64_t n_points, const float cam2world[16]);
 
 /*
  * One grid over several devices in ONE process.  The reference's host is a C++ program that owns its TSDFs directly

@@ -43,6 +43,8 @@ ABI_SYMBOLS = [
     "tsdf_segment_depth_device", "tsdf_segment_refine_masks_device", "tsdf_segment_frame",
     "tsdf_scan_projection", "tsdf_scanner_create", "tsdf_scanner_destroy", "tsdf_scan_project", "tsdf_scan_range_to_depth",
     "tsdf_integrate_range", "tsdf_integrate_scan",
+    "tsdf_scan_fill_params_default", "tsdf_scan_fill_depth", "tsdf_scan_project_filled", "tsdf_integrate_range_filled",
+    "tsdf_integrate_scan_filled",
     "tsdf_object_origin", "tsdf_batch_create", "tsdf_batch_destroy", "tsdf_batch_size", "tsdf_batch_volume",
     "tsdf_batch_integrate_device", "tsdf_batch_sync",
     "tsdf_group_create", "tsdf_group_destroy", "tsdf_group_size", "tsdf_group_voxels", "tsdf_group_volume",
@@ -213,6 +215,11 @@ class SegmentParams(C.Structure):
     ]
 
 
+class ScanFillParams(C.Structure):
+    """Mirror of `struct tsdf_scan_fill_params` (include/tsdf_hip.h)."""
+    _fields_ = [("max_span_u", C.c_int32), ("max_span_v", C.c_int32), ("jump_rel", C.c_float)]
+
+
 TRACK_STATUS = {0: "converged", 1: "iterations exhausted", 2: "lost"}
 
 _lib = None
@@ -362,6 +369,11 @@ def load():
     L.tsdf_scan_range_to_depth.argtypes = [vp, vp, vp, vp]
     L.tsdf_integrate_range.argtypes = [vp, vp, vp]
     L.tsdf_integrate_scan.argtypes = [vp, vp, vp, C.c_int64, vp]
+    L.tsdf_scan_fill_params_default.argtypes = [vp]
+    L.tsdf_scan_fill_depth.argtypes = [vp, vp, vp, vp, vp, i64p]
+    L.tsdf_scan_project_filled.argtypes = [vp, vp, vp, vp, vp, C.c_int64, vp, vp, i64p]
+    L.tsdf_integrate_range_filled.argtypes = [vp, vp, vp, vp]
+    L.tsdf_integrate_scan_filled.argtypes = [vp, vp, vp, vp, C.c_int64, vp]
     L.tsdf_object_origin.argtypes = [C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp]
     L.tsdf_batch_create.argtypes = [C.POINTER(TsdfConfig), C.c_int32, C.POINTER(vp)]
     L.tsdf_batch_destroy.argtypes = [vp]
@@ -683,6 +695,23 @@ def scan_projection(P_rect, R_rect, R_velo, t_velo):
     return out.reshape(3, 4)
 
 
+def scan_fill_params_default():
+    """The gap fill's default parameters (include/tsdf_hip.h): max_span_u 5, max_span_v 8, jump_rel 0.05 (no device)."""
+    p = ScanFillParams()
+    check(load().tsdf_scan_fill_params_default(C.byref(p)), "tsdf_scan_fill_params_default")
+    return p
+
+
+def _scan_fill_params(params):
+    """ScanFillParams from None (the defaults), a ScanFillParams or (max_span_u, max_span_v, jump_rel)."""
+    if params is None:
+        return scan_fill_params_default()
+    if isinstance(params, ScanFillParams):
+        return params
+    su, sv, jump = params
+    return ScanFillParams(int(su), int(sv), float(jump))
+
+
 def _scan_points(points):
     """A scan as contiguous float32 [n, 4] (the KITTI .bin layout)."""
     pts = np.ascontiguousarray(points, dtype=np.float32)
@@ -741,6 +770,37 @@ class Scanner:
         out = np.empty((self.h, self.w), np.float32)
         check(self.lib.tsdf_scan_range_to_depth(self._h, k.ctypes.data, r.ctypes.data, out.ctypes.data), "tsdf_scan_range_to_depth")
         return out
+
+    def fill_depth(self, depth, params=None, want_depth=True, want_kind=True, want_count=True, in_place=False):
+        """(filled depth [h, w] or None, kind [h, w] uint8 or None, filled pixels or None) of a sparse z-depth image [h, w];
+        in_place writes the filled image over `depth` itself (a contiguous float32 array)."""
+        d = depth if in_place else np.ascontiguousarray(depth, dtype=np.float32)
+        if in_place and not (isinstance(d, np.ndarray) and d.dtype == np.float32 and d.flags["C_CONTIGUOUS"] and want_depth):
+            raise ValueError("in_place needs a contiguous float32 array and want_depth")
+        if d.shape != (self.h, self.w):
+            raise ValueError(f"the depth image is {d.shape}, the scanner's {(self.h, self.w)}")
+        p = _scan_fill_params(params)
+        out = d if in_place else (np.empty((self.h, self.w), np.float32) if want_depth else None)
+        kind = np.empty((self.h, self.w), np.uint8) if want_kind else None
+        n = C.c_int64(-1)
+        check(self.lib.tsdf_scan_fill_depth(self._h, C.addressof(p), d.ctypes.data, None if out is None else out.ctypes.data,
+                                            None if kind is None else kind.ctypes.data, C.byref(n) if want_count else None),
+              "tsdf_scan_fill_depth")
+        return out, kind, (int(n.value) if want_count else None)
+
+    def project_filled(self, points, velo2img, K, params=None, want_depth=True, want_kind=True, want_count=True):
+        """project()'s depth image through fill_depth() without leaving the device: (filled depth, kind, filled pixels)."""
+        pts = _scan_points(points)
+        m, k = _f32(velo2img, 12), _f32(K, 9)
+        p = _scan_fill_params(params)
+        dep = np.empty((self.h, self.w), np.float32) if want_depth else None
+        kind = np.empty((self.h, self.w), np.uint8) if want_kind else None
+        n = C.c_int64(-1)
+        check(self.lib.tsdf_scan_project_filled(self._h, m.ctypes.data, k.ctypes.data, C.addressof(p),
+                                                pts.ctypes.data if len(pts) else None, len(pts),
+                                                None if dep is None else dep.ctypes.data, None if kind is None else kind.ctypes.data,
+                                                C.byref(n) if want_count else None), "tsdf_scan_project_filled")
+        return dep, kind, (int(n.value) if want_count else None)
 
 
 def selftest_round(device=0):
@@ -885,6 +945,21 @@ class Volume:
         m, p = _f32(velo2img, 12), _f32(cam2world, 16)
         check(self.lib.tsdf_integrate_scan(self._h, m.ctypes.data, pts.ctypes.data if len(pts) else None, len(pts), p.ctypes.data),
               "tsdf_integrate_scan")
+
+    def integrate_range_filled(self, range_host, cam2world, params=None):
+        """integrate_range() with the gaps between beams filled on the device (Scanner.fill_depth's rule)."""
+        r = _f32(range_host, self.cfg.im_height * self.cfg.im_width)
+        p = _f32(cam2world, 16)
+        f = _scan_fill_params(params)
+        check(self.lib.tsdf_integrate_range_filled(self._h, C.addressof(f), r.ctypes.data, p.ctypes.data), "tsdf_integrate_range_filled")
+
+    def integrate_scan_filled(self, points, velo2img, cam2world, params=None):
+        """integrate_scan() with the gaps between beams filled on the device (Scanner.fill_depth's rule)."""
+        pts = _scan_points(points)
+        m, p = _f32(velo2img, 12), _f32(cam2world, 16)
+        f = _scan_fill_params(params)
+        check(self.lib.tsdf_integrate_scan_filled(self._h, m.ctypes.data, C.addressof(f), pts.ctypes.data if len(pts) else None, len(pts),
+                                                  p.ctypes.data), "tsdf_integrate_scan_filled")
 
     def integrate_u16(self, raw_u16, cam2world, depth_factor=5000.0, row_step=1, col_step=1):
         """Raw 16-bit frame: half-size H2D copy, conversion (and optional subsampling) on the device."""

@@ -49,6 +49,7 @@
 #include "tsdf_associate.hip.h"
 #include "tsdf_segment.hip.h"
 #include "tsdf_scan.hip.h"
+#include "tsdf_scan_fill.hip.h"
 #ifdef TSDF_EXPERIMENTS
 #include "tsdf_experiments.hip.h"
 #endif
@@ -1717,6 +1718,7 @@ int tsdf_upload_colour(tsdf_volume *v, const uint32_t *colour_host)
 #include "tsdf_batch_track_host.hip.h"
 #include "tsdf_segment_host.hip.h"
 #include "tsdf_scan_host.hip.h"
+#include "tsdf_scan_fill_host.hip.h"
 #include "tsdf_extract_host.hip.h"
 #include "tsdf_group.hip.h"
 #include "tsdf_diag.hip.h"

@@ -29,7 +29,7 @@ void TSDF::fail(const char *what, int line) const
 }
 
 TSDF::TSDF(int h, int w, int MOid, std::vector<float> base2world_, std::vector<float> origin)
-	: voxel_grid_TSDF(NULL), voxel_grid_weight(NULL), vol_(NULL), grp_(NULL), save_on_destroy_(true), scan_(NULL)
+	: voxel_grid_TSDF(NULL), voxel_grid_weight(NULL), vol_(NULL), grp_(NULL), save_on_destroy_(true), scan_(NULL), fill_on_(false), fill_()
 {
 	tsdf_config_default(&cfg_, h, w);  // 200^3 @ 4 mm, trunc 20 mm, TUM K (ref: include/tsdf.hpp:63-67,96)
 	cfg_.id = MOid;
@@ -39,14 +39,14 @@ TSDF::TSDF(int h, int w, int MOid, std::vector<float> base2world_, std::vector<f
 }
 
 TSDF::TSDF(const tsdf_config &cfg)
-	: voxel_grid_TSDF(NULL), voxel_grid_weight(NULL), cfg_(cfg), vol_(NULL), grp_(NULL), save_on_destroy_(true), scan_(NULL)
+	: voxel_grid_TSDF(NULL), voxel_grid_weight(NULL), cfg_(cfg), vol_(NULL), grp_(NULL), save_on_destroy_(true), scan_(NULL), fill_on_(false), fill_()
 {
 	init();
 }
 
 TSDF::TSDF(const tsdf_config &cfg, const std::vector<int> &devices)
 	: voxel_grid_TSDF(NULL), voxel_grid_weight(NULL), cfg_(cfg), vol_(NULL), grp_(NULL), devices_(devices),
-	  save_on_destroy_(true), scan_(NULL)
+	  save_on_destroy_(true), scan_(NULL), fill_on_(false), fill_()
 {
 	cfg_.z_begin = 0;
 	cfg_.z_end = cfg_.dim_z;
@@ -89,16 +89,27 @@ float *TSDF::scan_image()
 	return scan_depth_.data();
 }
 
+void TSDF::SetScanFill(int max_span_u, int max_span_v, float jump_rel)
+{
+	fill_.max_span_u = max_span_u;
+	fill_.max_span_v = max_span_v;
+	fill_.jump_rel = jump_rel;
+	fill_on_ = true;
+}
+
 void TSDF::IntegrateRange(float *range_im, std::vector<float> cam2world_vec)
 {
 	float cam2world[16] = {0};
 	for (size_t i = 0; i < 16 && i < cam2world_vec.size(); ++i) cam2world[i] = cam2world_vec[i];
 	if (!grp_) {
-		if (tsdf_integrate_range(vol_, range_im, cam2world) != TSDF_OK) fail("tsdf_integrate_range", __LINE__);
+		if (fill_on_) {
+			if (tsdf_integrate_range_filled(vol_, &fill_, range_im, cam2world) != TSDF_OK) fail("tsdf_integrate_range_filled", __LINE__);
+		} else if (tsdf_integrate_range(vol_, range_im, cam2world) != TSDF_OK) fail("tsdf_integrate_range", __LINE__);
 		return;
 	}
 	float *depth = scan_image();
 	if (tsdf_scan_range_to_depth(scan_, cfg_.cam_K, range_im, depth) != TSDF_OK) fail("tsdf_scan_range_to_depth", __LINE__);
+	if (fill_on_ && tsdf_scan_fill_depth(scan_, &fill_, depth, depth, NULL, NULL) != TSDF_OK) fail("tsdf_scan_fill_depth", __LINE__);
 	if (tsdf_group_integrate(grp_, depth, cam2world) != TSDF_OK) fail("tsdf_group_integrate", __LINE__);
 }
 
@@ -107,11 +118,15 @@ void TSDF::IntegrateScan(const float *xyzi, size_t n, const float velo2img[12], 
 	float cam2world[16] = {0};
 	for (size_t i = 0; i < 16 && i < cam2world_vec.size(); ++i) cam2world[i] = cam2world_vec[i];
 	if (!grp_) {
-		if (tsdf_integrate_scan(vol_, velo2img, xyzi, (int64_t)n, cam2world) != TSDF_OK) fail("tsdf_integrate_scan", __LINE__);
+		if (fill_on_) {
+			if (tsdf_integrate_scan_filled(vol_, velo2img, &fill_, xyzi, (int64_t)n, cam2world) != TSDF_OK) fail("tsdf_integrate_scan_filled", __LINE__);
+		} else if (tsdf_integrate_scan(vol_, velo2img, xyzi, (int64_t)n, cam2world) != TSDF_OK) fail("tsdf_integrate_scan", __LINE__);
 		return;
 	}
 	float *depth = scan_image();
-	if (tsdf_scan_project(scan_, velo2img, cfg_.cam_K, xyzi, (int64_t)n, NULL, depth, NULL) != TSDF_OK) fail("tsdf_scan_project", __LINE__);
+	if (fill_on_) {
+		if (tsdf_scan_project_filled(scan_, velo2img, cfg_.cam_K, &fill_, xyzi, (int64_t)n, depth, NULL, NULL) != TSDF_OK) fail("tsdf_scan_project_filled", __LINE__);
+	} else if (tsdf_scan_project(scan_, velo2img, cfg_.cam_K, xyzi, (int64_t)n, NULL, depth, NULL) != TSDF_OK) fail("tsdf_scan_project", __LINE__);
 	if (tsdf_group_integrate(grp_, depth, cam2world) != TSDF_OK) fail("tsdf_group_integrate", __LINE__);
 }
 

@@ -12,6 +12,8 @@ struct tsdf_scanner {
     DevPtr<float> d_images;          // range | depth
     DevPtr<uint32_t> d_counts;       // written pixels per workgroup of scan_resolve
     HostPtr<float> h_images;         // the pinned mirror of d_images, and behind it of d_counts
+    DevPtr<char> d_fill;             // the gap fill's (tsdf_scan_fill_host.hip.h, at the first call that fills): filled depth |
+    HostPtr<char> h_fill;            // one count per tile | kind; and its pinned mirror
 };
 
 namespace {
