@@ -18,6 +18,8 @@
 //                                ranges, or the Velodyne scan itself, made into z-depth on the device
 //     SetScanFill(), ClearScanFill()   fill the gaps between lidar beams in front of IntegrateRange / IntegrateScan
 //                                (csrc/tsdf_scan_fill.hip.h); off by default
+//     SetScanGround(), ClearScanGround()   mark the ground of a scan and keep it out of (or alone in) IntegrateScan
+//                                (csrc/tsdf_scan_ground.hip.h); off by default
 //     Download(), Sync()         read results back without destroying the object
 //     SetSaveOnDestroy(false)    skip the two files the destructor writes
 //     TSDF::ThrowOnError(true)   throw std::runtime_error instead of print + exit(1)
@@ -85,6 +87,18 @@ class TSDF
 	/// back to the default: IntegrateRange and IntegrateScan integrate the sparse image as it is
 	void ClearScanFill() { fill_on_ = false; }
 
+	/** From here on IntegrateScan marks the ground of each scan on the device first (not in the reference, whose lidar call
+	site has projectPointCloud and groundRemoval dormant: ref: examples/label_instance_lidar.cpp:85-91, src/Utility.cpp:452-553)
+	and integrates only the points that select keeps: TSDF_SCAN_DROP_GROUND everything but the ground returns,
+	TSDF_SCAN_ONLY_GROUND nothing else (tsdf_scan_ground_params in tsdf_hip.h; tsdf_scan_ground_params_default gives the
+	reference's literals, which do not fit an HDL-64E: see there).  With SetScanFill the fill runs behind the selection.
+	Parameters outside their range make the next IntegrateScan fail.  IntegrateRange takes an image, which has no points
+	to mark, and is unaffected; so is Integrate.
+	*/
+	void SetScanGround(const tsdf_scan_ground_params &params, int select = TSDF_SCAN_DROP_GROUND);
+	/// back to the default: IntegrateScan integrates every point
+	void ClearScanGround() { ground_on_ = false; }
+
 	/// pointer to a TSDF voxel grid (host mirror; refreshed by Download() and by the destructor)
 	float * voxel_grid_TSDF;
 
@@ -119,5 +133,8 @@ class TSDF
 	float *scan_image();               // scan_ and scan_depth_ at their first use
 	bool fill_on_;                     // SetScanFill: the lidar calls go through the library's filled forms
 	tsdf_scan_fill_params fill_;
+	bool ground_on_;                   // SetScanGround: IntegrateScan goes through the library's selecting forms
+	tsdf_scan_ground_params ground_;
+	int ground_select_;
 };
 #endif // TSDF_HIP_DROPIN_TSDF_HPP

@@ -985,6 +985,70 @@ int tsdf_integrate_range_filled(tsdf_volume *vol, const tsdf_scan_fill_params *p
                                 const float cam2world[16]);
 int tsdf_integrate_scan_filled(tsdf_volume *vol, const float velo2img[12], const tsdf_scan_fill_params *params,
                                const float *points_host, int64_t n_points, const float cam2world[16]);
+/*
+ * Marking the ground of a scan.  The reference's lidar front end sorts a scan into a spherical image of n_rings x n_columns
+ * cells (ref: src/Utility.cpp:452-496, projectPointCloud) and calls a cell ground when the step to the cell one ring above
+ * it is nearly level (ref: :498-553, groundRemoval); both run on the CPU and are dormant at its call site
+ * (ref: examples/label_instance_lidar.cpp:85-91).  Here both run on the device in front of the camera splat, so that a scan
+ * can be projected or fused WITHOUT its ground returns, or with nothing else.  Off unless asked for: nothing above changes.
+ * The rule uses no transcendental function on the device (the angles become tables of tangents, cosines and sines, built on
+ * the host) and is stated exactly in csrc/tsdf_scan_ground.hip.h and restated in tests/scan_ground_spec.py.
+ *   n_rings, n_columns      2 ... 128 and 4 ... 16384: the spherical image.  Ring r holds elevations from r * ang_res_y -
+ *                           ang_bottom (inclusive) up to the next ring's; column c holds azimuths atan2(y, x) from
+ *                           (c - n_columns / 2 - 0.5) * 360 / n_columns degrees (inclusive, integer n_columns / 2) up to the
+ *                           next column's, x forward and y left, wrapping around
+ *   ang_res_y, ang_bottom   degrees; ang_res_y > 0, every ring boundary strictly inside (-90, 90)
+ *   mount_deg, tol_deg      a pair of cells is level when the step from the lower cell's point to the upper one's rises by
+ *                           mount_deg +- tol_deg; tol_deg >= 0, |mount_deg| + tol_deg < 90
+ *   min_range               >= 0: a point nearer than this has no cell
+ *   ground_rings            0 ... n_rings - 1: the rings whose step to the ring above is looked at (0 marks nothing)
+ *   mark_upper              0 or 1: whether a level step also marks its upper cell (ref: :531, commented out there).  The
+ *                           cell's own step comes first, as in the reference's ascending loop: a cell below ground_rings
+ *                           whose upper neighbour is empty is -1 even when the step below it is level; a cell at or above
+ *                           ground_rings has no step of its own and is 1 exactly when the step below it is looked at and level
+ * Every value must be finite.  tsdf_scan_ground_params_default gives the reference's literals (ref: include/Utility.hpp:52-58,
+ * src/Utility.cpp:484,529): 64, 4500, 26.9 / 63, 15.1, 0, 2.5, 0.1, 63, 0.  Those cover -15.1 ... +11.8 degrees, NOT the
+ * HDL-64E's +2 ... -24.8; for that sensor, with each beam at its ring's centre: ang_res_y = 26.8 / 63, ang_bottom = 24.8 +
+ * ang_res_y / 2.  Host only, needs no device.
+ * Where several points share a cell the one with the highest index is the cell's point, as for the camera image.  A point's
+ * flag is 2 when it has no cell (not finite, on the z axis, nearer than min_range, above or below the rings), 1 when its
+ * cell is ground -- every point of the cell, not only the cell's own --, else 0.
+ *   tsdf_scan_mark_ground        flags_host: n_points bytes; state_host: n_rings x n_columns int8 (1 ground, 0 not, -1 the
+ *                                cell or the one above it is empty); winner_host: n_rings x n_columns int32, the index of
+ *                                the cell's point or -1; counts = {points with a cell, occupied cells, ground cells, ground
+ *                                points}.  Each of the four may be NULL, not all of them
+ *   tsdf_scan_project_ground     tsdf_scan_project of the points that select keeps (TSDF_SCAN_DROP_GROUND: flag != 1,
+ *                                TSDF_SCAN_ONLY_GROUND: flag == 1), in their order: range_host and *n_pixels as
+ *                                tsdf_scan_project gives them; fill_params NULL: depth_host likewise (kind_host and
+ *                                n_filled must be NULL); otherwise depth_host, kind_host and *n_filled as
+ *                                tsdf_scan_project_filled gives them.  *n_selected: the points kept, in the image or
+ *                                not.  Every output may be NULL, not all of them
+ *   tsdf_integrate_scan_ground   tsdf_integrate_scan (fill_params NULL) or tsdf_integrate_scan_filled of the points that
+ *                                select keeps, deferral included.  Equal, bit for bit, to tsdf_integrate of
+ *                                tsdf_scan_project_ground's depth_host
+ */
+typedef struct tsdf_scan_ground_params {
+    int32_t n_rings, n_columns;
+    float ang_res_y, ang_bottom;
+    float mount_deg, tol_deg;
+    float min_range;
+    int32_t ground_rings;
+    int32_t mark_upper;
+} tsdf_scan_ground_params;
+#define TSDF_SCAN_DROP_GROUND 0
+#define TSDF_SCAN_ONLY_GROUND 1
+int tsdf_scan_ground_params_default(tsdf_scan_ground_params *out);
+int tsdf_scan_mark_ground(tsdf_scanner *scanner, const tsdf_scan_ground_params *params, const float *points_host,
+                          int64_t n_points, uint8_t *flags_host, int8_t *state_host, int32_t *winner_host,
+                          int64_t counts[4]);
+int tsdf_scan_project_ground(tsdf_scanner *scanner, const float velo2img[12], const float cam_K[9],
+                             const tsdf_scan_ground_params *ground_params, int32_t select,
+                             const tsdf_scan_fill_params *fill_params, const float *points_host, int64_t n_points,
+                             float *range_host, float *depth_host, uint8_t *kind_host, int64_t *n_pixels,
+                             int64_t *n_filled, int64_t *n_selected);
+int tsdf_integrate_scan_ground(tsdf_volume *vol, const float velo2img[12], const tsdf_scan_ground_params *ground_params,
+                               int32_t select, const tsdf_scan_fill_params *fill_params, const float *points_host,
+                               int64_t n_points, const float cam2world[16]);
 
 /*
  * One grid over several devices in ONE process.  The reference's host is a C++ program that owns its TSDFs directly

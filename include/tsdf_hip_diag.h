@@ -153,6 +153,19 @@ int tsdf_brick_shape(const tsdf_volume *vol, int32_t shape_out[3]);
 /* The shape tsdf_create would choose for this grid (host arithmetic only: needs no device). */
 int tsdf_default_brick_shape(const tsdf_config *cfg, int32_t shape_out[3]);
 
+/* ---- tables ---- */
+
+/*
+ * The tables a scanner or a handle searches when it marks the ground of a scan under *params (csrc/scan_ground_tables.h; the
+ * same builder, so the same bits): ring_tan_out n_rings + 1 floats, col_cos_out and col_sin_out n_columns floats each,
+ * slopes_out = {tan(mount - tol), tan(mount + tol)}, and per quadrant of the (x, y) plane the first column of its run of
+ * column boundaries and the run's length.  tests/scan_ground_spec.py takes them from here, so that it is held to the rule
+ * and not to a second libm.  Host arithmetic only: needs no device.
+ */
+int tsdf_scan_ground_tables(const tsdf_scan_ground_params *params, float *ring_tan_out, float *col_cos_out,
+                            float *col_sin_out, float slopes_out[2], int32_t quad_first_out[4],
+                            int32_t quad_len_out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,8 @@ ABI_SYMBOLS = [
     "tsdf_integrate_range", "tsdf_integrate_scan",
     "tsdf_scan_fill_params_default", "tsdf_scan_fill_depth", "tsdf_scan_project_filled", "tsdf_integrate_range_filled",
     "tsdf_integrate_scan_filled",
+    "tsdf_scan_ground_params_default", "tsdf_scan_mark_ground", "tsdf_scan_project_ground", "tsdf_integrate_scan_ground",
+    "tsdf_scan_ground_tables",
     "tsdf_object_origin", "tsdf_batch_create", "tsdf_batch_destroy", "tsdf_batch_size", "tsdf_batch_volume",
     "tsdf_batch_integrate_device", "tsdf_batch_sync",
     "tsdf_group_create", "tsdf_group_destroy", "tsdf_group_size", "tsdf_group_voxels", "tsdf_group_volume",
@@ -58,6 +60,7 @@ DIAG_SYMBOLS = [
     "tsdf_selftest_fastdiv", "tsdf_selftest_fastdiv_band", "tsdf_selftest_round", "tsdf_selftest_tile_tables",
     "tsdf_shortcut_stats", "tsdf_brick_list_stats", "tsdf_classification_info", "tsdf_store_stats", "tsdf_summary_stats", "tsdf_summary_words", "tsdf_frames_per_launch", "tsdf_last_cam2base",
     "tsdf_set_kernel_variant", "tsdf_set_brick_shape", "tsdf_brick_shape", "tsdf_default_brick_shape",
+    "tsdf_scan_ground_tables",
 ]
 
 
@@ -220,6 +223,15 @@ class ScanFillParams(C.Structure):
     _fields_ = [("max_span_u", C.c_int32), ("max_span_v", C.c_int32), ("jump_rel", C.c_float)]
 
 
+class ScanGroundParams(C.Structure):
+    """Mirror of `struct tsdf_scan_ground_params` (include/tsdf_hip.h)."""
+    _fields_ = [("n_rings", C.c_int32), ("n_columns", C.c_int32), ("ang_res_y", C.c_float), ("ang_bottom", C.c_float),
+                ("mount_deg", C.c_float), ("tol_deg", C.c_float), ("min_range", C.c_float), ("ground_rings", C.c_int32),
+                ("mark_upper", C.c_int32)]
+
+
+SCAN_DROP_GROUND, SCAN_ONLY_GROUND = 0, 1       # tsdf_scan_project_ground's and tsdf_integrate_scan_ground's `select`
+
 TRACK_STATUS = {0: "converged", 1: "iterations exhausted", 2: "lost"}
 
 _lib = None
@@ -374,6 +386,11 @@ def load():
     L.tsdf_scan_project_filled.argtypes = [vp, vp, vp, vp, vp, C.c_int64, vp, vp, i64p]
     L.tsdf_integrate_range_filled.argtypes = [vp, vp, vp, vp]
     L.tsdf_integrate_scan_filled.argtypes = [vp, vp, vp, vp, C.c_int64, vp]
+    L.tsdf_scan_ground_params_default.argtypes = [vp]
+    L.tsdf_scan_mark_ground.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, vp]
+    L.tsdf_scan_project_ground.argtypes = [vp, vp, vp, vp, C.c_int32, vp, vp, C.c_int64, vp, vp, vp, i64p, i64p, i64p]
+    L.tsdf_integrate_scan_ground.argtypes = [vp, vp, vp, C.c_int32, vp, vp, C.c_int64, vp]
+    L.tsdf_scan_ground_tables.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.tsdf_object_origin.argtypes = [C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp]
     L.tsdf_batch_create.argtypes = [C.POINTER(TsdfConfig), C.c_int32, C.POINTER(vp)]
     L.tsdf_batch_destroy.argtypes = [vp]
@@ -712,6 +729,44 @@ def _scan_fill_params(params):
     return ScanFillParams(int(su), int(sv), float(jump))
 
 
+def scan_ground_params_default():
+    """The ground marking's default parameters, the reference's literals (include/tsdf_hip.h): 64 x 4500 cells, 26.9 / 63 degrees
+    per ring from -15.1, level within 0 +- 2.5 degrees, ranges from 0.1, 63 ring pairs, the upper cell not marked (no device)."""
+    p = ScanGroundParams()
+    check(load().tsdf_scan_ground_params_default(C.byref(p)), "tsdf_scan_ground_params_default")
+    return p
+
+
+def _scan_ground_params(params):
+    """ScanGroundParams from None (the defaults), a ScanGroundParams, a dict of its fields over the defaults or the nine values."""
+    if params is None:
+        return scan_ground_params_default()
+    if isinstance(params, ScanGroundParams):
+        return params
+    if isinstance(params, dict):
+        p = scan_ground_params_default()
+        for k, v in params.items():
+            if k not in dict(ScanGroundParams._fields_):
+                raise ValueError(f"tsdf_scan_ground_params has no field {k}")
+            setattr(p, k, v)
+        return p
+    nr, nc, res, bottom, mount, tol, min_range, rings, upper = params
+    return ScanGroundParams(int(nr), int(nc), float(res), float(bottom), float(mount), float(tol), float(min_range), int(rings), int(upper))
+
+
+def scan_ground_tables(params=None):
+    """The tables the library searches under these parameters (tsdf_scan_ground_tables; no device): {"T": [n_rings + 1],
+    "C", "S": [n_columns], "tlo", "thi": float32, "first", "len": [4] int32 -- the quadrants' runs of column boundaries}."""
+    p = _scan_ground_params(params)
+    if not (0 < p.n_rings <= 1 << 20 and 0 < p.n_columns <= 1 << 20):
+        raise TsdfError(f"tsdf_scan_ground_tables: n_rings = {p.n_rings}, n_columns = {p.n_columns}")
+    T, Cc, S = np.zeros(p.n_rings + 1, np.float32), np.zeros(p.n_columns, np.float32), np.zeros(p.n_columns, np.float32)
+    slopes, first, length = np.zeros(2, np.float32), np.zeros(4, np.int32), np.zeros(4, np.int32)
+    check(load().tsdf_scan_ground_tables(C.addressof(p), T.ctypes.data, Cc.ctypes.data, S.ctypes.data, slopes.ctypes.data,
+                                         first.ctypes.data, length.ctypes.data), "tsdf_scan_ground_tables")
+    return {"T": T, "C": Cc, "S": S, "tlo": slopes[0], "thi": slopes[1], "first": first, "len": length}
+
+
 def _scan_points(points):
     """A scan as contiguous float32 [n, 4] (the KITTI .bin layout)."""
     pts = np.ascontiguousarray(points, dtype=np.float32)
@@ -801,6 +856,47 @@ class Scanner:
                                                 None if dep is None else dep.ctypes.data, None if kind is None else kind.ctypes.data,
                                                 C.byref(n) if want_count else None), "tsdf_scan_project_filled")
         return dep, kind, (int(n.value) if want_count else None)
+
+
+    def mark_ground(self, points, params=None, want_flags=True, want_state=True, want_winner=True, want_counts=True):
+        """The ground of a scan [n, 4]: (flags [n] uint8: 0 not ground, 1 ground, 2 no cell; state [n_rings, n_columns] int8: 1
+        ground, 0 not, -1 the cell or the one above it is empty; winner [n_rings, n_columns] int32: the cell's point or -1;
+        counts [4]: points with a cell, occupied cells, ground cells, ground points), None for what was not asked for."""
+        pts = _scan_points(points)
+        p = _scan_ground_params(params)
+        shape = (max(p.n_rings, 0), max(p.n_columns, 0))
+        flags = np.empty(len(pts), np.uint8) if want_flags else None
+        state = np.empty(shape, np.int8) if want_state else None
+        winner = np.empty(shape, np.int32) if want_winner else None
+        counts = np.full(4, -1, np.int64) if want_counts else None
+        check(self.lib.tsdf_scan_mark_ground(self._h, C.addressof(p), pts.ctypes.data if len(pts) else None, len(pts),
+                                             None if flags is None else flags.ctypes.data, None if state is None else state.ctypes.data,
+                                             None if winner is None else winner.ctypes.data,
+                                             None if counts is None else counts.ctypes.data), "tsdf_scan_mark_ground")
+        return flags, state, winner, counts
+
+    def project_ground(self, points, velo2img, K, ground_params=None, select=SCAN_DROP_GROUND, fill_params=None, fill=False,
+                       want_range=True, want_depth=True, want_kind=True, want_counts=True):
+        """project() -- or, with fill or fill_params, project_filled() -- of the points of a scan that `select` keeps:
+        {"range", "depth", "kind" (filled only), "n_pixels", "n_filled" (filled only), "n_selected"}, None for what was not
+        asked for."""
+        pts = _scan_points(points)
+        m, k = _f32(velo2img, 12), _f32(K, 9)
+        g = _scan_ground_params(ground_params)
+        f = _scan_fill_params(fill_params) if (fill or fill_params is not None) else None
+        rng = np.empty((self.h, self.w), np.float32) if want_range else None
+        dep = np.empty((self.h, self.w), np.float32) if want_depth else None
+        kind = np.empty((self.h, self.w), np.uint8) if (want_kind and f is not None) else None
+        n_px, n_fill, n_sel = C.c_int64(-1), C.c_int64(-1), C.c_int64(-1)
+        check(self.lib.tsdf_scan_project_ground(self._h, m.ctypes.data, k.ctypes.data, C.addressof(g), int(select),
+                                                None if f is None else C.addressof(f), pts.ctypes.data if len(pts) else None, len(pts),
+                                                None if rng is None else rng.ctypes.data, None if dep is None else dep.ctypes.data,
+                                                None if kind is None else kind.ctypes.data, C.byref(n_px) if want_counts else None,
+                                                C.byref(n_fill) if (want_counts and f is not None) else None,
+                                                C.byref(n_sel) if want_counts else None), "tsdf_scan_project_ground")
+        return {"range": rng, "depth": dep, "kind": kind, "n_pixels": int(n_px.value) if want_counts else None,
+                "n_filled": int(n_fill.value) if (want_counts and f is not None) else None,
+                "n_selected": int(n_sel.value) if want_counts else None}
 
 
 def selftest_round(device=0):
@@ -952,6 +1048,18 @@ class Volume:
         p = _f32(cam2world, 16)
         f = _scan_fill_params(params)
         check(self.lib.tsdf_integrate_range_filled(self._h, C.addressof(f), r.ctypes.data, p.ctypes.data), "tsdf_integrate_range_filled")
+
+    def integrate_scan_ground(self, points, velo2img, cam2world, ground_params=None, select=SCAN_DROP_GROUND, fill_params=None,
+                              fill=False):
+        """integrate_scan() -- or, with fill or fill_params, integrate_scan_filled() -- of the points that `select` keeps
+        (Scanner.mark_ground's rule)."""
+        pts = _scan_points(points)
+        m, p = _f32(velo2img, 12), _f32(cam2world, 16)
+        g = _scan_ground_params(ground_params)
+        f = _scan_fill_params(fill_params) if (fill or fill_params is not None) else None
+        check(self.lib.tsdf_integrate_scan_ground(self._h, m.ctypes.data, C.addressof(g), int(select), None if f is None else C.addressof(f),
+                                                  pts.ctypes.data if len(pts) else None, len(pts), p.ctypes.data),
+              "tsdf_integrate_scan_ground")
 
     def integrate_scan_filled(self, points, velo2img, cam2world, params=None):
         """integrate_scan() with the gaps between beams filled on the device (Scanner.fill_depth's rule)."""

@@ -30,6 +30,7 @@
 #include "pose_math.h"
 #include "host_derive.h"
 #include "launch_geometry.h"
+#include "scan_ground_tables.h"
 #include "host_copy.h"
 #include "hip_owned.h"
 #include "frame_store.h"
@@ -50,6 +51,7 @@
 #include "tsdf_segment.hip.h"
 #include "tsdf_scan.hip.h"
 #include "tsdf_scan_fill.hip.h"
+#include "tsdf_scan_ground.hip.h"
 #ifdef TSDF_EXPERIMENTS
 #include "tsdf_experiments.hip.h"
 #endif
@@ -122,6 +124,28 @@ struct ScanStage {
     HostBuf<float4> h_pts;
     Event pts_read;
     bool pts_in_use = false;
+};
+
+// What marking a scan's ground needs on a device (tsdf_scan_ground_host.hip.h), held like a ScanStage and beside one, whose
+// points it reads; allocated at the first call that marks, the grid's parts again when n_rings / n_columns grow.  keys: one
+// 64-bit key per cell of the spherical image, all zero between calls (cleared behind ground_mark; keys_clean as in ScanStage).
+// tables: T | C | S of `params`, in HBM and pinned, rebuilt when a call brings other parameters.  cells: one per point.
+// counts: one word per workgroup of the counting kernels, with its pinned mirror.  Whatever regrows or refills any of this
+// first waits for the ScanStage's pts_read, recorded behind the last kernel of a call.
+struct ScanGroundStage {
+    tsdf_scan_ground_params params = {};
+    bool have_tables = false;
+    tsdf_host::ScanGroundTables tables;
+    DevBuf<unsigned long long> d_keys;
+    bool keys_clean = false;
+    DevBuf<float> d_tables;
+    HostBuf<float> h_tables;
+    DevBuf<int8_t> d_state;
+    DevBuf<int32_t> d_winner;
+    DevBuf<uint32_t> d_cells;
+    DevBuf<uint8_t> d_flags;
+    DevBuf<uint32_t> d_counts;
+    HostBuf<char> h_out;             // what tsdf_scan_mark_ground brings back: states | winners | flags | counts
 };
 
 struct tsdf_volume {
@@ -230,6 +254,7 @@ struct tsdf_volume {
     HostPtr<unsigned long long> h_extent;
     // lidar scans (tsdf_integrate_scan), allocated on first use: a handle that never sees a scan allocates nothing
     ScanStage scan;
+    ScanGroundStage ground;          // ... and the ground marking in front of it (tsdf_integrate_scan_ground), likewise
 };
 
 using tsdf_host::kBatchSideStreams;
@@ -1719,6 +1744,7 @@ int tsdf_upload_colour(tsdf_volume *v, const uint32_t *colour_host)
 #include "tsdf_segment_host.hip.h"
 #include "tsdf_scan_host.hip.h"
 #include "tsdf_scan_fill_host.hip.h"
+#include "tsdf_scan_ground_host.hip.h"
 #include "tsdf_extract_host.hip.h"
 #include "tsdf_group.hip.h"
 #include "tsdf_diag.hip.h"

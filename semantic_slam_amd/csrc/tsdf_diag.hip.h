@@ -433,4 +433,23 @@ int tsdf_default_brick_shape(const tsdf_config *cfg, int32_t shape_out[3])
     return TSDF_OK;
 }
 
+// ---- tables ------------------------------------------------------------------------------------------------------------
+
+int tsdf_scan_ground_tables(const tsdf_scan_ground_params *params, float *ring_tan_out, float *col_cos_out, float *col_sin_out,
+                            float slopes_out[2], int32_t quad_first_out[4], int32_t quad_len_out[4])
+{
+    const char *who = "tsdf_scan_ground_tables";
+    if (!params || !ring_tan_out || !col_cos_out || !col_sin_out || !slopes_out || !quad_first_out || !quad_len_out)
+        return fail(TSDF_ERR_INVALID, "%s: NULL argument", who);
+    tsdf_host::ScanGroundTables t;
+    const tsdf_host::GroundLimit l = tsdf_host::build_scan_ground_tables(*params, t);      // the builder the scanners use
+    if (l != tsdf_host::GroundLimit::Ok) return fail(TSDF_ERR_INVALID, "%s: ground_params: %s", who, tsdf_host::ground_limit_text(l));
+    std::memcpy(ring_tan_out, t.T.data(), t.T.size() * sizeof(float));
+    std::memcpy(col_cos_out, t.C.data(), t.C.size() * sizeof(float));
+    std::memcpy(col_sin_out, t.S.data(), t.S.size() * sizeof(float));
+    slopes_out[0] = t.tlo; slopes_out[1] = t.thi;
+    for (int q = 0; q < 4; ++q) { quad_first_out[q] = t.first[q]; quad_len_out[q] = t.len[q]; }
+    return TSDF_OK;
+}
+
 }  // extern "C"

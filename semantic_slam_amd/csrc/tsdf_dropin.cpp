@@ -29,7 +29,7 @@ void TSDF::fail(const char *what, int line) const
 }
 
 TSDF::TSDF(int h, int w, int MOid, std::vector<float> base2world_, std::vector<float> origin)
-	: voxel_grid_TSDF(NULL), voxel_grid_weight(NULL), vol_(NULL), grp_(NULL), save_on_destroy_(true), scan_(NULL), fill_on_(false), fill_()
+	: voxel_grid_TSDF(NULL), voxel_grid_weight(NULL), vol_(NULL), grp_(NULL), save_on_destroy_(true), scan_(NULL), fill_on_(false), fill_(), ground_on_(false), ground_(), ground_select_(TSDF_SCAN_DROP_GROUND)
 {
 	tsdf_config_default(&cfg_, h, w);  // 200^3 @ 4 mm, trunc 20 mm, TUM K (ref: include/tsdf.hpp:63-67,96)
 	cfg_.id = MOid;
@@ -39,14 +39,14 @@ TSDF::TSDF(int h, int w, int MOid, std::vector<float> base2world_, std::vector<f
 }
 
 TSDF::TSDF(const tsdf_config &cfg)
-	: voxel_grid_TSDF(NULL), voxel_grid_weight(NULL), cfg_(cfg), vol_(NULL), grp_(NULL), save_on_destroy_(true), scan_(NULL), fill_on_(false), fill_()
+	: voxel_grid_TSDF(NULL), voxel_grid_weight(NULL), cfg_(cfg), vol_(NULL), grp_(NULL), save_on_destroy_(true), scan_(NULL), fill_on_(false), fill_(), ground_on_(false), ground_(), ground_select_(TSDF_SCAN_DROP_GROUND)
 {
 	init();
 }
 
 TSDF::TSDF(const tsdf_config &cfg, const std::vector<int> &devices)
 	: voxel_grid_TSDF(NULL), voxel_grid_weight(NULL), cfg_(cfg), vol_(NULL), grp_(NULL), devices_(devices),
-	  save_on_destroy_(true), scan_(NULL), fill_on_(false), fill_()
+	  save_on_destroy_(true), scan_(NULL), fill_on_(false), fill_(), ground_on_(false), ground_(), ground_select_(TSDF_SCAN_DROP_GROUND)
 {
 	cfg_.z_begin = 0;
 	cfg_.z_end = cfg_.dim_z;
@@ -97,6 +97,13 @@ void TSDF::SetScanFill(int max_span_u, int max_span_v, float jump_rel)
 	fill_on_ = true;
 }
 
+void TSDF::SetScanGround(const tsdf_scan_ground_params &params, int select)
+{
+	ground_ = params;
+	ground_select_ = select;
+	ground_on_ = true;
+}
+
 void TSDF::IntegrateRange(float *range_im, std::vector<float> cam2world_vec)
 {
 	float cam2world[16] = {0};
@@ -117,6 +124,17 @@ void TSDF::IntegrateScan(const float *xyzi, size_t n, const float velo2img[12], 
 {
 	float cam2world[16] = {0};
 	for (size_t i = 0; i < 16 && i < cam2world_vec.size(); ++i) cam2world[i] = cam2world_vec[i];
+	if (ground_on_) {   // the ground marked on the device first, and only the points that ground_select_ keeps projected
+		const tsdf_scan_fill_params *fill = fill_on_ ? &fill_ : NULL;
+		if (!grp_) {
+			if (tsdf_integrate_scan_ground(vol_, velo2img, &ground_, ground_select_, fill, xyzi, (int64_t)n, cam2world) != TSDF_OK) fail("tsdf_integrate_scan_ground", __LINE__);
+			return;
+		}
+		float *depth = scan_image();
+		if (tsdf_scan_project_ground(scan_, velo2img, cfg_.cam_K, &ground_, ground_select_, fill, xyzi, (int64_t)n, NULL, depth, NULL, NULL, NULL, NULL) != TSDF_OK) fail("tsdf_scan_project_ground", __LINE__);
+		if (tsdf_group_integrate(grp_, depth, cam2world) != TSDF_OK) fail("tsdf_group_integrate", __LINE__);
+		return;
+	}
 	if (!grp_) {
 		if (fill_on_) {
 			if (tsdf_integrate_scan_filled(vol_, velo2img, &fill_, xyzi, (int64_t)n, cam2world) != TSDF_OK) fail("tsdf_integrate_scan_filled", __LINE__);

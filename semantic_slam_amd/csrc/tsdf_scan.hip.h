@@ -50,14 +50,10 @@ __device__ __forceinline__ float scan_depth_of(const ScanCamera k, int u, int v,
     return (range > 0.0f && range <= FLT_MAX) ? range / rim : 0.0f;
 }
 
-// One point per lane, read as one 16-byte float4 (the compiler, seeing the intensity unused, issues it as ONE 12-byte
-// global_load_dwordx3 of the same address); one 8-byte atomic maximum per accepted point.
-__global__ __launch_bounds__(256) void scan_splat(const ScanProjection p, const float4 *__restrict__ points, int64_t n_points,
-                                                  unsigned long long *__restrict__ keys)
+// The projection of point i = q into its pixel's key, the whole of the rule above: what scan_splat does for every point, and
+// the selecting splat of tsdf_scan_ground.hip.h for the points it keeps.
+__device__ __forceinline__ void scan_splat_point(const ScanProjection &p, const float4 q, int64_t i, unsigned long long *__restrict__ keys)
 {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_points) return;
-    const float4 q = points[i];
     const float h0 = ((p.m[0] * q.x + p.m[1] * q.y) + p.m[2] * q.z) + p.m[3];
     const float h1 = ((p.m[4] * q.x + p.m[5] * q.y) + p.m[6] * q.z) + p.m[7];
     const float h2 = ((p.m[8] * q.x + p.m[9] * q.y) + p.m[10] * q.z) + p.m[11];
@@ -69,6 +65,16 @@ __global__ __launch_bounds__(256) void scan_splat(const ScanProjection p, const 
     if (!(range > 0.0f)) return;
     const unsigned long long key = ((unsigned long long)(i + 1) << 32) | (unsigned long long)__float_as_uint(range);
     atomicMax(&keys[(size_t)v * p.W + u], key);
+}
+
+// One point per lane, read as one 16-byte float4 (the compiler, seeing the intensity unused, issues it as ONE 12-byte
+// global_load_dwordx3 of the same address); one 8-byte atomic maximum per accepted point.
+__global__ __launch_bounds__(256) void scan_splat(const ScanProjection p, const float4 *__restrict__ points, int64_t n_points,
+                                                  unsigned long long *__restrict__ keys)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_points) return;
+    scan_splat_point(p, points[i], i, keys);
 }
 
 // One pixel per lane: the winning key's range into range_out and / or its depth into depth_out (either may be null), the key

@@ -14,6 +14,7 @@ struct tsdf_scanner {
     HostPtr<float> h_images;         // the pinned mirror of d_images, and behind it of d_counts
     DevPtr<char> d_fill;             // the gap fill's (tsdf_scan_fill_host.hip.h, at the first call that fills): filled depth |
     HostPtr<char> h_fill;            // one count per tile | kind; and its pinned mirror
+    ScanGroundStage ground;          // the ground marking's (tsdf_scan_ground_host.hip.h, at the first call that marks)
 };
 
 namespace {
@@ -53,27 +54,52 @@ tsdfk::ScanCamera scan_camera(const float cam_K[9])
 
 // The scan's points into HBM and their keys into the key image, all queued on `st`; the caller's buffer is free when this
 // returns.  n_points == 0 queues nothing but the key image's first clear.
-int scan_splat_points(ScanStage &s, const float velo2img[12], int H, int W, const float *points_host, int64_t n_points, hipStream_t st)
+// The three steps of it, which the ground marking (tsdf_scan_ground_host.hip.h) takes one by one with its own kernels in
+// between: the key image there and all zero; the last scan's work over; the points in HBM.
+int scan_keys_ready(ScanStage &s, size_t n_px, hipStream_t st)
 {
-    const size_t n_px = (size_t)H * W;
     if (!s.pts_read) HIP_TRY(event_create(s.pts_read));
     if (!s.d_keys.fits(n_px)) { HIP_TRY(s.d_keys.ensure(n_px)); s.keys_clean = false; }
     if (!s.keys_clean) HIP_TRY(hipMemsetAsync(s.d_keys, 0, n_px * sizeof(unsigned long long), st));
     s.keys_clean = true;
-    if (n_points == 0) return TSDF_OK;
-    if (s.pts_in_use) HIP_TRY(hipEventSynchronize(s.pts_read));   // the last scan's copy and kernel have run: both blocks are free
+    return TSDF_OK;
+}
+int scan_points_free(ScanStage &s)
+{
+    if (!s.pts_read) HIP_TRY(event_create(s.pts_read));
+    if (s.pts_in_use) HIP_TRY(hipEventSynchronize(s.pts_read));   // the last scan's copy and kernels have run: both blocks are free
     s.pts_in_use = false;
+    return TSDF_OK;
+}
+int scan_upload_points(ScanStage &s, const float *points_host, int64_t n_points, hipStream_t st)
+{
+    int rc = scan_points_free(s);
+    if (rc) return rc;
     HIP_TRY(s.h_pts.ensure((size_t)n_points));
     HIP_TRY(s.d_pts.ensure((size_t)n_points));
     const size_t bytes = (size_t)n_points * sizeof(float4);
     tsdf_host::copy_to_pinned(s.h_pts.get(), points_host, bytes);
     HIP_TRY(hipMemcpyAsync(s.d_pts, s.h_pts, bytes, hipMemcpyHostToDevice, st));
     s.pts_in_use = true;            // (from here on, whatever fails: the copy is queued)
-    s.keys_clean = false;
+    return TSDF_OK;
+}
+tsdfk::ScanProjection scan_projection_of(const float velo2img[12], int H, int W)
+{
     tsdfk::ScanProjection p;
     std::memcpy(p.m, velo2img, sizeof p.m);
     p.H = H; p.W = W;
-    hipLaunchKernelGGL(tsdfk::scan_splat, dim3(scan_blocks(n_points)), dim3(256), 0, st, p, s.d_pts.get(), n_points, s.d_keys.get());
+    return p;
+}
+
+int scan_splat_points(ScanStage &s, const float velo2img[12], int H, int W, const float *points_host, int64_t n_points, hipStream_t st)
+{
+    int rc = scan_keys_ready(s, (size_t)H * W, st);
+    if (rc || n_points == 0) return rc;
+    rc = scan_upload_points(s, points_host, n_points, st);
+    if (rc) return rc;
+    s.keys_clean = false;
+    hipLaunchKernelGGL(tsdfk::scan_splat, dim3(scan_blocks(n_points)), dim3(256), 0, st, scan_projection_of(velo2img, H, W), s.d_pts.get(),
+                       n_points, s.d_keys.get());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(s.pts_read, st));
     return TSDF_OK;
