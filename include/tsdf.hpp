@@ -16,6 +16,8 @@
 //                                process (tsdf_group_*): Integrate fans the frame out, the destructor gathers
 //     IntegrateRange(), IntegrateScan()   Integrate for the reference's second sensor (mSensor == 1): an image of lidar
 //                                ranges, or the Velodyne scan itself, made into z-depth on the device
+//     TrackScan()                estimate the pose IntegrateScan needs from the scan and the volume themselves, point to signed
+//                                distance (csrc/tsdf_scan_track.hip.h): the lidar path's own tracker
 //     SetScanFill(), ClearScanFill()   fill the gaps between lidar beams in front of IntegrateRange / IntegrateScan
 //                                (csrc/tsdf_scan_fill.hip.h); off by default
 //     SetScanGround(), ClearScanGround()   mark the ground of a scan and keep it out of (or alone in) IntegrateScan
@@ -77,6 +79,18 @@ class TSDF
 	*/
 	void IntegrateScan(const float *xyzi, size_t n, const float velo2img[12], std::vector<float> cam2world_vec);
 
+	/** Refine the camera pose of one Velodyne scan against the fused volume (not in the reference, which takes every pose of
+	its lidar call site from a stereo SLAM run: ref: examples/label_instance_lidar.cpp:36-40): tsdf_scan_track with
+	tsdf_scan_track_params_default, started from velo2world = cam2world_vec * velo2cam.  With SetScanGround on, the scan's
+	ground is marked first and left out of the tracking (drop_flag 1, whatever select says).  The volume is only read.
+	@param xyzi, n the scan as IntegrateScan takes it
+	@param velo2cam 16 floats, row-major 4x4: scanner frame to camera frame (tsdf_scan_pose composes it)
+	@param cam2world_vec in: the guess; out: the refined pose, velo2world * inverse(velo2cam) in tsdf_multiply_matrix's order
+	@return false when the track is lost (or velo2cam is singular): cam2world_vec is then left as it was
+	A multi-device object is refused: tracking needs the whole grid on one device.
+	*/
+	bool TrackScan(const float *xyzi, size_t n, const float velo2cam[16], std::vector<float> &cam2world_vec);
+
 	/** From here on IntegrateRange and IntegrateScan fill the gaps between beams in their z-depth image before it is
 	integrated (not in the reference, whose lidar call site fuses the sparse image): inverse depth is interpolated between
 	the nearest sources at most max_span_u pixels apart along rows, then at most max_span_v apart along columns, never
@@ -136,5 +150,6 @@ class TSDF
 	bool ground_on_;                   // SetScanGround: IntegrateScan goes through the library's selecting forms
 	tsdf_scan_ground_params ground_;
 	int ground_select_;
+	std::vector<unsigned char> scan_flags_;   // TrackScan with SetScanGround: the scan's flags
 };
 #endif // TSDF_HIP_DROPIN_TSDF_HPP

@@ -1049,6 +1049,60 @@ int tsdf_scan_project_ground(tsdf_scanner *scanner, const float velo2img[12], co
 int tsdf_integrate_scan_ground(tsdf_volume *vol, const float velo2img[12], const tsdf_scan_ground_params *ground_params,
                                int32_t select, const tsdf_scan_fill_params *fill_params, const float *points_host,
                                int64_t n_points, const float cam2world[16]);
+/*
+ * Tracking a scan against the fused volume, point to signed distance.  Every tsdf_integrate_scan* call needs the pose of the
+ * scan; the reference takes it from a stereo SLAM run beside it (ref: examples/label_instance_lidar.cpp:36-40).  These calls
+ * estimate it from the scan and the volume alone: every point, taken through the pose estimate, should land where the
+ * signed distance is zero, so the trilinearly sampled TSDF value is the residual and its gradient the normal.  No image is
+ * made and no camera enters it: the whole revolution takes part.  The rule is stated exactly in csrc/tsdf_scan_track.hip.h
+ * and restated in tests/scan_track_spec.py; every pointer here is host memory, borrowed for the call only.  The volume is
+ * only read.  Whole-grid handles only: a z-slab and a slab of a tsdf_group are refused, as tsdf_track refuses them.
+ *   weight_thresh            finite: all eight corners of a point's cell must have a weight above it
+ *   resid_thresh             metres, finite, > 0: a pair whose |signed distance| exceeds it is left out
+ *   min_range_m, max_range_m finite, 0 <= min <= max: a point takes part when its distance from the scanner lies in
+ *                            [min, max] (compared as float32 squares)
+ *   n_levels, iters          1 ... 3 levels, level l takes every 2^l-th point, in scan order; iters[l] >= 0 iterations of
+ *                            level l, coarsest level first (0 skips a level)
+ *   min_pairs                >= 0: an iteration with fewer pairs loses the track
+ *   drop_flag                -1: flags_host is not looked at; 0 ... 255: a point whose flag equals it is left out.
+ *                            flags_host: n_points bytes or NULL; tsdf_scan_mark_ground's flags_host fits as it is, and
+ *                            drop_flag = 1 then tracks without the ground
+ *   eps_rot, eps_trans       finite, > 0: a level ends when a step turns by less than eps_rot radians and moves by less than
+ *                            eps_trans metres
+ * tsdf_scan_track_params_default gives 0.9, the handle's truncation distance, 2.5 (the ground rule's nearest range of a
+ * ground step) and 80, 3 levels of {10, 5, 4} iterations, 300, -1, 1e-5 and 1e-5: choices, not measurements.  Host only,
+ * needs no device.
+ * tsdf_scan_pose composes velo2cam = [R_rect 0; 0 1] * [R_velo t_velo; 0 1] (tsdf_scan_projection's product without P_rect)
+ * in tsdf_multiply_matrix's fp32 operation order; host arithmetic only, needs no device.  The caller forms velo2world =
+ * cam2world * velo2cam for the guess and gets back to a camera pose with tsdf_invert_matrix and tsdf_multiply_matrix.
+ *   points_host, n_points    as for tsdf_scan_project; 0 <= n_points <= 2147483584 (2^31 - 64: one lane per point).
+ *                            n_points == 0 is valid (points_host may then be NULL) and loses the track
+ *   guess_velo2world         4 x 4 row-major, scanner frame to world; only the first three rows are read, and they must be
+ *                            finite.  Rigidity is the caller's duty
+ *   tsdf_scan_track          the frames the handle has collected are applied first; returns when the result is on the host.
+ *                            status 0: the finest level that ran ended by the eps test, 1: its iterations ran out, 2: lost
+ *                            -- not an error: TSDF_OK, and velo2world is then the guess's own bits.  iters_run per level;
+ *                            pairs and rmse (metres) of the last iteration that ran
+ *   tsdf_scan_track_system   the 29 sums of ONE pass of `level` (0 <= level < n_levels) at the pose velo2world, no step:
+ *                            21 of J^T J (upper triangle, row-major), 6 of J^T r, sum r^2, the pair count; returns when
+ *                            they are on the host.  What the tests hold against the restatement
+ * Two calls with the same volume, scan and pose give the same bits: the sums are made in a fixed order.
+ */
+typedef struct tsdf_scan_track_params {
+    float weight_thresh, resid_thresh;
+    float min_range_m, max_range_m;
+    int32_t n_levels; int32_t iters[3];
+    int32_t min_pairs;
+    int32_t drop_flag;
+    float eps_rot, eps_trans;
+} tsdf_scan_track_params;
+typedef struct tsdf_scan_track_result { float velo2world[16]; int32_t status; int32_t iters_run[3]; int32_t pairs; float rmse; } tsdf_scan_track_result;
+int tsdf_scan_track_params_default(const tsdf_config *cfg, tsdf_scan_track_params *out);
+int tsdf_scan_pose(const float R_rect[9], const float R_velo[9], const float t_velo[3], float velo2cam_out[16]);
+int tsdf_scan_track(tsdf_volume *vol, const tsdf_scan_track_params *p, const float *points_host, int64_t n_points,
+                    const uint8_t *flags_host /* may be NULL */, const float guess_velo2world[16], tsdf_scan_track_result *out);
+int tsdf_scan_track_system(tsdf_volume *vol, const tsdf_scan_track_params *p, const float *points_host, int64_t n_points,
+                           const uint8_t *flags_host, const float velo2world[16], int32_t level, double system_out[29]);
 
 /*
  * One grid over several devices in ONE process.  The reference's host is a C++ program that owns its TSDFs directly

@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "tsdf_integrate_scan_filled",
     "tsdf_scan_ground_params_default", "tsdf_scan_mark_ground", "tsdf_scan_project_ground", "tsdf_integrate_scan_ground",
     "tsdf_scan_ground_tables",
+    "tsdf_scan_track_params_default", "tsdf_scan_pose", "tsdf_scan_track", "tsdf_scan_track_system",
     "tsdf_object_origin", "tsdf_batch_create", "tsdf_batch_destroy", "tsdf_batch_size", "tsdf_batch_volume",
     "tsdf_batch_integrate_device", "tsdf_batch_sync",
     "tsdf_group_create", "tsdf_group_destroy", "tsdf_group_size", "tsdf_group_voxels", "tsdf_group_volume",
@@ -230,7 +231,20 @@ class ScanGroundParams(C.Structure):
                 ("mark_upper", C.c_int32)]
 
 
-SCAN_DROP_GROUND, SCAN_ONLY_GROUND = 0, 1       # tsdf_scan_project_ground's and tsdf_integrate_scan_ground's `select`
+class ScanTrackParams(C.Structure):
+    """Mirror of `struct tsdf_scan_track_params` (include/tsdf_hip.h)."""
+    _fields_ = [("weight_thresh", C.c_float), ("resid_thresh", C.c_float), ("min_range_m", C.c_float), ("max_range_m", C.c_float),
+                ("n_levels", C.c_int32), ("iters", C.c_int32 * 3), ("min_pairs", C.c_int32), ("drop_flag", C.c_int32),
+                ("eps_rot", C.c_float), ("eps_trans", C.c_float)]
+
+
+class ScanTrackResult(C.Structure):
+    """Mirror of `struct tsdf_scan_track_result` (include/tsdf_hip.h)."""
+    _fields_ = [("velo2world", C.c_float * 16), ("status", C.c_int32), ("iters_run", C.c_int32 * 3), ("pairs", C.c_int32),
+                ("rmse", C.c_float)]
+
+
+SCAN_DROP_GROUND, SCAN_ONLY_GROUND = 0, 1      # tsdf_scan_project_ground's and tsdf_integrate_scan_ground's `select`
 
 TRACK_STATUS = {0: "converged", 1: "iterations exhausted", 2: "lost"}
 
@@ -391,6 +405,10 @@ def load():
     L.tsdf_scan_project_ground.argtypes = [vp, vp, vp, vp, C.c_int32, vp, vp, C.c_int64, vp, vp, vp, i64p, i64p, i64p]
     L.tsdf_integrate_scan_ground.argtypes = [vp, vp, vp, C.c_int32, vp, vp, C.c_int64, vp]
     L.tsdf_scan_ground_tables.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.tsdf_scan_track_params_default.argtypes = [C.POINTER(TsdfConfig), C.POINTER(ScanTrackParams)]
+    L.tsdf_scan_pose.argtypes = [vp, vp, vp, vp]
+    L.tsdf_scan_track.argtypes = [vp, C.POINTER(ScanTrackParams), vp, C.c_int64, vp, vp, C.POINTER(ScanTrackResult)]
+    L.tsdf_scan_track_system.argtypes = [vp, C.POINTER(ScanTrackParams), vp, C.c_int64, vp, vp, C.c_int32, vp]
     L.tsdf_object_origin.argtypes = [C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp]
     L.tsdf_batch_create.argtypes = [C.POINTER(TsdfConfig), C.c_int32, C.POINTER(vp)]
     L.tsdf_batch_destroy.argtypes = [vp]
@@ -773,6 +791,33 @@ def _scan_points(points):
     if pts.ndim != 2 or pts.shape[1] != 4:
         raise ValueError(f"expected points of shape [n, 4], got {pts.shape}")
     return pts
+
+
+def scan_track_params_default(cfg):
+    """Scan tracking parameters for a volume's config (include/tsdf_hip.h): weight_thresh 0.9, resid_thresh = the truncation
+    distance, ranges 2.5 ... 80 m, 3 levels of {10, 5, 4} iterations, min_pairs 300, drop_flag -1, eps 1e-5 rad / 1e-5 m
+    (no device)."""
+    p = ScanTrackParams()
+    check(load().tsdf_scan_track_params_default(C.byref(cfg), C.byref(p)), "tsdf_scan_track_params_default")
+    return p
+
+
+def scan_pose(R_rect, R_velo, t_velo):
+    """velo2cam [4, 4] = [R_rect 0; 0 1] * [R_velo t_velo; 0 1] in the library's fp32 operation order (no device)."""
+    out = np.zeros(16, np.float32)
+    Rr, Rv, t = _f32(R_rect, 9), _f32(R_velo, 9), _f32(t_velo, 3)
+    check(load().tsdf_scan_pose(Rr.ctypes.data, Rv.ctypes.data, t.ctypes.data, out.ctypes.data), "tsdf_scan_pose")
+    return out.reshape(4, 4)
+
+
+def _scan_flags(flags, n):
+    """A scan's flags as contiguous uint8 [n], or None."""
+    if flags is None:
+        return None
+    f = np.ascontiguousarray(flags, dtype=np.uint8).ravel()
+    if f.size != n:
+        raise ValueError(f"expected {n} flags, got {f.size}")
+    return f
 
 
 class Scanner:
@@ -1435,6 +1480,36 @@ class Volume:
         A[np.triu_indices(6)] = out[:21]
         A = A + np.triu(A, 1).T
         return A, out[21:27].copy(), float(out[27]), int(out[28])
+
+    # -- tracking a lidar scan --------------------------------------------------------------
+    def track_scan(self, points, guess_velo2world, params=None, flags=None):
+        """Track a lidar scan [n, 4] against this volume, point to signed distance (csrc/tsdf_scan_track.hip.h).  Returns
+        (velo2world [4, 4] float32, status dict with status, status_name, iters_run, pairs, rmse); a lost run returns the
+        guess itself with status 2.  params: a ScanTrackParams, default scan_track_params_default(cfg); flags: n bytes
+        (Scanner.mark_ground's), looked at when params.drop_flag >= 0.  Reads the volume only."""
+        p = scan_track_params_default(self.cfg) if params is None else params
+        pts = _scan_points(points)
+        f = _scan_flags(flags, len(pts))
+        g = _f32(guess_velo2world, 16)
+        res = ScanTrackResult()
+        check(self.lib.tsdf_scan_track(self._h, C.byref(p), pts.ctypes.data if len(pts) else None, len(pts),
+                                       None if f is None or not len(pts) else f.ctypes.data, g.ctypes.data, C.byref(res)), "tsdf_scan_track")
+        pose = np.array(res.velo2world, np.float32).reshape(4, 4)
+        return pose, {"status": res.status, "status_name": TRACK_STATUS[res.status], "iters_run": list(res.iters_run),
+                      "pairs": res.pairs, "rmse": res.rmse}
+
+    def track_scan_system(self, points, velo2world, level=0, params=None, flags=None):
+        """The 29 sums of one scan tracking pass at `level` and the pose velo2world (tsdf_scan_track_system): 21 of J^T J (upper
+        triangle), 6 of J^T r, sum r^2, the pair count; float64 [29]."""
+        p = scan_track_params_default(self.cfg) if params is None else params
+        pts = _scan_points(points)
+        f = _scan_flags(flags, len(pts))
+        m = _f32(velo2world, 16)
+        out = np.zeros(29, np.float64)
+        check(self.lib.tsdf_scan_track_system(self._h, C.byref(p), pts.ctypes.data if len(pts) else None, len(pts),
+                                              None if f is None or not len(pts) else f.ctypes.data, m.ctypes.data, level, out.ctypes.data),
+              "tsdf_scan_track_system")
+        return out
 
     # -- extent -----------------------------------------------------------------------------
     def extent(self, params=None):

@@ -52,6 +52,7 @@
 #include "tsdf_scan.hip.h"
 #include "tsdf_scan_fill.hip.h"
 #include "tsdf_scan_ground.hip.h"
+#include "tsdf_scan_track.hip.h"
 #ifdef TSDF_EXPERIMENTS
 #include "tsdf_experiments.hip.h"
 #endif
@@ -255,6 +256,13 @@ struct tsdf_volume {
     // lidar scans (tsdf_integrate_scan), allocated on first use: a handle that never sees a scan allocates nothing
     ScanStage scan;
     ScanGroundStage ground;          // ... and the ground marking in front of it (tsdf_integrate_scan_ground), likewise
+    // tracking a scan (tsdf_scan_track*), allocated on first use: the partial rows of a pass and the pose state in one block
+    // of HBM and the state's pinned copy (no size of the scan enters them; the points go through `scan`), and the points'
+    // flags in HBM and pinned, grown with the scan at the first call that brings flags
+    DevBuf<char> d_scan_track;
+    HostPtr<tsdfk::TrackState> h_scan_track;
+    DevBuf<uint8_t> d_scan_flags;
+    HostBuf<uint8_t> h_scan_flags;
 };
 
 using tsdf_host::kBatchSideStreams;
@@ -1745,6 +1753,7 @@ int tsdf_upload_colour(tsdf_volume *v, const uint32_t *colour_host)
 #include "tsdf_scan_host.hip.h"
 #include "tsdf_scan_fill_host.hip.h"
 #include "tsdf_scan_ground_host.hip.h"
+#include "tsdf_scan_track_host.hip.h"
 #include "tsdf_extract_host.hip.h"
 #include "tsdf_group.hip.h"
 #include "tsdf_diag.hip.h"

@@ -148,6 +148,33 @@ void TSDF::IntegrateScan(const float *xyzi, size_t n, const float velo2img[12], 
 	if (tsdf_group_integrate(grp_, depth, cam2world) != TSDF_OK) fail("tsdf_group_integrate", __LINE__);
 }
 
+bool TSDF::TrackScan(const float *xyzi, size_t n, const float velo2cam[16], std::vector<float> &cam2world_vec)
+{
+	float cam2world[16] = {0}, cam2velo[16], guess[16];
+	for (size_t i = 0; i < 16 && i < cam2world_vec.size(); ++i) cam2world[i] = cam2world_vec[i];
+	if (!tsdf_invert_matrix(velo2cam, cam2velo)) return false;
+	tsdf_multiply_matrix(cam2world, velo2cam, guess);
+	tsdf_volume *vol = vol_;   // (a multi-device object: slab 0, which the library refuses by name)
+	if (grp_ && tsdf_group_volume(grp_, 0, &vol) != TSDF_OK) fail("tsdf_group_volume", __LINE__);
+	tsdf_scan_track_params p;
+	if (tsdf_scan_track_params_default(&cfg_, &p) != TSDF_OK) fail("tsdf_scan_track_params_default", __LINE__);
+	const uint8_t *flags = NULL;
+	if (ground_on_ && n > 0) {   // the ground marked on the device first, and left out
+		const int device = devices_.empty() ? cfg_.device : devices_[0];
+		if (!scan_ && tsdf_scanner_create(device, cfg_.im_height, cfg_.im_width, &scan_) != TSDF_OK) fail("tsdf_scanner_create", __LINE__);
+		scan_flags_.resize(n);
+		if (tsdf_scan_mark_ground(scan_, &ground_, xyzi, (int64_t)n, scan_flags_.data(), NULL, NULL, NULL) != TSDF_OK) fail("tsdf_scan_mark_ground", __LINE__);
+		flags = scan_flags_.data();
+		p.drop_flag = 1;
+	}
+	tsdf_scan_track_result res;
+	if (tsdf_scan_track(vol, &p, xyzi, (int64_t)n, flags, guess, &res) != TSDF_OK) fail("tsdf_scan_track", __LINE__);
+	if (res.status == 2) return false;
+	tsdf_multiply_matrix(res.velo2world, cam2velo, cam2world);
+	cam2world_vec.assign(cam2world, cam2world + 16);
+	return true;
+}
+
 void TSDF::Sync()
 {
 	if ((grp_ ? tsdf_group_sync(grp_) : tsdf_sync(vol_)) != TSDF_OK) fail("tsdf_sync", __LINE__);
